@@ -18,7 +18,14 @@ line is marked `"baseline_only": true` and its metric says so.  `auto` = the rou
 `new` block by block against an fp32 truth and `round1`, and times both); when it does not end on `new` the run EXITS with
 status 3 instead of printing a MIOpen-backed headline.
 
-Extra objects on the line:
+A plain run sets up, settles, warms up, times the K steps, writes `--dump-outputs DIR` if given and prints the line (metric,
+value, unit, higher_is_better, dtype, ms_per_step = milliseconds of one timed step, ...).  The warm-up and timed steps start from
+the seeded initial training state (reset after settling), so the same arguments give the same inputs and the same computation.
+`--dump-outputs DIR` writes what the last timed step computed: DIR/{loss,logits,params,buffers}.npy, float32 (dump_outputs).
+
+`--full` adds everything else (secondary, roofline and cpu_baseline can each be switched off by its --no-* flag):
+  host_issue_ms_one_step_idle_queue, config.nodes_per_step, config.module_fallbacks_per_step   one more replayed and one
+                more eager step after the timed region (what actually ran: single-node blocks, module fallbacks)
   secondary     default run only (N = 1, CoTNet-50 B = 80): BASELINE configs 4 (CoTNeXt-101, B = 64) and 5 (SE-CoTNetD-152 320^2,
                 B = 64) and config 3 at the reference's fp32 precision, each measured by a short child run of this script on the
                 same GPU with the same kernel set and timing protocol (8 timed steps); `--no-secondary` skips them.
@@ -54,8 +61,16 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--settle-seconds", type=float, default=30.0,
-                    help="untimed settling before the warm-up steps: chunks of 10 steps until three agree within 1 %% (0 = off)")
+    ap.add_argument("--settle-seconds", type=float, default=10.0,
+                    help="untimed settling before the warm-up steps: chunks of 10 steps until three agree within 1 %% (0 = off); "
+                         "the training state is reset to its seeded initial values after it")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: host issue time into an idle queue, node / fallback counters, the roofline "
+                         "object (kernel timing, PMC passes), cpu_baseline and the secondary configurations.  Off by default: a plain "
+                         "run sets up, settles, warms up, times --steps steps, writes --dump-outputs and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32): loss, logits, "
+                         "and for training the updated fp32 parameters (a fixed sample when larger) and BatchNorm buffers")
     ap.add_argument("--batch", type=int, default=80, help="images per GPU (reference recipe: 80)")
     ap.add_argument("--model", default="cotnet50")
     ap.add_argument("--img", type=int, default=224)
@@ -518,7 +533,7 @@ def secondary_lines(timeout_s=170):
     out = {}
     for key, what, extra in SECONDARY:
         cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", "8", "--warmup", "3", "--settle-seconds", "8",
-               "--no-cpu-baseline", "--no-kernel-timing", "--no-secondary", "--kernels", "new"] + extra
+               "--full", "--no-cpu-baseline", "--no-kernel-timing", "--no-secondary", "--kernels", "new"] + extra
         t0 = time.perf_counter()
         try:
             env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "COT_KERNEL_SUMMARY")}
@@ -598,6 +613,62 @@ def measure_agg_traffic(key, timeout_s=90):
         sys.path.pop(0)
 
 
+def training_state(model, opt):
+    """every tensor a step writes in place: the parameters, the buffers (BatchNorm running statistics) and the optimizer's state
+    (FlatSGD: fp32 masters, momentum, EMA per bucket; torch.optim keeps its momentum in `opt.state`, made at the first step)"""
+    ts = list(model.parameters()) + list(model.buffers())
+    st = getattr(opt, "state", None)
+    if isinstance(st, list):
+        ts += [v for d in st for v in d.values() if v is not None] + list(getattr(opt, "_buf_ema", []))
+    return ts
+
+
+def reset_training_state(state, initial, opt):
+    """copy the values of training_state() back in place (the captured graph keeps reading the same tensors)"""
+    from cotnet_amd.cot_layer_fused import invalidate_packs
+    with torch.no_grad():
+        for t, t0 in zip(state, initial):
+            t.copy_(t0)
+        st = getattr(opt, "state", None)
+        if isinstance(st, dict):  # torch.optim.SGD: a zero momentum buffer steps exactly as the first step does (dampening 0)
+            for d in st.values():
+                for v in d.values():
+                    if torch.is_tensor(v) and v.is_floating_point():
+                        v.zero_()
+    invalidate_packs()  # (raw in-place writes: packings made ahead of time are stale)
+
+
+DUMP_PARAMS = 1 << 22  # --dump-outputs: parameters beyond this many are written as a fixed seeded sample of this size (16 MB)
+
+
+def dump_outputs(out_dir, loss, logits, model, opt):
+    """what the last timed step handed back, as out_dir/<name>.npy (float32): `loss` (training), `logits` [B, 1000], and for
+    training the state the step left: `params` = every parameter in model.parameters() order, flattened and concatenated (fp32
+    master copies where the optimizer keeps them; a sorted sample drawn by torch.randperm with seed 0 when there are more than
+    DUMP_PARAMS values) and `buffers` = the floating-point buffers (BatchNorm running statistics) in model.buffers() order.
+    -> {"dir": ..., "arrays": {name: shape}}"""
+    import numpy as np
+    torch.cuda.synchronize()
+    arrays = {}
+    if loss is not None:
+        arrays["loss"] = loss.detach().float().reshape(1)
+    arrays["logits"] = logits.float()
+    if opt is not None:
+        masters = opt.master_parameters() if hasattr(opt, "master_parameters") else {}
+        flat = torch.cat([masters.get(p, p).detach().float().reshape(-1) for p in model.parameters()])
+        if flat.numel() > DUMP_PARAMS:
+            idx = torch.randperm(flat.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_PARAMS].sort().values
+            flat = flat[idx.to(flat.device)]
+        arrays["params"] = flat
+        bufs = [b.detach().float().reshape(-1) for b in model.buffers() if b.is_floating_point()]
+        if bufs:
+            arrays["buffers"] = torch.cat(bufs)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a.cpu().numpy().astype(np.float32))
+    return {"dir": out_dir, "arrays": {name: list(a.shape) for name, a in arrays.items()}}
+
+
 def spawn_ranks(n):
     """`python bench.py --gpus N` without a launcher: re-execute this command line under torch.distributed.run, one rank
     per GPU on 127.0.0.1 (the driver's own launch line).  Returns the launcher's exit code."""
@@ -617,6 +688,8 @@ def spawn_ranks(n):
 def main():
     args = parse()
     if os.environ.get("COT_KERNEL_SUMMARY"):
+        if not (args.full and not args.no_kernel_timing):
+            raise SystemExit("bench.py: COT_KERNEL_SUMMARY comes from the kernel-timing steps: run with --full (and without --no-kernel-timing)")
         os.environ["COT_PROFILE_ALL"] = "1"  # (costs host time per launch: not for headline numbers)
     if args.probe_child:
         return probe_child(args)
@@ -720,6 +793,13 @@ def main():
     x = torch.randn(B, 3, args.img, args.img, device=dev).contiguous(memory_format=mf)
     t = torch.randint(0, 1000, (B,), device=dev)
 
+    last = {}  # the last step's logits (a graph replay rewrites the captured tensor in place): for --dump-outputs
+
+    def logits():
+        out = model(x).float()
+        last["logits"] = out.detach()
+        return out
+
     mixed = amp and args.precision == "mixed"
     if mixed:
         from cotnet_amd.flat_sgd import FlatSGD, to_mixed_bf16
@@ -733,14 +813,14 @@ def main():
 
         def step():
             opt.zero_grad()
-            loss = torch.nn.functional.cross_entropy(model(x).float(), t)
+            loss = torch.nn.functional.cross_entropy(logits(), t)
             loss.backward()
             opt.step()
             return loss
 
         def step_compute_only():  # (graph capture with N > 1: forward + backward fill the flat buckets, no collective inside)
             opt.zero_grad()
-            loss = torch.nn.functional.cross_entropy(model(x).float(), t)
+            loss = torch.nn.functional.cross_entropy(logits(), t)
             loss.backward()
             return loss
     elif args.mode == "train":
@@ -751,8 +831,7 @@ def main():
         def step():
             red.zero_grad()
             with torch.autocast("cuda", dtype=torch.bfloat16, enabled=amp):
-                out = model(x)
-                loss = torch.nn.functional.cross_entropy(out.float(), t)
+                loss = torch.nn.functional.cross_entropy(logits(), t)
             loss.backward()
             red.finish()
             opt.step()
@@ -762,7 +841,13 @@ def main():
 
         def step():
             with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16, enabled=amp and not mixed):
-                return model(x).float().sum()
+                return logits().sum()
+
+    # the warm-up and timed steps start from the seeded initial training state whatever the settling steps did: with the same
+    # arguments the last timed step then computes the same thing from run to run (--dump-outputs)
+    state = training_state(model, opt if args.mode == "train" else None)
+    initial = [s.detach().clone() for s in state]  # (detached: an autograd node on a parameter would keep its AccumulateGrad
+                                                   # node alive under the default stream, and the graph capture would abort)
 
     def barrier():
         if world > 1:
@@ -890,6 +975,9 @@ def main():
                 invalidate_packs()  # (the replayed SGD kernels moved the weights behind torch's version counters)
                 return graph_loss
         graph_form = "full" if (captured and (full or not reducing)) else ("deferred" if captured else "eager")
+    torch.cuda.synchronize()
+    reset_training_state(state, initial, opt if args.mode == "train" else None)
+    del initial
     for _ in range(args.warmup):
         loss = step()
     barrier()
@@ -906,28 +994,35 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     roctx_window(resume=False)
-    # host time to issue ONE step into an empty queue (the loop above blocks on the launch queue whenever the device is the
-    # slower side, so `issued` only bounds it from above)
-    t1 = time.perf_counter()
-    step()
-    issue_one = time.perf_counter() - t1
-    torch.cuda.synchronize()
-    # what actually ran: one more eager step with the node counters on (residual blocks of the model vs the single-node kinds taken)
-    from cotnet_amd import cot_layer_fused as _clf0
-    if args.graph and reducing:
-        opt.reducer.defer_comm = False  # (the eager steps from here on reduce from their hooks again)
-    _clf0.reset_node_counts()
-    from cotnet_amd import _lib as _lib0
-    _lib0.FALLBACKS.clear()  # (calls a wrapper handed back to the torch module it wraps during this one step: {} on the BASELINE configurations' hot path)
-    eager_step()
-    torch.cuda.synchronize()
-    module_fallbacks = dict(_lib0.FALLBACKS)
-    n_blocks = sum(1 for m in model.modules() if type(m).__name__ in ("Bottleneck", "CoTBottleneck"))
-    nodes_per_step = dict(_clf0.NODE_COUNTS, residual_blocks=n_blocks)
-    nodes_per_step["single_node_blocks"] = (f"{nodes_per_step['bottleneck'] + nodes_per_step['bottleneck_channel_major'] + nodes_per_step['split_attn_block'] + nodes_per_step['bottleneck_eval']}"
-                                            f"/{n_blocks}")
+    final_loss = float(loss.detach())
+    dumped = None
+    if args.dump_outputs and rank == 0:  # (before any further step moves the weights)
+        dumped = dump_outputs(args.dump_outputs, loss if args.mode == "train" else None, last["logits"], model,
+                              opt if args.mode == "train" else None)
+    issue_one, module_fallbacks, nodes_per_step = None, None, None
+    if args.full:
+        # host time to issue ONE step into an empty queue (the loop above blocks on the launch queue whenever the device is the
+        # slower side, so `issued` only bounds it from above)
+        t1 = time.perf_counter()
+        step()
+        issue_one = time.perf_counter() - t1
+        torch.cuda.synchronize()
+        # what actually ran: one more eager step with the node counters on (residual blocks of the model vs the single-node kinds taken)
+        from cotnet_amd import cot_layer_fused as _clf0
+        if args.graph and reducing:
+            opt.reducer.defer_comm = False  # (the eager steps from here on reduce from their hooks again)
+        _clf0.reset_node_counts()
+        from cotnet_amd import _lib as _lib0
+        _lib0.FALLBACKS.clear()  # (calls a wrapper handed back to the torch module it wraps during this one step: {} on the BASELINE configurations' hot path)
+        eager_step()
+        torch.cuda.synchronize()
+        module_fallbacks = dict(_lib0.FALLBACKS)
+        n_blocks = sum(1 for m in model.modules() if type(m).__name__ in ("Bottleneck", "CoTBottleneck"))
+        nodes_per_step = dict(_clf0.NODE_COUNTS, residual_blocks=n_blocks)
+        nodes_per_step["single_node_blocks"] = (f"{nodes_per_step['bottleneck'] + nodes_per_step['bottleneck_channel_major'] + nodes_per_step['split_attn_block'] + nodes_per_step['bottleneck_eval']}"
+                                                f"/{n_blocks}")
     recs, timing_steps = [], 0
-    if not args.no_kernel_timing:
+    if args.full and not args.no_kernel_timing:
         timing_steps = 3
         os.environ["COT_PROFILE_ALL"] = "1"  # events on every launch of the library (outside the timed region)
         # Every launch on ONE stream for these steps: an event pair around a launch also counts the time the kernel waits for CUs
@@ -944,7 +1039,6 @@ def main():
             recs = agg_mod.profile_end()
         finally:
             _clf.SIDE_WGRAD = _side
-    final_loss = float(loss.detach())
 
     tmax = torch.tensor([elapsed], device=dev, dtype=torch.float64)
     if world > 1:
@@ -1087,13 +1181,14 @@ def main():
                        "conv3x3": __import__("cotnet_amd.conv3x3g", fromlist=["MODE"]).MODE or "module",
                        "group_norm9": __import__("cotnet_amd.group_norm9", fromlist=["MODE"]).MODE or "module",
                        "cot_layer_single_node_enabled": __import__("cotnet_amd.cot_layer_fused", fromlist=["ENABLED"]).ENABLED,
-                       "nodes_per_step": nodes_per_step, "module_fallbacks_per_step": module_fallbacks,
+                       **({"nodes_per_step": nodes_per_step, "module_fallbacks_per_step": module_fallbacks} if args.full else {}),
                        "grad_sync": (f"RCCL all-reduce (AVG), flat {'fp32' if args.grad_dtype == 'fp32' else 'parameter-dtype'} buckets, side stream"
                                      if reducing else "none (1 GPU)")},
             "final_loss": round(final_loss, 4),
             # host time to issue a step (the timed loop's own duration before the final synchronize; with the device the longer
             # of the two the loop blocks on the launch queue, so this is an upper bound of the host's own work)
-            "host_issue_ms_per_step": round(issued / args.steps * 1e3, 3), "host_issue_ms_one_step_idle_queue": round(issue_one * 1e3, 3),
+            "host_issue_ms_per_step": round(issued / args.steps * 1e3, 3),
+            **({"host_issue_ms_one_step_idle_queue": round(issue_one * 1e3, 3)} if args.full else {}),
             **({"graph": ("forward + backward + bucket fills captured in one HIP graph after the settling steps; every warm-up / timed step = one "
                           "replay, then the buckets' all-reduces (RCCL, communication stream) and the flat SGD kernels issued eagerly"
                           + (f" [{graph_note}]" if graph_note else "")) if (reducing and graph_form == "deferred")
@@ -1101,13 +1196,14 @@ def main():
                       "stream, overlapping backward) and the flat SGD kernels inside it" if reducing else "") + "; warm-up and timed steps are replays")}
                if args.graph else
                ({"graph": graph_note} if graph_note else {"graph": "off: every step issued launch by launch"})),
-            "roofline": roofline,
+            **({"roofline": roofline} if args.full else {}),
+            **({"outputs": dumped} if dumped else {}),
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline()
         default_cfg = (args.model == "cotnet50" and args.img == 224 and args.batch == 80 and args.mode == "train" and mixed
                        and not explicit and not args.tune and not args.recipe and not graph_explicit and not args.eager)
-        if world == 1 and default_cfg and not args.no_secondary:
+        if world == 1 and default_cfg and args.full and not args.no_secondary:
             torch.cuda.empty_cache()  # (the children run on this GPU while this process is idle)
             line["secondary"] = secondary_lines()
             line["secondary"]["aggmix_config5"] = aggmix_config5()

@@ -21,9 +21,9 @@ python scripts/agg_traffic_from_pmc.py $O/ev_pmc_FETCH_SIZE $O/ev_pmc_WRITE_SIZE
 timeout 200 python scripts/bench_agg_abi.py --variants lds,dot2 --iters 20 --rounds 5 --out $O/ev_agg_abi.json > $O/ev_agg_abi.log 2>&1; tail -20 $O/ev_agg_abi.log | cut -c1-200
 timeout 300 python scripts/bench_conv_abi.py --iters 20 --json $O/ev_conv_abi.json > $O/ev_conv_abi.log 2>&1; tail -5 $O/ev_conv_abi.log | cut -c1-200
 T1=$(date +%s)
-timeout 900 python bench.py > $O/ev_bench_default.json 2> $O/ev_bench_default.err; echo "bench rc=$? wall=$(( $(date +%s) - T1 ))s"
+timeout 900 python bench.py --full > $O/ev_bench_default.json 2> $O/ev_bench_default.err; echo "bench rc=$? wall=$(( $(date +%s) - T1 ))s"
 cut -c1-600 $O/ev_bench_default.json
-timeout 300 python bench.py --mode fwd --no-cpu-baseline > $O/ev_bench_fwd.json 2> $O/ev_bench_fwd.err || tail -5 $O/ev_bench_fwd.err; cut -c1-300 $O/ev_bench_fwd.json
-timeout 300 python bench.py --mode fwd --graph --no-cpu-baseline --no-kernel-timing > $O/ev_bench_fwd_graph.json 2> $O/ev_bench_fwd_graph.err || tail -5 $O/ev_bench_fwd_graph.err; cut -c1-200 $O/ev_bench_fwd_graph.json
-timeout 300 python bench.py --recipe --no-cpu-baseline > $O/ev_bench_recipe.json 2> $O/ev_bench_recipe.err; cut -c1-300 $O/ev_bench_recipe.json
+timeout 300 python bench.py --full --mode fwd --no-cpu-baseline > $O/ev_bench_fwd.json 2> $O/ev_bench_fwd.err || tail -5 $O/ev_bench_fwd.err; cut -c1-300 $O/ev_bench_fwd.json
+timeout 300 python bench.py --full --mode fwd --graph --no-cpu-baseline --no-kernel-timing > $O/ev_bench_fwd_graph.json 2> $O/ev_bench_fwd_graph.err || tail -5 $O/ev_bench_fwd_graph.err; cut -c1-200 $O/ev_bench_fwd_graph.json
+timeout 300 python bench.py --full --recipe --no-cpu-baseline > $O/ev_bench_recipe.json 2> $O/ev_bench_recipe.err; cut -c1-300 $O/ev_bench_recipe.json
 echo "session wall=$(( $(date +%s) - T0 ))s"

@@ -12,7 +12,7 @@ timeout 300 python scripts/bench_conv_general.py --json $O/gen_conv_general.json
 for cfg in "fp32:--dtype fp32" "cotnext101:--model cotnext101_2x48d --batch 64" "secotnetd152:--model se_cotnetd_152_L --img 320 --batch 64"; do
   tag=${cfg%%:*}; flags=${cfg#*:}
   for ks in round1 new; do
-    timeout 400 python bench.py $flags --kernels $ks --steps 10 --warmup 3 --no-cpu-baseline > $O/gen_bench_${tag}_${ks}.json 2> $O/gen_bench_${tag}_${ks}.err || tail -5 $O/gen_bench_${tag}_${ks}.err
+    timeout 400 python bench.py --full $flags --kernels $ks --steps 10 --warmup 3 --no-cpu-baseline > $O/gen_bench_${tag}_${ks}.json 2> $O/gen_bench_${tag}_${ks}.err || tail -5 $O/gen_bench_${tag}_${ks}.err
     python -c "
 import json,sys
 try:

@@ -8,7 +8,7 @@ grep -E "passed|failed|^FAILED|^ERROR|rc=" $O/se_pytest.log | cut -c1-300 | tail
 for cfg in "secotnetd152:--model se_cotnetd_152_L --img 320 --batch 64" "cotnext101:--model cotnext101_2x48d --batch 64" "fp32:--dtype fp32"; do
   tag=${cfg%%:*}; flags=${cfg#*:}
   for ks in new round1; do
-    timeout 400 python bench.py $flags --kernels $ks --steps 10 --warmup 3 --no-cpu-baseline > $O/se_bench_${tag}_${ks}.json 2> $O/se_bench_${tag}_${ks}.err || tail -5 $O/se_bench_${tag}_${ks}.err
+    timeout 400 python bench.py --full $flags --kernels $ks --steps 10 --warmup 3 --no-cpu-baseline > $O/se_bench_${tag}_${ks}.json 2> $O/se_bench_${tag}_${ks}.err || tail -5 $O/se_bench_${tag}_${ks}.err
     python -c "
 import json
 try:

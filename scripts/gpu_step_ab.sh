@@ -10,7 +10,7 @@ if [ -n "$TESTS" ]; then
 fi
 for t in "$@"; do
   name=${t%%:*}; flags=${t#*:}
-  timeout 300 python bench.py --kernels new $flags --steps 20 --warmup 6 --no-cpu-baseline --no-kernel-timing > $O/${TAG}_step_$name.json 2> $O/${TAG}_step_$name.err || tail -3 $O/${TAG}_step_$name.err
+  timeout 300 python bench.py --full --kernels new $flags --steps 20 --warmup 6 --no-cpu-baseline --no-kernel-timing > $O/${TAG}_step_$name.json 2> $O/${TAG}_step_$name.err || tail -3 $O/${TAG}_step_$name.err
   python -c "
 import json
 d=json.load(open('$O/${TAG}_step_$name.json')); print('$name', d['value'], d['ms_per_step'], d['final_loss'], d['config'].get('tune'))"

@@ -12,5 +12,5 @@ import json
 d=json.load(open('$O/r05_abs_cm${v}_$rep.json')); print('cm=$v rep$rep', d['value'], d['ms_per_step'], d['settle'], d['host_issue_ms_per_step'])"
 done; done
 for v in 0 1; do
-COT_CM_LAYOUT=$v COT_KERNEL_SUMMARY=$O/r05_ksum_cm$v.json timeout 300 python bench.py --kernels new --steps 5 --warmup 3 --settle-seconds 3 --no-cpu-baseline --no-secondary > /dev/null 2> $O/r05_ksum_cm$v.err
+COT_CM_LAYOUT=$v COT_KERNEL_SUMMARY=$O/r05_ksum_cm$v.json timeout 300 python bench.py --full --kernels new --steps 5 --warmup 3 --settle-seconds 3 --no-cpu-baseline --no-secondary > /dev/null 2> $O/r05_ksum_cm$v.err
 done

@@ -17,8 +17,8 @@ timeout 200 python scripts/bench_agg_abi.py --variants lds,dot2 --iters 20 --rou
 timeout 300 python scripts/bench_conv_abi.py --iters 20 --json $O/ev5_conv_abi.json > $O/ev5_conv_abi.log 2>&1; tail -3 $O/ev5_conv_abi.log | cut -c1-200
 timeout 300 python scripts/probe_cnhw.py 30 > $O/ev5_probe_cnhw.log 2>&1; grep "^sum" $O/ev5_probe_cnhw.log | cut -c1-300
 T1=$(date +%s)
-timeout 900 python bench.py > $O/ev5_bench_default.json 2> $O/ev5_bench_default.err; echo "bench rc=$? wall=$(( $(date +%s) - T1 ))s"
+timeout 900 python bench.py --full > $O/ev5_bench_default.json 2> $O/ev5_bench_default.err; echo "bench rc=$? wall=$(( $(date +%s) - T1 ))s"
 cut -c1-400 $O/ev5_bench_default.json
-timeout 300 python bench.py --recipe --no-cpu-baseline --no-secondary --no-pmc > $O/ev5_bench_recipe.json 2> $O/ev5_bench_recipe.err; cut -c1-300 $O/ev5_bench_recipe.json
+timeout 300 python bench.py --full --recipe --no-cpu-baseline --no-secondary --no-pmc > $O/ev5_bench_recipe.json 2> $O/ev5_bench_recipe.err; cut -c1-300 $O/ev5_bench_recipe.json
 timeout 300 python bench.py --eager --no-cpu-baseline --no-secondary --no-pmc --no-kernel-timing > $O/ev5_bench_eager.json 2> $O/ev5_bench_eager.err; cut -c1-300 $O/ev5_bench_eager.json
 echo "session wall=$(( $(date +%s) - T0 ))s"

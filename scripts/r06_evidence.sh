@@ -11,7 +11,7 @@ timeout 1500 python -m pytest tests -m gpu -q --timeout 300 -rfEx -p no:cachepro
 grep -E "passed|failed|^FAILED|^ERROR|^XFAIL|^XPASS|rc=" $O/${T}_pytest.log | cut -c1-300 | tail -14
 timeout 180 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/${T}_smoke.log 2>&1; tail -2 $O/${T}_smoke.log | cut -c1-400
 T1=$(date +%s)
-timeout 900 python bench.py > $O/${T}_bench_default.json 2> $O/${T}_bench_default.err; echo "bench rc=$? wall=$(( $(date +%s) - T1 ))s"
+timeout 900 python bench.py --full > $O/${T}_bench_default.json 2> $O/${T}_bench_default.err; echo "bench rc=$? wall=$(( $(date +%s) - T1 ))s"
 cut -c1-400 $O/${T}_bench_default.json
 if [ "$2" != "notrace" ]; then
 bash scripts/gpu_trace_new.sh ${T}_trace --no-pmc > $O/${T}_trace_sh.log 2>&1; tail -2 $O/${T}_trace_sh.log | cut -c1-200

@@ -30,8 +30,14 @@ def rng_tensor(rng, shape, dtype):
 
 
 def load_golden(name):
-    z = np.load(os.path.join(GOLDEN, name + ".npz"))
-    return {k: z[k] for k in z.files}
+    """the arrays of tests/golden/<name>.npz, merged with those of <name>.part2.npz where a fixture is kept in two files (every
+    committed file stays under 1 MiB)"""
+    out = {}
+    for f in (name + ".npz", name + ".part2.npz"):
+        if f == name + ".npz" or os.path.exists(os.path.join(GOLDEN, f)):
+            z = np.load(os.path.join(GOLDEN, f))
+            out.update({k: z[k] for k in z.files})
+    return out
 
 
 def pair(v):

@@ -74,8 +74,13 @@ def make_op_fixtures():
         out = ref.forward(x, w)
         gx = ref.backward_input(gout, w)
         gw = ref.backward_weight(gout, x)
-        np.savez_compressed(os.path.join(HERE, f"agg_{name}.npz"), out=out.numpy(), gx=gx.numpy(), gw=gw.numpy(),
-                            seed=np.int64(seed), geom=json.dumps(geom))
+        if out.numel() * out.element_size() * 3 > (1 << 20):  # (a committed file stays under 1 MiB: gw goes to a second part)
+            np.savez_compressed(os.path.join(HERE, f"agg_{name}.npz"), out=out.numpy(), gx=gx.numpy(), seed=np.int64(seed),
+                                geom=json.dumps(geom))
+            np.savez_compressed(os.path.join(HERE, f"agg_{name}.part2.npz"), gw=gw.numpy())
+        else:
+            np.savez_compressed(os.path.join(HERE, f"agg_{name}.npz"), out=out.numpy(), gx=gx.numpy(), gw=gw.numpy(),
+                                seed=np.int64(seed), geom=json.dumps(geom))
         print(f"agg_{name}: out {tuple(out.shape)}")
     # mix: reference self-test geometry (heads=1) and a heads=2 case that exposes the head-0-only input grad
     for name, geom, seed in (("mix_selftest", build_ref.PREBUILT_MIX[0], 21), ("mix_heads2", build_ref.PREBUILT_MIX[1], 22)):
@@ -316,8 +321,26 @@ def make_model_fixtures(models):
         print(f"model_{name}: logits {tuple(logits.shape)} |max| {logits.abs().max():.4f}")
 
 
+def make_reference_line_counts():
+    """reference_line_counts.json: {path inside the reference checkout: number of lines} of its .py / .yaml / .sh files -- what
+    tests/test_citations.py checks every `path:line` citation against"""
+    counts = {}
+    for d, _, fs in os.walk(build_ref.REFERENCE):
+        if ".git" in d:
+            continue
+        for f in fs:
+            if f.endswith((".py", ".yaml", ".sh")):
+                p = os.path.join(d, f)
+                with open(p, errors="replace") as fh:
+                    counts[os.path.relpath(p, build_ref.REFERENCE)] = sum(1 for _ in fh)
+    with open(os.path.join(HERE, "reference_line_counts.json"), "w") as fh:
+        json.dump(dict(sorted(counts.items())), fh, indent=0)
+    print(f"reference_line_counts: {len(counts)} files")
+
+
 if __name__ == "__main__":
     assert build_ref.reference_available(), "the reference checkout is required to regenerate fixtures"
+    make_reference_line_counts()
     if "--real-layers-only" not in sys.argv:
         make_op_fixtures()
     models, ref_cotnet, ref_hybrid = import_reference_models()
