@@ -5,6 +5,7 @@ Public surface mirrors the reference (JDAI-CV/CoTNet):
     cupy_layers.aggregation_zeropad_mix  -> cotnet_amd.aggregation_zeropad_mix
     models.cotnet                        -> cotnet_amd.cotnet               (CotLayer, CoXtLayer, Bottleneck, cotnet50 ...)
     models.cotnet_hybrid                 -> cotnet_amd.cotnet_hybrid        (CoTLayer, CoTBottleneck, se_cotnetd_* ...)
+    models.lr_net                        -> cotnet_amd.lr_net               (SelfAttLayer, Bottleneck, lrnet50, lrnet50_ks3)
     models.factory / models.registry     -> cotnet_amd.registry             (create_model, register_model)
 Device code lives in cotnet_amd/csrc (HIP, gfx950) behind the C ABI of include/cotnet_amd.h.
 """
@@ -17,6 +18,8 @@ from .aggregation_zeropad_mix import AggregationZeropadMix, LocalConvolutionMix 
 from .cotnet import Bottleneck, CotLayer, CoXtLayer, cotnet50, cotnet101, cotnext50_2x48d, cotnext101_2x48d  # noqa: F401
 from .cotnet_hybrid import (CoTBottleneck, CoTHybridNet, CoTLayer, se_cotnetd_50, se_cotnetd_101,  # noqa: F401
                             se_cotnetd_152, se_cotnetd_152_L, se_cotnetd_200, se_cotnetd_270)
+from . import local_relation  # noqa: F401  (the sub-module: import the functions from it, as with aggregation_zeropad)
+from .lr_net import Bottleneck_Ks3, SelfAttLayer, lrnet50, lrnet50_ks3  # noqa: F401
 from .registry import create_model, list_models, load_checkpoint, register_model  # noqa: F401
 from .resnet import ResNet  # noqa: F401
 

@@ -55,6 +55,9 @@ SYMBOLS = {
     "cot_agg_backward": (_I, [_P, _P, _P, _P, _P, _G, _I, _I, _P]),
     "cot_agg_softmax_forward": (_I, [_P, _P, _P, _P, _G, _I, _P]),
     "cot_agg_softmax_backward": (_I, [_P, _P, _P, _P, _P, _G, _I, _P]),
+    "cot_local_relation_workspace_bytes": (ctypes.c_int64, [_G, _I]),
+    "cot_local_relation_forward": (_I, [_P] * 6 + [_G, _I, _P]),
+    "cot_local_relation_backward": (_I, [_P] * 11 + [_G, _I, _P]),
     "cot_aggmix_forward": (_I, [_P, _P, _P, _P, _G, _I, _I, _I, _P]),
     "cot_aggmix_backward_input": (_I, [_P, _P, _P, _P, _G, _I, _I, _I, _I, _P]),
     "cot_aggmix_backward_weight": (_I, [_P, _P, _P, _P, _G, _I, _I, _I, _P]),

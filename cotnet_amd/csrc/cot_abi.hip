@@ -145,6 +145,14 @@ template <typename T>
 int agg_softmax_forward_nchw(const T*, const T*, T*, T*, const cot_agg_geom&, hipStream_t);
 template <typename T>
 int agg_softmax_backward_nchw(const T*, const T*, const T*, T*, T*, const cot_agg_geom&, hipStream_t);
+bool lr_covers(const cot_agg_geom&);
+int64_t lr_workspace_bytes(const cot_agg_geom&, size_t);
+const char* last_kernel_lr();
+template <typename T>
+int lr_forward(const T*, const T*, const T*, const float*, T*, T*, const cot_agg_geom&, hipStream_t);
+template <typename T>
+int lr_backward(const T*, const T*, const T*, const T*, const float*, const T*, T*, T*, T*, float*, void*, const cot_agg_geom&,
+                hipStream_t);
 template <typename T> int radix_gap(const void*, const void*, void*, int64_t, int, hipStream_t);
 template <typename T> int radix_mix(const void*, const void*, const void*, void*, int64_t, int, hipStream_t);
 template <typename T>
@@ -1072,6 +1080,57 @@ int cot_agg_softmax_backward(const void* gout, const void* x, const void* probs,
     }
     if (rc == COT_ERR_UNSUPPORTED) set_error(rc, "fused window-softmax aggregation backward: geometry/dtype not covered");
     else g_kernel = last_kernel_nchw();
+    return rc;
+}
+
+// ---- LR-Net local relation (local_relation.hip)
+static int lr_check(const cot_agg_geom* g, int dtype) {
+    int Ho, Wo, rc = validate(g, &Ho, &Wo);
+    if (rc) return rc;
+    if (dtype != COT_F32 && dtype != COT_BF16) return set_error(COT_ERR_UNSUPPORTED, "local relation: fp32 / bf16 storage only");
+    if (!lr_covers(*g))
+        return set_error(COT_ERR_UNSUPPORTED, "local relation: geometry not covered (3x3 / stride 1 / pad 1 / dilation 1, heads 1, "
+                                              "C %% 8 == 0, wC == C / 8, a tile that fits LDS)");
+    return COT_OK;
+}
+
+int64_t cot_local_relation_workspace_bytes(const cot_agg_geom* g, int dtype) {
+    const int rc = lr_check(g, dtype);
+    if (rc) return rc;
+    return lr_workspace_bytes(*g, dtype == COT_BF16 ? 2 : 4);
+}
+
+int cot_local_relation_forward(const void* q, const void* k, const void* v, const float* pos, void* out, void* probs,
+                               const cot_agg_geom* g, int dtype, void* stream) {
+    int rc = lr_check(g, dtype);
+    if (rc) return rc;
+    if (!q || !k || !v || !pos || !out) return set_error(COT_ERR_INVALID_ARG, "NULL device pointer");
+    if ((rc = check_align16({q, k, v, pos, out, probs}))) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == COT_F32)
+        rc = lr_forward<float>((const float*)q, (const float*)k, (const float*)v, pos, (float*)out, (float*)probs, *g, s);
+    else
+        rc = lr_forward<bf16_t>((const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, pos, (bf16_t*)out, (bf16_t*)probs, *g, s);
+    if (!rc) g_kernel = last_kernel_lr();
+    return rc;
+}
+
+int cot_local_relation_backward(const void* gout, const void* q, const void* k, const void* v, const float* pos,
+                                const void* probs, void* gq, void* gk, void* gv, float* gpos, void* workspace,
+                                const cot_agg_geom* g, int dtype, void* stream) {
+    int rc = lr_check(g, dtype);
+    if (rc) return rc;
+    if (!gout || !q || !k || !v || !pos || !probs || !gq || !gk || !gv || !gpos || !workspace)
+        return set_error(COT_ERR_INVALID_ARG, "NULL device pointer");
+    if ((rc = check_align16({gout, q, k, v, pos, probs, gq, gk, gv, gpos, workspace}))) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == COT_F32)
+        rc = lr_backward<float>((const float*)gout, (const float*)q, (const float*)k, (const float*)v, pos, (const float*)probs,
+                                (float*)gq, (float*)gk, (float*)gv, gpos, workspace, *g, s);
+    else
+        rc = lr_backward<bf16_t>((const bf16_t*)gout, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, pos,
+                                 (const bf16_t*)probs, (bf16_t*)gq, (bf16_t*)gk, (bf16_t*)gv, gpos, workspace, *g, s);
+    if (!rc) g_kernel = last_kernel_lr();
     return rc;
 }
 

@@ -100,6 +100,28 @@ int cot_agg_softmax_forward(const void* x, const void* logits, void* out, void* 
 int cot_agg_softmax_backward(const void* gout, const void* x, const void* probs, void* gx, void* glogits,
                              const cot_agg_geom* g, int dtype, void* stream);
 
+/* ---- LR-Net's local relation (SelfAttLayer, models/lr_net.py:82-96), the producer of the window softmax fused in front of
+ * the aggregation.  dim = C, G = C/8 heads of 8 CONSECUTIVE q/k channels (:47, :90-92), 3x3 window t = 3i + j, pad 1:
+ *   pos[c][t]      = pos_h[c][i] + pos_w[c][j]                                   (:87-88; fp32 [C][9], whatever the storage)
+ *   logit[n,g,t,p] = sum_{j<8} q[n,8g+j,p] * (uk[n,8g+j,t,p] + pos[8g+j][t])     (:85-93; uk = k at p + off_t, 0 outside, :75)
+ *   probs          = softmax over t                                              (:94)
+ *   out[n,c,p]     = sum_t probs[n,0,c mod G,t,p] * v[n,c,p + off_t], zero pad   (:95-96: wC = G)
+ * A padded tap keeps the logit sum_j q*pos and its probability mass; only v is zero there.
+ * q, k, v, out, gq, gk, gv: [N,C,H,W]; probs: [N,1,G,9,H,W] (may be NULL in the forward: inference), all in the storage
+ * dtype (COT_F32 / COT_BF16, fp32 accumulation); pos / gpos fp32 [C][9].  The geometry is a cot_agg_geom with kh = kw = 3,
+ * stride 1, pad 1, dilation 1, heads 1, wC = C/8, C % 8 == 0; anything else (or a tile that does not fit LDS) returns
+ * COT_ERR_UNSUPPORTED and the caller composes unfold + softmax + aggregation.
+ * Backward: gv and glogits as cot_agg_softmax_backward, then gq = sum_t gL (uk + pos), gk[p'] = sum_t gL[p' - off_t] q[p' - off_t]
+ * and gpos[c][t] = sum_{n,p} gL[n,c/8,t,p] q[n,c,p] (per-workgroup partials reduced in a fixed order: bit-identical run to run).
+ * No allocation and no host synchronisation (graph-capture safe): `workspace` holds
+ * cot_local_relation_workspace_bytes(g, dtype) bytes (a negative cot_status when the geometry is not covered). */
+int64_t cot_local_relation_workspace_bytes(const cot_agg_geom* g, int dtype);
+int cot_local_relation_forward(const void* q, const void* k, const void* v, const float* pos, void* out, void* probs,
+                               const cot_agg_geom* g, int dtype, void* stream);
+int cot_local_relation_backward(const void* gout, const void* q, const void* k, const void* v, const float* pos,
+                                const void* probs, void* gq, void* gk, void* gv, float* gpos, void* workspace,
+                                const cot_agg_geom* g, int dtype, void* stream);
+
 /* ---- aggregation_zeropad_mix: 3x3 (w1) and 5x5 (w2) aggregation of the same x; NCHW only.
  * out[N, 2*heads*C, Ho, Wo] ordered [kernel_idx][head][c] (aggregation_zeropad_mix.py:20-74).
  * geometry: kh/kw/ph/pw of `g` describe the 3x3 set (kh=kw=3, pad1); p2h/p2w pad the 5x5 set.
