@@ -5,7 +5,9 @@ or a call fails, a RuntimeError is raised (the product path must fail loudly, ne
 on the CPU).  The reference's equivalent is cupy_layers/utils.py:14-18 (`load_kernel`).
 """
 import ctypes
+import functools
 import os
+import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # COT_LIB_PATH: developer A/B of two builds of the library on one box (scripts/gpu_session.sh); the product loads the in-tree one
@@ -161,6 +163,11 @@ SYMBOLS = {
     "cot_profile_begin": (_I, []),
     "cot_profile_end": (_I, [ctypes.POINTER(ProfileRec), _I]),
 }
+# the `int` returns that are a value, not a cot_status (a size, a count, a mode, a yes/no): api() passes them through unchecked
+NOT_STATUS = frozenset((
+    "cot_abi_version", "cot_agg_out_size", "cot_xchg_mode", "cot_launch_log", "cot_bn_act_workspace", "cot_profile_end",
+    "cot_gn9_fused_covers", "cot_conv1x1_backward_data_relu_res_covers", "cot_conv1x1_lds_covers", "cot_bn_act_lay_covers",
+    "cot_conv1x1_stats_covers"))
 
 
 def build(verbose=False):
@@ -171,6 +178,11 @@ def build(verbose=False):
     return LIB_PATH
 
 
+# How a wrapper calls the library.  `L = api()` is the library with every status checked: `L.cot_x(ptr(a), ..., stream())` raises
+# CotError (the entry point's name, the status, cot_last_error()) unless it returns COT_OK; sizes, counts and the *_covers predicates
+# (NOT_STATUS, the int64 / string returns) come back as they are.  lib() is the raw handle for callers that branch on a status.
+# Every wrapper's eligible() and stream() read the one DEVICE_ONLY flag below, here, at call time.
+#
 # Module fallbacks.  Every wrapper (conv1x1, conv3x3g, fused_bn, group_norm9, pool3x3, stem7x7, head_fused) serves a tensor that is off its
 # kernels' grid with the torch module it wraps.  While the library's kernels were asked for (the wrapper's switch is on) and the tensor is
 # on a GPU, each such call is counted here per site (bench.py prints the counters as `module_fallbacks`), and COT_STRICT_DISPATCH=1
@@ -189,6 +201,16 @@ def fallback(site, x=None, detail=""):
                            "(the torch module would have run)")
 
 
+def bind(cdll, lenient=False):
+    """restype / argtypes of every SYMBOLS entry on a loaded library (lenient: entry points it lacks are simply not bound)"""
+    for name, (res, args) in SYMBOLS.items():
+        if lenient and not hasattr(cdll, name):
+            continue
+        fn = getattr(cdll, name)  # AttributeError here = header/library mismatch
+        fn.restype, fn.argtypes = res, args
+    return cdll
+
+
 def lib():
     global _lib
     if _lib is None:
@@ -196,12 +218,8 @@ def lib():
             raise RuntimeError(
                 f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950). cotnet_amd has no CPU or eager fallback.")
-        L = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in SYMBOLS.items():
-            if os.environ.get("COT_LIB_PATH") and not hasattr(L, name):
-                continue  # (developer A/B against an OLDER build of the library: entry points it lacks are simply not bound)
-            fn = getattr(L, name)  # AttributeError here = header/library mismatch
-            fn.restype, fn.argtypes = res, args
+        # (lenient under COT_LIB_PATH: a developer A/B against an OLDER build of the library)
+        L = bind(ctypes.CDLL(LIB_PATH), lenient=bool(os.environ.get("COT_LIB_PATH")))
         if L.cot_abi_version() != 1:
             raise RuntimeError(f"libcotnet_hip.so ABI version {L.cot_abi_version()} != 1")
         raw_set_tuning = L.cot_set_tuning
@@ -220,11 +238,87 @@ def lib():
     return _lib
 
 
+class CotError(RuntimeError):  # an entry point returned a cot_status other than COT_OK: .entry is its name, .status the code
+    def __init__(self, status, entry, message):
+        super().__init__(message)
+        self.status, self.entry = status, entry
+
+
 def check(status, what):
     if status != 0:
         L = lib()
-        raise RuntimeError(f"{what} failed: {L.cot_status_string(status).decode()} -- "
-                           f"{L.cot_last_error().decode()}")
+        raise CotError(status, what, f"{what} failed: {L.cot_status_string(status).decode()} -- "
+                                     f"{L.cot_last_error().decode()}")
+
+
+class _Checked:
+    """view of one library handle: a status entry point's wrapper is built on first use and found in the instance's dict from then
+    on; it looks the entry point up on the handle per call, as `L.cot_x(...)` always did (tests rebind entry points there)"""
+
+    def __init__(self, raw):
+        self._raw = raw
+
+    def __getattr__(self, name):
+        raw = self._raw
+        if name in NOT_STATUS or SYMBOLS.get(name, (None,))[0] is not _I:
+            return getattr(raw, name)
+        getattr(raw, name)  # (AttributeError here, not at the first launch)
+
+        def fn(*args):
+            rc = getattr(raw, name)(*args)
+            if rc:
+                check(rc, name)
+        setattr(self, name, fn)
+        return fn
+
+
+_api = None
+
+
+def api():
+    """lib() with every status checked ("How a wrapper calls the library" above); follows whatever lib() returns now"""
+    global _api
+    L = lib()
+    if _api is None or _api._raw is not L:
+        _api = _Checked(L)
+    return _api
+
+
+def ptr(t):
+    # a plain int is accepted for a c_void_p parameter and skips building a ctypes object per argument (~1000 per step)
+    return t.data_ptr() if t is not None else None
+
+
+DEVICE_ONLY = True  # False: CPU tensors reach the kernels too (tests, with a host-compiled build of them behind lib())
+_TLS = threading.local()  # .st: the compute stream's handle for the node invocation running on this thread
+
+
+def _current_stream():
+    import torch
+    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def stream():
+    if not DEVICE_ONLY:
+        return None
+    st = getattr(_TLS, "st", None)
+    return st if st is not None else _current_stream()
+
+
+def one_stream_query(fn):
+    """torch.cuda.current_stream() costs ~9 us and a node makes ~100 launches: ask once per forward / backward of a node (the
+    current stream cannot change inside one; forward and backward run on different threads, hence thread-local).  Measured:
+    1.3 ms of a step's ~12 ms of host time (gpurun_out/r3_cpu_profile.log)"""
+    @functools.wraps(fn)
+    def wrapped(*a, **k):
+        if not DEVICE_ONLY or getattr(_TLS, "st", None) is not None:
+            return fn(*a, **k)
+        _TLS.st = _current_stream()
+        try:
+            return fn(*a, **k)
+        finally:
+            _TLS.st = None
+    return wrapped
 
 
 def last_kernel():

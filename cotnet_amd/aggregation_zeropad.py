@@ -26,6 +26,7 @@ from torch.autograd import Function
 from torch.nn.modules.utils import _pair
 
 from . import _lib
+from ._lib import ptr as _ptr, stream as _stream
 
 
 def _out_hw(H, W, k, s, p, d):
@@ -61,23 +62,15 @@ def _pick_layout(input, weight):
     return _lib.COT_NCHW, input.contiguous(), weight.contiguous()
 
 
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
 def _aligned(t):
     return t if t.data_ptr() % 16 == 0 else t.clone(memory_format=torch.preserve_format)
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 # ---- optional in-situ kernel timing (bench.py) ---------------------------------------------------------------
 # The library attaches start/stop events to each kernel dispatch (cot_profile_begin/_end in include/cotnet_amd.h),
 # so durations are device execution times -- the same quantity rocprofv3 --kernel-trace reports.
 def profile_begin():
-    _lib.check(_lib.lib().cot_profile_begin(), "cot_profile_begin")
+    _lib.api().cot_profile_begin()
 
 
 def profile_end(max_records=65536):
@@ -150,10 +143,8 @@ class AggregationZeropad(Function):
                             kernel_size[0], kernel_size[1], stride[0], stride[1], padding[0], padding[1],
                             dilation[0], dilation[1])
         # one process per GPU: tensors live on the current device, launches go to its current stream (ref :130,:143)
-        rc = _lib.lib().cot_agg_forward(_ptr(input), _ptr(weight), _ptr(output), ctypes.byref(geom),
-                                        _lib.dtype_code(input.dtype), layout, _stream())
-        if rc:
-            _lib.check(rc, "cot_agg_forward")
+        _lib.api().cot_agg_forward(_ptr(input), _ptr(weight), _ptr(output), ctypes.byref(geom),
+                                   _lib.dtype_code(input.dtype), layout, _stream())
         ctx.geom, ctx.layout = geom, layout
         ctx.save_for_backward(input, weight)
         return output
@@ -175,11 +166,9 @@ class AggregationZeropad(Function):
             grad_weight = (_empty_nhwc_weight(weight.shape, weight) if layout == _lib.COT_NHWC
                            else torch.empty_like(weight))
         if grad_input is not None or grad_weight is not None:
-            rc = _lib.lib().cot_agg_backward(_ptr(grad_output), _ptr(input), _ptr(weight), _ptr(grad_input),
-                                             _ptr(grad_weight), ctypes.byref(ctx.geom),
-                                             _lib.dtype_code(input.dtype), layout, _stream())
-            if rc:
-                _lib.check(rc, "cot_agg_backward")
+            _lib.api().cot_agg_backward(_ptr(grad_output), _ptr(input), _ptr(weight), _ptr(grad_input),
+                                        _ptr(grad_weight), ctypes.byref(ctx.geom),
+                                        _lib.dtype_code(input.dtype), layout, _stream())
         return grad_input, grad_weight, None, None, None, None
 
 
@@ -234,10 +223,8 @@ class AggregationZeropadSoftmax(Function):
         N, heads, C = geom.N, geom.heads, geom.C
         out = torch.empty((N, heads * C, geom.H, geom.W), dtype=input.dtype, device=input.device)
         probs = torch.empty_like(logits)
-        rc = _lib.lib().cot_agg_softmax_forward(_ptr(input), _ptr(logits), _ptr(out), _ptr(probs), ctypes.byref(geom),
-                                                _lib.dtype_code(input.dtype), _stream())
-        if rc:
-            _lib.check(rc, "cot_agg_softmax_forward")
+        _lib.api().cot_agg_softmax_forward(_ptr(input), _ptr(logits), _ptr(out), _ptr(probs), ctypes.byref(geom),
+                                           _lib.dtype_code(input.dtype), _stream())
         ctx.geom = geom
         ctx.save_for_backward(input, probs)
         return out
@@ -247,10 +234,8 @@ class AggregationZeropadSoftmax(Function):
         input, probs = ctx.saved_tensors
         grad_output = _aligned(grad_output.contiguous())
         gx, gl = torch.empty_like(input), torch.empty_like(probs)
-        rc = _lib.lib().cot_agg_softmax_backward(_ptr(grad_output), _ptr(input), _ptr(probs), _ptr(gx), _ptr(gl),
-                                                 ctypes.byref(ctx.geom), _lib.dtype_code(input.dtype), _stream())
-        if rc:
-            _lib.check(rc, "cot_agg_softmax_backward")
+        _lib.api().cot_agg_softmax_backward(_ptr(grad_output), _ptr(input), _ptr(probs), _ptr(gx), _ptr(gl),
+                                            ctypes.byref(ctx.geom), _lib.dtype_code(input.dtype), _stream())
         return gx, gl, None
 
 
@@ -269,7 +254,7 @@ def aggregation_zeropad_softmax(input, logits, kernel_size=3, stride=1, padding=
         geom = _lib.AggGeom(N, C, H, W, 1, logits.shape[2], 3, 3, 1, 1, 1, 1, 1, 1)
         try:
             return AggregationZeropadSoftmax.apply(input, logits, geom)
-        except RuntimeError as e:
-            if "not covered" not in str(e):  # COT_ERR_UNSUPPORTED (tile does not fit LDS, odd alignment): compose
+        except _lib.CotError as e:
+            if e.status != _lib.COT_ERR_UNSUPPORTED:  # (unsupported = tile does not fit LDS, odd alignment: compose)
                 raise
     return aggregation_zeropad(input, torch.softmax(logits, dim=3), kernel_size, stride, padding, dilation)

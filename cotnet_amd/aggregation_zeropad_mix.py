@@ -20,7 +20,8 @@ from torch.autograd import Function
 from torch.nn.modules.utils import _pair
 
 from . import _lib
-from .aggregation_zeropad import _aligned, _out_hw, _ptr, _stream
+from ._lib import ptr as _ptr, stream as _stream
+from .aggregation_zeropad import _aligned, _out_hw
 
 
 class AggregationZeropadMix(Function):
@@ -43,10 +44,9 @@ class AggregationZeropadMix(Function):
         geom = _lib.AggGeom(N, C, H, W, heads, wC, 3, 3, stride[0], stride[1], padding1[0], padding1[1],
                             dilation[0], dilation[1])
         with torch.cuda.device_of(input):
-            rc = _lib.lib().cot_aggmix_forward(_ptr(input), _ptr(weight1), _ptr(weight2), _ptr(output),
-                                               ctypes.byref(geom), padding2[0], padding2[1],
-                                               _lib.dtype_code(input.dtype), _stream())
-        _lib.check(rc, "cot_aggmix_forward")
+            _lib.api().cot_aggmix_forward(_ptr(input), _ptr(weight1), _ptr(weight2), _ptr(output),
+                                          ctypes.byref(geom), padding2[0], padding2[1],
+                                          _lib.dtype_code(input.dtype), _stream())
         ctx.geom, ctx.padding2 = geom, padding2
         ctx.save_for_backward(input, weight1, weight2)
         return output
@@ -61,16 +61,14 @@ class AggregationZeropadMix(Function):
         with torch.cuda.device_of(input):
             if ctx.needs_input_grad[0]:
                 grad_input = torch.empty_like(input)
-                rc = _lib.lib().cot_aggmix_backward_input(
+                _lib.api().cot_aggmix_backward_input(
                     _ptr(grad_output), _ptr(weight1), _ptr(weight2), _ptr(grad_input), ctypes.byref(ctx.geom),
                     p2[0], p2[1], 1 if AggregationZeropadMix.all_heads else 0, dt, _stream())
-                _lib.check(rc, "cot_aggmix_backward_input")
             if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
                 grad_weight1, grad_weight2 = torch.empty_like(weight1), torch.empty_like(weight2)
-                rc = _lib.lib().cot_aggmix_backward_weight(
+                _lib.api().cot_aggmix_backward_weight(
                     _ptr(grad_output), _ptr(input), _ptr(grad_weight1), _ptr(grad_weight2), ctypes.byref(ctx.geom),
                     p2[0], p2[1], dt, _stream())
-                _lib.check(rc, "cot_aggmix_backward_weight")
         return grad_input, grad_weight1, grad_weight2, None, None, None, None, None, None
 
 

@@ -19,16 +19,15 @@ models/cotnet.py:81).  Implementation is chosen by COT_CONV1X1:
 `hip` is verified against torch through the host emulation of the kernels (tests/test_kernels_emulated.py) and on the MI355X
 by tests/test_conv1x1_gpu.py / tests/test_conv_general_gpu.py.
 """
-import ctypes
 import os
 
 import torch
 from torch.autograd import Function
 
 from . import _lib
+from ._lib import ptr as _p, stream as _stream
 
 MODE = os.environ.get("COT_CONV1X1", "hip")  # default: the library's kernels; COT_CONV1X1=module opts out
-_DEVICE_ONLY = True  # tests drive the autograd wiring on CPU tensors through the host-emulated kernels
 
 
 class _Conv1x1(Function):
@@ -60,14 +59,6 @@ class _Conv1x1(Function):
         return gx, gw, gb
 
 
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream) if _DEVICE_ONLY else None
-
-
 _WS = _lib.register_cache({})  # (N, Ci, Co, HW, has_bias) -> backward workspace bytes (pure function of the shape)
 
 
@@ -87,10 +78,8 @@ class _Conv1x1Hip(Function):
         N, c1, H, W = x1.shape
         Co, Ci = weight.shape[0], weight.shape[1]
         y = torch.empty((N, Co, H, W), dtype=x1.dtype, device=x1.device)
-        rc = _lib.lib().cot_conv1x1_forward(_p(x1), _p(x2), c1, _p(weight), _p(bias), _p(y), N, Ci, Co, H * W,
-                                            _lib.dtype_code(x1.dtype), _stream())
-        if rc:
-            _lib.check(rc, "cot_conv1x1_forward")
+        _lib.api().cot_conv1x1_forward(_p(x1), _p(x2), c1, _p(weight), _p(bias), _p(y), N, Ci, Co, H * W,
+                                       _lib.dtype_code(x1.dtype), _stream())
         ctx.save_for_backward(x1, x2, weight)
         ctx.has_bias = bias is not None
         return y
@@ -102,7 +91,7 @@ class _Conv1x1Hip(Function):
         Co, Ci = weight.shape[0], weight.shape[1]
         HW = H * W
         gy = gy.contiguous()
-        L = _lib.lib()
+        L = _lib.api()
         has_bias = 1 if ctx.has_bias else 0
         dt = _lib.dtype_code(x1.dtype)
         nbytes = (int(L.cot_convg_workspace(N, Ci, Co, 1, HW, 1, 1)) if x1.dtype == torch.float32
@@ -112,17 +101,13 @@ class _Conv1x1Hip(Function):
         if ctx.needs_input_grad[0] or (x2 is not None and ctx.needs_input_grad[1]):
             gx1 = torch.empty_like(x1)
             gx2 = torch.empty_like(x2) if x2 is not None else None
-            rc = L.cot_conv1x1_backward_data(_p(gy), _p(weight), _p(gx1), _p(gx2), c1, 0, _p(ws), N, Ci, Co, HW,
-                                             dt, _stream())
-            if rc:
-                _lib.check(rc, "cot_conv1x1_backward_data")
+            L.cot_conv1x1_backward_data(_p(gy), _p(weight), _p(gx1), _p(gx2), c1, 0, _p(ws), N, Ci, Co, HW,
+                                        dt, _stream())
         if ctx.needs_input_grad[2] or (ctx.has_bias and ctx.needs_input_grad[3]):
             gw = torch.empty_like(weight)
             gb = torch.empty(Co, dtype=weight.dtype, device=gy.device) if ctx.has_bias else None
-            rc = L.cot_conv1x1_backward_weight(_p(gy), _p(x1), _p(x2), c1, _p(gw), _p(gb), _p(ws), N, Ci, Co, HW,
-                                               dt, _stream())
-            if rc:
-                _lib.check(rc, "cot_conv1x1_backward_weight")
+            L.cot_conv1x1_backward_weight(_p(gy), _p(x1), _p(x2), c1, _p(gw), _p(gb), _p(ws), N, Ci, Co, HW,
+                                          dt, _stream())
         return gx1, gx2, gw, gb
 
 
@@ -135,10 +120,8 @@ class _Conv1x1gHip(Function):
         N, Ci, H, W = x.shape
         Co = weight.shape[0]
         y = torch.empty((N, Co, H, W), dtype=x.dtype, device=x.device)
-        rc = _lib.lib().cot_conv1x1g_forward(_p(x), _p(weight), _p(bias), _p(y), N, Ci, Co, groups, H * W,
-                                             _lib.dtype_code(x.dtype), _stream())
-        if rc:
-            _lib.check(rc, "cot_conv1x1g_forward")
+        _lib.api().cot_conv1x1g_forward(_p(x), _p(weight), _p(bias), _p(y), N, Ci, Co, groups, H * W,
+                                        _lib.dtype_code(x.dtype), _stream())
         ctx.save_for_backward(x, weight)
         ctx.has_bias = bias is not None
         ctx.groups = groups
@@ -150,21 +133,17 @@ class _Conv1x1gHip(Function):
         N, Ci, H, W = x.shape
         Co, G, HW = weight.shape[0], ctx.groups, H * W
         gy = gy.contiguous()
-        L = _lib.lib()
+        L = _lib.api()
         dt = _lib.dtype_code(x.dtype)
         gx = gw = gb = None
         if ctx.needs_input_grad[0]:
             gx = torch.empty_like(x)
-            rc = L.cot_conv1x1g_backward_data(_p(gy), _p(weight), _p(gx), 0, N, Ci, Co, G, HW, dt, _stream())
-            if rc:
-                _lib.check(rc, "cot_conv1x1g_backward_data")
+            L.cot_conv1x1g_backward_data(_p(gy), _p(weight), _p(gx), 0, N, Ci, Co, G, HW, dt, _stream())
         if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
             ws = torch.empty(int(L.cot_convg_workspace(N, Ci, Co, G, HW, 1, 1)), dtype=torch.uint8, device=gy.device)
             gw = torch.empty_like(weight)
             gb = torch.empty(Co, dtype=weight.dtype, device=gy.device) if ctx.has_bias else None
-            rc = L.cot_conv1x1g_backward_weight(_p(gy), _p(x), _p(gw), _p(gb), _p(ws), N, Ci, Co, G, HW, dt, _stream())
-            if rc:
-                _lib.check(rc, "cot_conv1x1g_backward_weight")
+            L.cot_conv1x1g_backward_weight(_p(gy), _p(x), _p(gw), _p(gb), _p(ws), N, Ci, Co, G, HW, dt, _stream())
         return gx, gw, gb, None
 
 
@@ -186,14 +165,14 @@ def eligible(conv, x):
 
 def eligible_general(conv, x):
     """the general kernels: any groups and channel counts, bf16 or fp32 (one input tensor)"""
-    return (MODE == "hip" and _is_1x1(conv) and (x.is_cuda or not _DEVICE_ONLY) and x.dim() == 4
+    return (MODE == "hip" and _is_1x1(conv) and (x.is_cuda or not _lib.DEVICE_ONLY) and x.dim() == 4
             and x.dtype in (torch.bfloat16, torch.float32) and conv.weight.dtype == x.dtype and x.is_contiguous()
             and conv.weight.is_contiguous() and x.shape[1] == conv.in_channels
             and (conv.bias is None or conv.bias.dtype == x.dtype))
 
 
 def eligible_hip(conv, x, x2=None):
-    if not (MODE == "hip" and _plain_1x1(conv) and (x.is_cuda or not _DEVICE_ONLY) and x.dim() == 4 and x.dtype == torch.bfloat16
+    if not (MODE == "hip" and _plain_1x1(conv) and (x.is_cuda or not _lib.DEVICE_ONLY) and x.dim() == 4 and x.dtype == torch.bfloat16
             and conv.weight.dtype == torch.bfloat16 and x.is_contiguous() and conv.weight.is_contiguous()):
         return False
     if x2 is not None and not (x2.dtype == x.dtype and x2.is_contiguous() and x2.shape[0] == x.shape[0]
@@ -232,7 +211,7 @@ def run_downsample(ds, x):
             if isinstance(m, torch.nn.Conv2d):
                 if (MODE == "hip" and m.kernel_size == (1, 1) and m.stride == (2, 2) and m.padding == (0, 0)
                         and m.groups == 1 and x.dim() == 4 and x.dtype in (torch.bfloat16, torch.float32)
-                        and m.weight.dtype == x.dtype and (x.is_cuda or not _DEVICE_ONLY)
+                        and m.weight.dtype == x.dtype and (x.is_cuda or not _lib.DEVICE_ONLY)
                         and m.in_channels % 8 == 0 and m.out_channels % 8 == 0):  # (fp32: the general kernels, conv_gen.hip)
                     x = _Conv1x1Hip.apply(x[:, :, ::2, ::2].contiguous(), None, m.weight, m.bias)
                 else:

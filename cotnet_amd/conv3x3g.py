@@ -8,38 +8,27 @@ bf16 with channels per group a multiple of 8 runs the tuned kernels (csrc/conv_l
 channel counts (CoXtLayer: 12 / 24 per group) the general ones (csrc/conv_gen.hip).  Verified against torch through the
 host emulation of the kernels (tests/test_kernels_emulated.py) and on the device by tests/test_conv3x3g_gpu.py.
 """
-import ctypes
 import os
 
 import torch
 from torch.autograd import Function
 
 from . import _lib
+from ._lib import ptr as _p, stream as _stream
 
 MODE = os.environ.get("COT_CONV3X3", "hip")  # default: the library's kernels; COT_CONV3X3=module opts out
-_DEVICE_ONLY = True  # tests drive the autograd wiring on CPU tensors through the host-emulated kernels
 
 _MASKS = {}  # (H, W, device) -> uint8 tensor holding the per-pixel tap-validity table (read-only after creation)
 _WS = _lib.register_cache({})     # (N, Cin, Cout, G, H, W) -> workspace bytes
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream) if _DEVICE_ONLY else None
 
 
 def _masks(H, W, device):
     k = (H, W, str(device))
     m = _MASKS.get(k)
     if m is None:
-        L = _lib.lib()
+        L = _lib.api()
         m = torch.empty(int(L.cot_conv3x3g_masks_bytes(H, W)), dtype=torch.uint8, device=device)
-        rc = L.cot_conv3x3g_masks(_p(m), H, W, _stream())
-        if rc:
-            _lib.check(rc, "cot_conv3x3g_masks")
+        L.cot_conv3x3g_masks(_p(m), H, W, _stream())
         _MASKS[k] = m
     return m
 
@@ -50,7 +39,7 @@ def _ws_bytes(N, Cin, Cout, G, H, W, dtype=torch.bfloat16):
     key = (N, Cin, Cout, G, H, W, general)
     v = _WS.get(key)
     if v is None:
-        L = _lib.lib()
+        L = _lib.api()
         v = _WS[key] = max(int(L.cot_conv3x3g_workspace(N, Cin, Cout, G, H, W)),
                            int(L.cot_convg_workspace(N, Cin, Cout, G, H, W, 3)) if general else 0)
     return v
@@ -82,10 +71,8 @@ class _Conv3x3G(Function):
         masks = _masks(H, W, x.device)
         ws = torch.empty(_ws_bytes(N, Cin, Cout, groups, H, W, x.dtype), dtype=torch.uint8, device=x.device)
         y = torch.empty((N, Cout, H, W), dtype=x.dtype, device=x.device)
-        rc = _lib.lib().cot_conv3x3g_forward(_p(x), _p(weight), _p(y), _p(masks), _p(ws), N, Cin, Cout, groups, H, W,
-                                             _lib.dtype_code(x.dtype), _stream())
-        if rc:
-            _lib.check(rc, "cot_conv3x3g_forward")
+        _lib.api().cot_conv3x3g_forward(_p(x), _p(weight), _p(y), _p(masks), _p(ws), N, Cin, Cout, groups, H, W,
+                                        _lib.dtype_code(x.dtype), _stream())
         ctx.save_for_backward(x, weight)
         ctx.groups = groups
         return y
@@ -96,30 +83,26 @@ class _Conv3x3G(Function):
         N, Cin, H, W = x.shape
         Cout, G = weight.shape[0], ctx.groups
         gy = gy.contiguous()
-        L = _lib.lib()
+        L = _lib.api()
         masks = _masks(H, W, x.device)
         ws = torch.empty(_ws_bytes(N, Cin, Cout, G, H, W, x.dtype), dtype=torch.uint8, device=x.device)
         gx = gw = None
         if ctx.needs_input_grad[0]:
             gx = torch.empty_like(x)
-            rc = L.cot_conv3x3g_backward_data(_p(gy), _p(weight), _p(gx), 0, _p(masks), _p(ws), N, Cin, Cout, G, H, W,
-                                              _lib.dtype_code(x.dtype), _stream())
-            if rc:
-                _lib.check(rc, "cot_conv3x3g_backward_data")
+            L.cot_conv3x3g_backward_data(_p(gy), _p(weight), _p(gx), 0, _p(masks), _p(ws), N, Cin, Cout, G, H, W,
+                                         _lib.dtype_code(x.dtype), _stream())
         if ctx.needs_input_grad[1]:
             gw = torch.empty_like(weight)
             # (the margins x's own allocation has around it: with W + 1 or more the LDS-staged kernel runs, with 0 the per-wave one)
-            rc = L.cot_conv3x3g_backward_weight_guarded(_p(gy), _p(x), _p(gw), _p(masks), _p(ws), N, Cin, Cout, G, H, W,
-                                                        _lib.dtype_code(x.dtype), guard_elems(x), _stream())
-            if rc:
-                _lib.check(rc, "cot_conv3x3g_backward_weight")
+            L.cot_conv3x3g_backward_weight_guarded(_p(gy), _p(x), _p(gw), _p(masks), _p(ws), N, Cin, Cout, G, H, W,
+                                                   _lib.dtype_code(x.dtype), guard_elems(x), _stream())
         return gx, gw, None
 
 
 def eligible(conv, x):
     return (MODE == "hip" and isinstance(conv, torch.nn.Conv2d) and conv.kernel_size == (3, 3)
             and conv.stride == (1, 1) and conv.padding == (1, 1) and conv.dilation == (1, 1) and conv.bias is None
-            and conv.padding_mode == "zeros" and (x.is_cuda or not _DEVICE_ONLY) and x.dim() == 4
+            and conv.padding_mode == "zeros" and (x.is_cuda or not _lib.DEVICE_ONLY) and x.dim() == 4
             and x.dtype in (torch.bfloat16, torch.float32) and conv.weight.dtype == x.dtype and x.is_contiguous()
             and conv.weight.is_contiguous() and x.shape[1] == conv.in_channels)
 

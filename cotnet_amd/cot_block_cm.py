@@ -6,10 +6,11 @@ import ctypes
 import torch
 from torch.autograd import Function
 from . import _lib, grad_sink
+from ._lib import one_stream_query as _one_stream_query, ptr as _p, stream as _stream
 from . import cot_layer_fused as clf
 from .cot_layer_fused import (  # noqa: E402  (helpers; the switches are read as clf.NAME at call time: tests rebind them there)
-    BF16, NODE_COUNTS, _Side, _block_plan, _bn_bwd, _bn_fwd, _ck, _conv3x3_dgrad, _conv3x3_fwd, _drop_path_scale,
-    _guard_elems, _masks, _new_guarded, _one_stream_query, _p, _plan, _relu_mask, _stream)
+    BF16, NODE_COUNTS, _Side, _block_plan, _bn_bwd, _bn_fwd, _conv3x3_dgrad, _conv3x3_fwd, _drop_path_scale,
+    _guard_elems, _masks, _new_guarded, _plan, _relu_mask)
 
 # ---- channel-major Bottlenecks for the 14 x 14 / 7 x 7 stages (round 5).  The layers of these stages spend their time in
 # 1x1 convolutions and BatchNorms whose NCHW operands are N short rows per channel (392 / 98 bytes); stored channel-major --
@@ -115,7 +116,7 @@ def _cm_geometry_ok(L, N, Cin, C, H, W, grouped=False):
 
 def cm_block_eligible(blk, x):
     """training-mode identity-shortcut cotnet.Bottleneck of a deep stage on a bf16 tensor that is NCHW-contiguous or channel-major"""
-    if not (clf.ENABLED and clf.CM_LAYOUT and blk.training and (x.is_cuda or not clf._DEVICE_ONLY) and x.dim() == 4
+    if not (clf.ENABLED and clf.CM_LAYOUT and blk.training and (x.is_cuda or not _lib.DEVICE_ONLY) and x.dim() == 4
             and x.dtype == torch.bfloat16 and x.data_ptr() % 16 == 0 and (x.is_contiguous() or _is_cm(x))):
         return False
     if not _cm_static_ok(blk):
@@ -140,15 +141,15 @@ def cm_block_forward(blk, x):
 
 
 def _bn_fwd_lay(L, x, res, y, y2, bn, stats, N, C, HW, act, lay, ps=None):
-    _ck(L.cot_bn_act_forward_lay(_p(x), _p(res), _p(y), _p(y2), _p(bn.weight), _p(bn.bias), _p(stats), _p(stats[C:]),
-                                 _p(bn.running_mean), _p(bn.running_var), _p(bn.num_batches_tracked), _p(ps), N, C, HW,
-                                 float(bn.eps), float(bn.momentum), act, lay, BF16, _stream()), "cot_bn_act_forward_lay")
+    L.cot_bn_act_forward_lay(_p(x), _p(res), _p(y), _p(y2), _p(bn.weight), _p(bn.bias), _p(stats), _p(stats[C:]),
+                             _p(bn.running_mean), _p(bn.running_var), _p(bn.num_batches_tracked), _p(ps), N, C, HW,
+                             float(bn.eps), float(bn.momentum), act, lay, BF16, _stream())
 
 
 def _bn_bwd_lay(L, dy, dy2, x, y, dx, dres, bn, stats, N, C, HW, act, lay, ps=None):
     dg, db = grad_sink.out_like(bn.weight), grad_sink.out_like(bn.bias)
-    _ck(L.cot_bn_act_backward_lay(_p(dy), _p(dy2), _p(x), _p(y), _p(dx), _p(dres), _p(bn.weight), _p(bn.bias), _p(stats), _p(stats[C:]),
-                                  _p(dg), _p(db), _p(ps), N, C, HW, act, lay, BF16, _stream()), "cot_bn_act_backward_lay")
+    L.cot_bn_act_backward_lay(_p(dy), _p(dy2), _p(x), _p(y), _p(dx), _p(dres), _p(bn.weight), _p(bn.bias), _p(stats), _p(stats[C:]),
+                              _p(dg), _p(db), _p(ps), N, C, HW, act, lay, BF16, _stream())
     return dg, db
 
 
@@ -156,7 +157,7 @@ class _BottleneckCMNode(Function):
     @staticmethod
     @_one_stream_query
     def forward(ctx, blk, x, *params):
-        L = _lib.lib()
+        L = _lib.api()
         bp = _block_plan(blk)
         pl = _plan(bp.cot)
         N, Cin, H0, W0 = x.shape
@@ -181,20 +182,20 @@ class _BottleneckCMNode(Function):
             # conv1 -> bn1 + relu on the 2H x 2W input planes (NCHW, the ordinary kernels), pooled to H x W: a1 (NCHW with margins) and
             # its channel-major copy for the 1x1 convolutions
             c1 = torch.empty((N, C, H0, W0), dtype=x.dtype, device=dev)
-            _ck(L.cot_conv1x1_forward(_p(xb), None, Cin, _p(bp.conv1.weight), None, _p(c1), N, Cin, C, H0 * W0, BF16, st), "cot_conv1x1_forward")
+            L.cot_conv1x1_forward(_p(xb), None, Cin, _p(bp.conv1.weight), None, _p(c1), N, Cin, C, H0 * W0, BF16, st)
             a1f = torch.empty_like(c1)
             s_1 = stat(C, nws_c)
             _bn_fwd(L, c1, a1f, bp.bn1, s_1, 2 * C, N, C, H0 * W0, 1)
             a1 = _new_guarded(N, C, H, W, x.dtype, dev)
-            _ck(L.cot_avgpool3x3s2_forward(_p(a1f), _p(a1), N * C, H0, W0, BF16, st), "cot_avgpool3x3s2_forward")
+            L.cot_avgpool3x3s2_forward(_p(a1f), _p(a1), N * C, H0, W0, BF16, st)
             a1c = a1.permute(1, 0, 2, 3).contiguous()
         else:
             # conv1 -> bn1 + relu -> a1 (NCHW with margins: the 3x3 weight gradient reads it shifted) and a1c (channel-major)
             c1 = cmj(C) if in_cm else nchw(C)
             if in_cm:
-                _ck(L.cot_conv1x1_forward(_p(xb), None, Cin, _p(bp.conv1.weight), None, _p(c1), 1, Cin, C, M, BF16, st), "cot_conv1x1_forward")
+                L.cot_conv1x1_forward(_p(xb), None, Cin, _p(bp.conv1.weight), None, _p(c1), 1, Cin, C, M, BF16, st)
             else:
-                _ck(L.cot_conv1x1_forward(_p(xb), None, Cin, _p(bp.conv1.weight), None, _p(c1), N, Cin, C, HW, BF16, st), "cot_conv1x1_forward")
+                L.cot_conv1x1_forward(_p(xb), None, Cin, _p(bp.conv1.weight), None, _p(c1), N, Cin, C, HW, BF16, st)
             a1, a1c = _new_guarded(N, C, H, W, x.dtype, dev), cmj(C)
             s_1 = stat(C, 0)
             _bn_fwd_lay(L, c1, None, a1, a1c, bp.bn1, s_1, N, C, HW, 1, (1 if in_cm else 0) | 8)
@@ -214,32 +215,30 @@ class _BottleneckCMNode(Function):
             qk = pl.em0.weight.view(Ch, C // 2, 2).permute(0, 2, 1).reshape(Ch, C)  # [Ch][x-part C/2 | k-part C/2], a copy (kept for the backward)
             Hc, Mg = C // 2, Ch // 2
             for g_ in range(2):
-                _ck(L.cot_conv1x1_forward(_p(a1c[g_ * Hc:]), _p(k[g_ * Hc:]), Hc, _p(qk[g_ * Mg:]), None, _p(e0[g_ * Mg:]), 1, C, Mg, M, BF16, st),
-                    "cot_conv1x1_forward")
+                L.cot_conv1x1_forward(_p(a1c[g_ * Hc:]), _p(k[g_ * Hc:]), Hc, _p(qk[g_ * Mg:]), None, _p(e0[g_ * Mg:]), 1, C, Mg, M, BF16, st)
         elif GX:
             qk = torch.stack([a1c, k], dim=1).view(2 * C, N, H, W)  # rows x0, k0, x1, k1, ... (ref :153-154)
-            _ck(L.cot_conv1x1g_forward(_p(qk), _p(pl.em0.weight), None, _p(e0), 1, 2 * C, Ch, 2, M, BF16, st), "cot_conv1x1g_forward")
+            L.cot_conv1x1g_forward(_p(qk), _p(pl.em0.weight), None, _p(e0), 1, 2 * C, Ch, 2, M, BF16, st)
         else:
-            _ck(L.cot_conv1x1_forward(_p(a1c), _p(k), C, _p(pl.em0.weight), None, _p(e0), 1, 2 * C, Ch, M, BF16, st), "cot_conv1x1_forward")
+            L.cot_conv1x1_forward(_p(a1c), _p(k), C, _p(pl.em0.weight), None, _p(e0), 1, 2 * C, Ch, M, BF16, st)
         s_e = stat(Ch, nws_h1)
         _bn_fwd(L, e0, e1, pl.em1, s_e, 2 * Ch, 1, Ch, M, 1)
         if GX:
-            _ck(L.cot_conv1x1g_forward(_p(e1), _p(pl.em3.weight), _p(pl.em3.bias), _p(e3), 1, Ch, Ce, 2, M, BF16, st), "cot_conv1x1g_forward")
+            L.cot_conv1x1g_forward(_p(e1), _p(pl.em3.weight), _p(pl.em3.bias), _p(e3), 1, Ch, Ce, 2, M, BF16, st)
         else:
-            _ck(L.cot_conv1x1_forward(_p(e1), None, Ch, _p(pl.em3.weight), _p(pl.em3.bias), _p(e3), 1, Ch, Ce, M, BF16, st),
-                "cot_conv1x1_forward")
+            L.cot_conv1x1_forward(_p(e1), None, Ch, _p(pl.em3.weight), _p(pl.em3.bias), _p(e3), 1, Ch, Ce, M, BF16, st)
         gn = pl.gn
         w = nchw(Ce)
         gn_mean = torch.empty(2 * N * gn.num_groups, dtype=torch.float32, device=dev)
         gn_rstd = gn_mean[N * gn.num_groups:]
-        _ck(L.cot_group_norm9_forward_lay(_p(e3), _p(gn.weight), _p(gn.bias), _p(w), _p(gn_mean), _p(gn_rstd), N, Ce, HW, float(gn.eps), 1,
-                                          BF16, st), "cot_group_norm9_forward_lay")
+        L.cot_group_norm9_forward_lay(_p(e3), _p(gn.weight), _p(gn.bias), _p(w), _p(gn_mean), _p(gn_rstd), N, Ce, HW, float(gn.eps), 1,
+                                      BF16, st)
         # values: 1x1 on channel rows, its BatchNorm writes NCHW                                                     (ref :87)
         v_pre, v = cmj(C), nchw(C)
         if GX:
-            _ck(L.cot_conv1x1g_forward(_p(a1c), _p(pl.cv0.weight), None, _p(v_pre), 1, C, C, 2, M, BF16, st), "cot_conv1x1g_forward")
+            L.cot_conv1x1g_forward(_p(a1c), _p(pl.cv0.weight), None, _p(v_pre), 1, C, C, 2, M, BF16, st)
         else:
-            _ck(L.cot_conv1x1_forward(_p(a1c), None, C, _p(pl.cv0.weight), None, _p(v_pre), 1, C, C, M, BF16, st), "cot_conv1x1_forward")
+            L.cot_conv1x1_forward(_p(a1c), None, C, _p(pl.cv0.weight), None, _p(v_pre), 1, C, C, M, BF16, st)
         s_v = stat(C, 0)
         _bn_fwd_lay(L, v_pre, None, v, None, pl.cv1, s_v, N, C, HW, 0, 1)
         # aggregation, bn + swish (NCHW)                                                                            (ref :88-90)
@@ -252,7 +251,7 @@ class _BottleneckCMNode(Function):
         if bn_tail:  # (aggregation + the statistics of bn out of its epilogue; bn + swish themselves happen inside the tail's kernels)
             y_final = clf._agg_fwd_stats(L, v, w, a, None, None, None, geom, bnl, s_y, N, C, H, W)
         else:
-            _ck(L.cot_agg_forward(_p(v), _p(w), _p(a), ctypes.byref(geom), BF16, _lib.COT_NCHW, st), "cot_agg_forward")
+            L.cot_agg_forward(_p(v), _p(w), _p(a), ctypes.byref(geom), BF16, _lib.COT_NCHW, st)
             _bn_fwd(L, a, y, bnl, s_y, 2 * C, N, C, HW, 2)
         # radix-2 split attention: y NCHW, k channel-major, the mix written channel-major for conv3                (ref :92-104)
         row = lambda c: torch.empty((c, N), dtype=x.dtype, device=dev)  # noqa: E731
@@ -260,29 +259,28 @@ class _BottleneckCMNode(Function):
         if bn_tail:
             clf._tail_gap(L, a, k, gapT, bnl, s_y, y_final, N, C, HW, 2)
         else:
-            _ck(L.cot_radix_gap_t_lay(_p(y), _p(k), _p(gapT), N, C, HW, 2, BF16, st), "cot_radix_gap_t_lay")
-        _ck(L.cot_conv1x1_forward(_p(gapT), None, C, _p(pl.se0.weight), _p(pl.se0.bias), _p(hpre), 1, C, A, N, BF16, st), "cot_conv1x1_forward")
+            L.cot_radix_gap_t_lay(_p(y), _p(k), _p(gapT), N, C, HW, 2, BF16, st)
+        L.cot_conv1x1_forward(_p(gapT), None, C, _p(pl.se0.weight), _p(pl.se0.bias), _p(hpre), 1, C, A, N, BF16, st)
         s_a = stat(A, nws_a)
         _bn_fwd(L, hpre, h, pl.sebn, s_a, 2 * A, 1, A, N, 1)
-        _ck(L.cot_conv1x1_forward(_p(h), None, A, _p(pl.se3.weight), _p(pl.se3.bias), _p(logitsT), 1, A, 2 * C, N, BF16, st),
-            "cot_conv1x1_forward")
+        L.cot_conv1x1_forward(_p(h), None, A, _p(pl.se3.weight), _p(pl.se3.bias), _p(logitsT), 1, A, 2 * C, N, BF16, st)
         attn = torch.empty((N, C, 2), dtype=x.dtype, device=dev)
         cot_out = cmj(C)
         if bn_tail:
-            _ck(L.cot_radix_mix_logits_bn(_p(a), _p(k), _p(logitsT), _p(cot_out), _p(attn), _p(bnl.weight), _p(bnl.bias), _p(s_y), _p(s_y[C:]),
-                                          N, C, HW, 2 | 4, BF16, st), "cot_radix_mix_logits_bn")
+            L.cot_radix_mix_logits_bn(_p(a), _p(k), _p(logitsT), _p(cot_out), _p(attn), _p(bnl.weight), _p(bnl.bias), _p(s_y), _p(s_y[C:]),
+                                      N, C, HW, 2 | 4, BF16, st)
         else:
-            _ck(L.cot_radix_mix_logits_lay(_p(y), _p(k), _p(logitsT), _p(cot_out), _p(attn), N, C, HW, 2 | 4, BF16, st), "cot_radix_mix_logits_lay")
+            L.cot_radix_mix_logits_lay(_p(y), _p(k), _p(logitsT), _p(cot_out), _p(attn), N, C, HW, 2 | 4, BF16, st)
         # conv3 -> bn3 + residual + relu.  The residual: the block's input (identity) or bn(conv1x1(every second pixel of it))
         c3 = cmj(Cout)
-        _ck(L.cot_conv1x1_forward(_p(cot_out), None, C, _p(bp.conv3.weight), None, _p(c3), 1, C, Cout, M, BF16, st), "cot_conv1x1_forward")
+        L.cot_conv1x1_forward(_p(cot_out), None, C, _p(bp.conv3.weight), None, _p(c3), 1, C, Cout, M, BF16, st)
         ps = _drop_path_scale(blk, N, dev)
         yb = cmj(Cout) if out_cm else nchw(Cout)
         if opening:
             xs = torch.empty((N, Cin, H, W), dtype=x.dtype, device=dev)
-            _ck(L.cot_subsample2_forward(_p(xb), _p(xs), N * Cin, H0, W0, BF16, st), "cot_subsample2_forward")
+            L.cot_subsample2_forward(_p(xb), _p(xs), N * Cin, H0, W0, BF16, st)
             d0 = nchw(Cout)
-            _ck(L.cot_conv1x1_forward(_p(xs), None, Cin, _p(bp.ds_conv.weight), None, _p(d0), N, Cin, Cout, HW, BF16, st), "cot_conv1x1_forward")
+            L.cot_conv1x1_forward(_p(xs), None, Cin, _p(bp.ds_conv.weight), None, _p(d0), N, Cin, Cout, HW, BF16, st)
             res_cm = out_cm  # (the projection's BatchNorm writes the layout bn3 writes)
             res = cmj(Cout) if res_cm else nchw(Cout)
             s_d = stat(Cout, 0)
@@ -307,7 +305,7 @@ class _BottleneckCMNode(Function):
     @staticmethod
     @_one_stream_query
     def backward(ctx, gout):
-        L = _lib.lib()
+        L = _lib.api()
         blk = ctx.blk
         bp = _block_plan(blk)
         pl = _plan(bp.cot)
@@ -350,69 +348,65 @@ class _BottleneckCMNode(Function):
             d_bn3_w, d_bn3_b = _bn_bwd_lay(L, gb, None, c3, yb, g_c3, g_res, bp.bn3, s_3, N, Cout, HW, 1,
                                            (1 if out_cm else 0) | 4 | (8 if out_cm else 0) | 16 | (32 if res_cm else 0), ps=ps)
         g_out = cmj(C)
-        _ck(L.cot_conv1x1_backward_data(_p(g_c3), _p(bp.conv3.weight), _p(g_out), None, C, 0, _p(ws), 1, C, Cout, M, BF16, st),
-            "cot_conv1x1_backward_data")
+        L.cot_conv1x1_backward_data(_p(g_c3), _p(bp.conv3.weight), _p(g_out), None, C, 0, _p(ws), 1, C, Cout, M, BF16, st)
         g_w3c = grad_sink.out_like(bp.conv3.weight)
-        side.run(lambda st_, a_=(_p(g_c3), _p(cot_out), None, C, _p(g_w3c), None, _p(side.ws), 1, C, Cout, M, BF16): _ck(L.cot_conv1x1_backward_weight(*a_, st_), "cot_conv1x1_backward_weight"), g_c3, cot_out)
+        side.run(lambda st_, a_=(_p(g_c3), _p(cot_out), None, C, _p(g_w3c), None, _p(side.ws), 1, C, Cout, M, BF16): L.cot_conv1x1_backward_weight(*a_, st_), g_c3, cot_out)
         # radix mix -> pair-softmax backward -> se branch -> gap
         row = lambda c: torch.empty((c, N), dtype=a1.dtype, device=dev)  # noqa: E731
         glogT, gh, ggapT = row(2 * C), row(A), row(C)
         bnl = pl.bn
         if y is None:  # (the forward folded bn + swish into the tail: so does the backward)
             tsum = torch.empty(N * C * 4, dtype=torch.float32, device=dev)
-            _ck(L.cot_radix_mix_backward_reduce_bn(_p(g_out), _p(a), _p(k), _p(attn), _p(glogT), _p(tsum), _p(bnl.weight), _p(bnl.bias),
-                                                   _p(s_y), _p(s_y[C:]), N, C, HW, 1 | 4, BF16, st), "cot_radix_mix_backward_reduce_bn")
+            L.cot_radix_mix_backward_reduce_bn(_p(g_out), _p(a), _p(k), _p(attn), _p(glogT), _p(tsum), _p(bnl.weight), _p(bnl.bias),
+                                               _p(s_y), _p(s_y[C:]), N, C, HW, 1 | 4, BF16, st)
         else:
-            _ck(L.cot_radix_mix_backward_reduce_lay(_p(g_out), _p(y), _p(k), _p(attn), _p(glogT), N, C, HW, 1 | 4, BF16, st),
-                "cot_radix_mix_backward_reduce_lay")
-        _ck(L.cot_conv1x1_backward_data(_p(glogT), _p(se3.weight), _p(gh), None, A, 0, _p(ws), 1, A, 2 * C, N, BF16, st), "cot_conv1x1_backward_data")
+            L.cot_radix_mix_backward_reduce_lay(_p(g_out), _p(y), _p(k), _p(attn), _p(glogT), N, C, HW, 1 | 4, BF16, st)
+        L.cot_conv1x1_backward_data(_p(glogT), _p(se3.weight), _p(gh), None, A, 0, _p(ws), 1, A, 2 * C, N, BF16, st)
         g_w3, g_b3 = grad_sink.out_like(se3.weight), grad_sink.out_like(se3.bias)
-        side.run(lambda st_, a_=(_p(glogT), _p(h), None, A, _p(g_w3), _p(g_b3), _p(side.ws), 1, A, 2 * C, N, BF16): _ck(L.cot_conv1x1_backward_weight(*a_, st_), "cot_conv1x1_backward_weight"), glogT, h)
+        side.run(lambda st_, a_=(_p(glogT), _p(h), None, A, _p(g_w3), _p(g_b3), _p(side.ws), 1, A, 2 * C, N, BF16): L.cot_conv1x1_backward_weight(*a_, st_), glogT, h)
         ghpre = row(A)
         d_sa_w, d_sa_b = _bn_bwd(L, gh, hpre, None, ghpre, sebn, s_a, 1, A, N, 1, nws_a)
-        _ck(L.cot_conv1x1_backward_data(_p(ghpre), _p(se0.weight), _p(ggapT), None, C, 0, _p(ws), 1, C, A, N, BF16, st), "cot_conv1x1_backward_data")
+        L.cot_conv1x1_backward_data(_p(ghpre), _p(se0.weight), _p(ggapT), None, C, 0, _p(ws), 1, C, A, N, BF16, st)
         g_w0, g_b0 = grad_sink.out_like(se0.weight), grad_sink.out_like(se0.bias)
-        side.run(lambda st_, a_=(_p(ghpre), _p(gapT), None, C, _p(g_w0), _p(g_b0), _p(side.ws), 1, C, A, N, BF16): _ck(L.cot_conv1x1_backward_weight(*a_, st_), "cot_conv1x1_backward_weight"), ghpre, gapT)
+        side.run(lambda st_, a_=(_p(ghpre), _p(gapT), None, C, _p(g_w0), _p(g_b0), _p(side.ws), 1, C, A, N, BF16): L.cot_conv1x1_backward_weight(*a_, st_), ghpre, gapT)
         # bn + swish, aggregation (NCHW)
         ga, gk = nchw(C), cmj(C)
         if y is None:
             d_bn_w, d_bn_b = grad_sink.out_like(bnl.weight), grad_sink.out_like(bnl.bias)
-            _ck(L.cot_radix_mix_backward_apply_bn(_p(g_out), _p(a), _p(attn), _p(ggapT), _p(tsum), _p(ga), _p(gk), _p(bnl.weight),
-                                                  _p(bnl.bias), _p(s_y), _p(s_y[C:]), _p(d_bn_w), _p(d_bn_b), N, C, HW, 1 | 4, BF16, st),
-                "cot_radix_mix_backward_apply_bn")
+            L.cot_radix_mix_backward_apply_bn(_p(g_out), _p(a), _p(attn), _p(ggapT), _p(tsum), _p(ga), _p(gk), _p(bnl.weight),
+                                              _p(bnl.bias), _p(s_y), _p(s_y[C:]), _p(d_bn_w), _p(d_bn_b), N, C, HW, 1 | 4, BF16, st)
         else:
             gy = nchw(C)
-            _ck(L.cot_radix_mix_backward_apply_lay(_p(g_out), _p(attn), _p(ggapT), _p(gy), _p(gk), N, C, HW, 1 | 4, BF16, st),
-                "cot_radix_mix_backward_apply_lay")
+            L.cot_radix_mix_backward_apply_lay(_p(g_out), _p(attn), _p(ggapT), _p(gy), _p(gk), N, C, HW, 1 | 4, BF16, st)
             d_bn_w, d_bn_b = _bn_bwd(L, gy, a, None, ga, bnl, s_y, N, C, HW, 2, nws_c)
         gv, gw = nchw(C), nchw(Ce)
-        _ck(L.cot_agg_backward(_p(ga), _p(v), _p(w), _p(gv), _p(gw), ctypes.byref(ctx.geom), BF16, _lib.COT_NCHW, st), "cot_agg_backward")
+        L.cot_agg_backward(_p(ga), _p(v), _p(w), _p(gv), _p(gw), ctypes.byref(ctx.geom), BF16, _lib.COT_NCHW, st)
         # values branch: bn (NCHW gradient in, channel-major out), 1x1 -> first contribution to the channel-major dx
         gv_pre = cmj(C)
         d_cv_w, d_cv_b = _bn_bwd_lay(L, gv, None, v_pre, None, gv_pre, None, cv1, s_v, N, C, HW, 0, 4 | 16)
         gxc = cmj(C)
         g_wv = grad_sink.out_like(cv0.weight)
         if GX:
-            _ck(L.cot_conv1x1g_backward_data(_p(gv_pre), _p(cv0.weight), _p(gxc), 0, 1, C, C, 2, M, BF16, st), "cot_conv1x1g_backward_data")
-            side.run(lambda st_, a_=(_p(gv_pre), _p(a1c), _p(g_wv), None, _p(side.ws), 1, C, C, 2, M, BF16): _ck(L.cot_conv1x1g_backward_weight(*a_, st_), "cot_conv1x1g_backward_weight"), gv_pre, a1c)
+            L.cot_conv1x1g_backward_data(_p(gv_pre), _p(cv0.weight), _p(gxc), 0, 1, C, C, 2, M, BF16, st)
+            side.run(lambda st_, a_=(_p(gv_pre), _p(a1c), _p(g_wv), None, _p(side.ws), 1, C, C, 2, M, BF16): L.cot_conv1x1g_backward_weight(*a_, st_), gv_pre, a1c)
         else:
-            _ck(L.cot_conv1x1_backward_data(_p(gv_pre), _p(cv0.weight), _p(gxc), None, C, 0, _p(ws), 1, C, C, M, BF16, st), "cot_conv1x1_backward_data")
-            side.run(lambda st_, a_=(_p(gv_pre), _p(a1c), None, C, _p(g_wv), None, _p(side.ws), 1, C, C, M, BF16): _ck(L.cot_conv1x1_backward_weight(*a_, st_), "cot_conv1x1_backward_weight"), gv_pre, a1c)
+            L.cot_conv1x1_backward_data(_p(gv_pre), _p(cv0.weight), _p(gxc), None, C, 0, _p(ws), 1, C, C, M, BF16, st)
+            side.run(lambda st_, a_=(_p(gv_pre), _p(a1c), None, C, _p(g_wv), None, _p(side.ws), 1, C, C, M, BF16): L.cot_conv1x1_backward_weight(*a_, st_), gv_pre, a1c)
         # logits branch: GroupNorm (NCHW gradient in, channel-major out), 1x1 (+bias), bn + relu, 1x1 on [x | k] -> dx +=, dk +=
         gn = pl.gn
         ge3, g_gn_w, g_gn_b = cmj(Ce), grad_sink.out_like(gn.weight), grad_sink.out_like(gn.bias)
         gn_ws = torch.empty(2 * N * Ce, dtype=torch.float32, device=dev)
-        _ck(L.cot_group_norm9_backward_lay(_p(gw), _p(e3), _p(gn_mean), _p(gn_rstd), _p(gn.weight), _p(ge3), None, None, _p(gn_ws),
-                                           N, Ce, HW, 2 | 4, BF16, st), "cot_group_norm9_backward_lay")
-        side.run(lambda st_, a_=(_p(gn_ws), _p(g_gn_w), _p(g_gn_b), N, Ce, BF16): _ck(L.cot_group_norm9_backward_params(*a_, st_), "cot_group_norm9_backward_params"), gn_ws)
+        L.cot_group_norm9_backward_lay(_p(gw), _p(e3), _p(gn_mean), _p(gn_rstd), _p(gn.weight), _p(ge3), None, None, _p(gn_ws),
+                                       N, Ce, HW, 2 | 4, BF16, st)
+        side.run(lambda st_, a_=(_p(gn_ws), _p(g_gn_w), _p(g_gn_b), N, Ce, BF16): L.cot_group_norm9_backward_params(*a_, st_), gn_ws)
         ge1 = cmj(Ch)
         g_we3, g_be3 = grad_sink.out_like(em3.weight), grad_sink.out_like(em3.bias)
         if GX:
-            _ck(L.cot_conv1x1g_backward_data(_p(ge3), _p(em3.weight), _p(ge1), 0, 1, Ch, Ce, 2, M, BF16, st), "cot_conv1x1g_backward_data")
-            side.run(lambda st_, a_=(_p(ge3), _p(e1), _p(g_we3), _p(g_be3), _p(side.ws), 1, Ch, Ce, 2, M, BF16): _ck(L.cot_conv1x1g_backward_weight(*a_, st_), "cot_conv1x1g_backward_weight"), ge3, e1)
+            L.cot_conv1x1g_backward_data(_p(ge3), _p(em3.weight), _p(ge1), 0, 1, Ch, Ce, 2, M, BF16, st)
+            side.run(lambda st_, a_=(_p(ge3), _p(e1), _p(g_we3), _p(g_be3), _p(side.ws), 1, Ch, Ce, 2, M, BF16): L.cot_conv1x1g_backward_weight(*a_, st_), ge3, e1)
         else:
-            _ck(L.cot_conv1x1_backward_data(_p(ge3), _p(em3.weight), _p(ge1), None, Ch, 0, _p(ws), 1, Ch, Ce, M, BF16, st), "cot_conv1x1_backward_data")
-            side.run(lambda st_, a_=(_p(ge3), _p(e1), None, Ch, _p(g_we3), _p(g_be3), _p(side.ws), 1, Ch, Ce, M, BF16): _ck(L.cot_conv1x1_backward_weight(*a_, st_), "cot_conv1x1_backward_weight"), ge3, e1)
+            L.cot_conv1x1_backward_data(_p(ge3), _p(em3.weight), _p(ge1), None, Ch, 0, _p(ws), 1, Ch, Ce, M, BF16, st)
+            side.run(lambda st_, a_=(_p(ge3), _p(e1), None, Ch, _p(g_we3), _p(g_be3), _p(side.ws), 1, Ch, Ce, M, BF16): L.cot_conv1x1_backward_weight(*a_, st_), ge3, e1)
         ge0 = cmj(Ch)
         d_em_w, d_em_b = _bn_bwd(L, ge1, e0, None, ge0, em1, s_e, 1, Ch, M, 1, nws_h1)
         g_we0 = grad_sink.out_like(em0.weight)
@@ -420,9 +414,9 @@ class _BottleneckCMNode(Function):
             Hc, Mg = C // 2, Ch // 2
             gwp = torch.empty_like(qk)  # gradient w.r.t. the de-interleaved weight, re-interleaved into the parameter's slot below
             for g_ in range(2):
-                _ck(L.cot_conv1x1_backward_data(_p(ge0[g_ * Mg:]), _p(qk[g_ * Mg:]), _p(gxc[g_ * Hc:]), _p(gk[g_ * Hc:]), Hc, 3, _p(ws), 1, C, Mg, M,
-                                                BF16, st), "cot_conv1x1_backward_data")
-                side.run(lambda st_, a_=(_p(ge0[g_ * Mg:]), _p(a1c[g_ * Hc:]), _p(k[g_ * Hc:]), Hc, _p(gwp[g_ * Mg:]), None, _p(side.ws), 1, C, Mg, M, BF16): _ck(L.cot_conv1x1_backward_weight(*a_, st_), "cot_conv1x1_backward_weight"), ge0, a1c, k, gwp)
+                L.cot_conv1x1_backward_data(_p(ge0[g_ * Mg:]), _p(qk[g_ * Mg:]), _p(gxc[g_ * Hc:]), _p(gk[g_ * Hc:]), Hc, 3, _p(ws), 1, C, Mg, M,
+                                            BF16, st)
+                side.run(lambda st_, a_=(_p(ge0[g_ * Mg:]), _p(a1c[g_ * Hc:]), _p(k[g_ * Hc:]), Hc, _p(gwp[g_ * Mg:]), None, _p(side.ws), 1, C, Mg, M, BF16): L.cot_conv1x1_backward_weight(*a_, st_), ge0, a1c, k, gwp)
 
             def _interleave(st_, dst=g_we0, src=gwp, side_=side):  # [Ch][2][C/2] -> [Ch][C/2][2], behind the two launches above on their stream
                 if side_.on:
@@ -433,19 +427,19 @@ class _BottleneckCMNode(Function):
             side.run(_interleave, gwp)
         elif GX:  # gradient of the row-interleaved [x0, k0, x1, k1, ...]: de-interleaved into dx / dk (two strided adds)
             gqk = torch.empty_like(qk)
-            _ck(L.cot_conv1x1g_backward_data(_p(ge0), _p(em0.weight), _p(gqk), 0, 1, 2 * C, Ch, 2, M, BF16, st), "cot_conv1x1g_backward_data")
+            L.cot_conv1x1g_backward_data(_p(ge0), _p(em0.weight), _p(gqk), 0, 1, 2 * C, Ch, 2, M, BF16, st)
             gq5 = gqk.view(C, 2, N, H, W)
             gxc.add_(gq5[:, 0])
             gk.add_(gq5[:, 1])
-            side.run(lambda st_, a_=(_p(ge0), _p(qk), _p(g_we0), None, _p(side.ws), 1, 2 * C, Ch, 2, M, BF16): _ck(L.cot_conv1x1g_backward_weight(*a_, st_), "cot_conv1x1g_backward_weight"), ge0, qk)
+            side.run(lambda st_, a_=(_p(ge0), _p(qk), _p(g_we0), None, _p(side.ws), 1, 2 * C, Ch, 2, M, BF16): L.cot_conv1x1g_backward_weight(*a_, st_), ge0, qk)
         else:
-            _ck(L.cot_conv1x1_backward_data(_p(ge0), _p(em0.weight), _p(gxc), _p(gk), C, 3, _p(ws), 1, 2 * C, Ch, M, BF16, st), "cot_conv1x1_backward_data")
-            side.run(lambda st_, a_=(_p(ge0), _p(a1c), _p(k), C, _p(g_we0), None, _p(side.ws), 1, 2 * C, Ch, M, BF16): _ck(L.cot_conv1x1_backward_weight(*a_, st_), "cot_conv1x1_backward_weight"), ge0, a1c, k)
+            L.cot_conv1x1_backward_data(_p(ge0), _p(em0.weight), _p(gxc), _p(gk), C, 3, _p(ws), 1, 2 * C, Ch, M, BF16, st)
+            side.run(lambda st_, a_=(_p(ge0), _p(a1c), _p(k), C, _p(g_we0), None, _p(side.ws), 1, 2 * C, Ch, M, BF16): L.cot_conv1x1_backward_weight(*a_, st_), ge0, a1c, k)
         # key branch: bn + relu (channel-major gradient in, NCHW out), grouped 3x3 -> the NCHW contribution to dx
         gk_pre = nchw(C)
         d_ke_w, d_ke_b = _bn_bwd_lay(L, gk, None, k_pre, None, gk_pre, None, ke1, s_k, N, C, HW, 1, 1)
         g_wk = grad_sink.out_like(ke0.weight)
-        side.run(lambda st_, a_=(_p(gk_pre), _p(a1), _p(g_wk), _p(masks), _p(side.ws), N, C, C, G, H, W, BF16, _guard_elems(a1)): _ck(L.cot_conv3x3g_backward_weight_guarded(*a_, st_), "cot_conv3x3g_backward_weight"), gk_pre, a1, masks)
+        side.run(lambda st_, a_=(_p(gk_pre), _p(a1), _p(g_wk), _p(masks), _p(side.ws), N, C, C, G, H, W, BF16, _guard_elems(a1)): L.cot_conv3x3g_backward_weight_guarded(*a_, st_), gk_pre, a1, masks)
         gx3 = nchw(C)
         _conv3x3_dgrad(L, ke0, gk_pre, gx3, 0, masks, ws, N, C, G, H, W)
         g_w1 = grad_sink.out_like(bp.conv1.weight)
@@ -455,38 +449,35 @@ class _BottleneckCMNode(Function):
             # pooling, bn1 and conv1 at the input resolution; the projection: its BatchNorm takes the residual gradient in bn3's layout
             gx3.add_(_cm_view(gxc))
             g_a1f = torch.empty((N, C, H0, W0), dtype=a1.dtype, device=dev)
-            _ck(L.cot_avgpool3x3s2_backward(_p(gx3), _p(g_a1f), N * C, H0, W0, BF16, st), "cot_avgpool3x3s2_backward")
+            L.cot_avgpool3x3s2_backward(_p(gx3), _p(g_a1f), N * C, H0, W0, BF16, st)
             g_c1 = torch.empty_like(c1)
             d_bn1_w, d_bn1_b = _bn_bwd(L, g_a1f, c1, None, g_c1, bp.bn1, s_1, N, C, H0 * W0, 1, nws_c)
             g_d0 = nchw(Cout)
             d_ds_w, d_ds_b = _bn_bwd_lay(L, g_res, None, d0, None, g_d0, None, bp.ds_bn, s_d, N, Cout, HW, 0, 1 if res_cm else 0)
             g_xs = torch.empty_like(xs)
-            _ck(L.cot_conv1x1_backward_data(_p(g_d0), _p(bp.ds_conv.weight), _p(g_xs), None, Cin, 0, _p(ws), N, Cin, Cout, HW, BF16, st),
-                "cot_conv1x1_backward_data")
+            L.cot_conv1x1_backward_data(_p(g_d0), _p(bp.ds_conv.weight), _p(g_xs), None, Cin, 0, _p(ws), N, Cin, Cout, HW, BF16, st)
             gx = torch.empty_like(xb)
-            _ck(L.cot_subsample2_backward(_p(g_xs), _p(gx), N * Cin, H0, W0, BF16, st), "cot_subsample2_backward")
+            L.cot_subsample2_backward(_p(g_xs), _p(gx), N * Cin, H0, W0, BF16, st)
             g_wd = grad_sink.out_like(bp.ds_conv.weight)
-            side.run(lambda st_, a_=(_p(g_d0), _p(xs), None, Cin, _p(g_wd), None, _p(side.ws), N, Cin, Cout, HW, BF16): _ck(L.cot_conv1x1_backward_weight(*a_, st_), "cot_conv1x1_backward_weight"), g_d0, xs)
+            side.run(lambda st_, a_=(_p(g_d0), _p(xs), None, Cin, _p(g_wd), None, _p(side.ws), N, Cin, Cout, HW, BF16): L.cot_conv1x1_backward_weight(*a_, st_), g_d0, xs)
             g_ds = (g_wd, d_ds_w, d_ds_b)
-            side.run(lambda st_, a_=(_p(g_c1), _p(xb), None, Cin, _p(g_w1), None, _p(side.ws), N, Cin, C, H0 * W0, BF16): _ck(L.cot_conv1x1_backward_weight(*a_, st_), "cot_conv1x1_backward_weight"), g_c1, xb)
-            _ck(L.cot_conv1x1_backward_data(_p(g_c1), _p(bp.conv1.weight), _p(gx), None, Cin, 1, _p(ws), N, Cin, C, H0 * W0, BF16, st),
-                "cot_conv1x1_backward_data")
+            side.run(lambda st_, a_=(_p(g_c1), _p(xb), None, Cin, _p(g_w1), None, _p(side.ws), N, Cin, C, H0 * W0, BF16): L.cot_conv1x1_backward_weight(*a_, st_), g_c1, xb)
+            L.cot_conv1x1_backward_data(_p(g_c1), _p(bp.conv1.weight), _p(gx), None, Cin, 1, _p(ws), N, Cin, C, H0 * W0, BF16, st)
         else:
             # bn1: the two contributions to da1 (channel-major from the 1x1s, NCHW from the 3x3) meet in its backward
             g_c1 = cmj(C) if in_cm else nchw(C)
             d_bn1_w, d_bn1_b = _bn_bwd_lay(L, gxc, gx3, c1, None, g_c1, None, bp.bn1, s_1, N, C, HW, 1, 1 | (4 if in_cm else 0) | (16 if in_cm else 0))
             gx = g_res  # identity shortcut: the residual's gradient is the first contribution to dx
             if in_cm:
-                side.run(lambda st_, a_=(_p(g_c1), _p(xb), None, Cin, _p(g_w1), None, _p(side.ws), 1, Cin, C, M, BF16): _ck(L.cot_conv1x1_backward_weight(*a_, st_), "cot_conv1x1_backward_weight"), g_c1, xb)
+                side.run(lambda st_, a_=(_p(g_c1), _p(xb), None, Cin, _p(g_w1), None, _p(side.ws), 1, Cin, C, M, BF16): L.cot_conv1x1_backward_weight(*a_, st_), g_c1, xb)
                 if fold:
                     gx = cmj(Cin)
-                    _ck(L.cot_conv1x1_backward_data_relu_res(_p(g_c1), _p(bp.conv1.weight), _p(gx), _p(gb), _p(m3), 1, Cin, C, M, BF16, st),
-                        "cot_conv1x1_backward_data_relu_res")
+                    L.cot_conv1x1_backward_data_relu_res(_p(g_c1), _p(bp.conv1.weight), _p(gx), _p(gb), _p(m3), 1, Cin, C, M, BF16, st)
                 else:
-                    _ck(L.cot_conv1x1_backward_data(_p(g_c1), _p(bp.conv1.weight), _p(gx), None, Cin, 1, _p(ws), 1, Cin, C, M, BF16, st), "cot_conv1x1_backward_data")
+                    L.cot_conv1x1_backward_data(_p(g_c1), _p(bp.conv1.weight), _p(gx), None, Cin, 1, _p(ws), 1, Cin, C, M, BF16, st)
             else:
-                side.run(lambda st_, a_=(_p(g_c1), _p(xb), None, Cin, _p(g_w1), None, _p(side.ws), N, Cin, C, HW, BF16): _ck(L.cot_conv1x1_backward_weight(*a_, st_), "cot_conv1x1_backward_weight"), g_c1, xb)
-                _ck(L.cot_conv1x1_backward_data(_p(g_c1), _p(bp.conv1.weight), _p(gx), None, Cin, 1, _p(ws), N, Cin, C, HW, BF16, st), "cot_conv1x1_backward_data")
+                side.run(lambda st_, a_=(_p(g_c1), _p(xb), None, Cin, _p(g_w1), None, _p(side.ws), N, Cin, C, HW, BF16): L.cot_conv1x1_backward_weight(*a_, st_), g_c1, xb)
+                L.cot_conv1x1_backward_data(_p(g_c1), _p(bp.conv1.weight), _p(gx), None, Cin, 1, _p(ws), N, Cin, C, HW, BF16, st)
         side.join()
         g_cot = (g_wk, d_ke_w, d_ke_b, g_we0, d_em_w, d_em_b, g_we3, g_be3, g_gn_w, g_gn_b, g_wv, d_cv_w, d_cv_b, d_bn_w, d_bn_b,
                  g_w0, g_b0, d_sa_w, d_sa_b, g_w3, g_b3)

@@ -6,10 +6,11 @@ import torch
 from torch import nn
 from torch.autograd import Function
 from . import _lib, grad_sink
+from ._lib import one_stream_query as _one_stream_query, ptr as _p, stream as _stream
 from . import cot_layer_fused as clf
 from .cot_layer_fused import (  # noqa: E402  (helpers; the switches are read as clf.NAME at call time: tests rebind them there)
-    BF16, NODE_COUNTS, _Side, _bn_bwd, _bn_fwd, _bn_static_ok, _ck, _conv3x3_dgrad, _conv3x3_fwd, _conv_ok,
-    _drop_path_scale, _guard_elems, _masks, _new_guarded, _one_stream_query, _p, _relu_mask, _stream)
+    BF16, NODE_COUNTS, _Side, _bn_bwd, _bn_fwd, _bn_static_ok, _conv3x3_dgrad, _conv3x3_fwd, _conv_ok,
+    _drop_path_scale, _guard_elems, _masks, _new_guarded, _relu_mask)
 
 # ---- SE-CoTNetD's OTHER block kind as one node: CoTBottleneck whose conv2 is SplitAttnConv2d(radix = 1) (models/cotnet_hybrid.py:
 # 138-146, :172-202; models/layers/split_attn.py:62-88) -- conv1 -> bn1+relu -> dense 3x3 -> bn0+act -> SE gate x * sigmoid(fc2(act(
@@ -99,7 +100,7 @@ class _SplitAttnBlockNode(Function):
     @staticmethod
     @_one_stream_query
     def forward(ctx, blk, x, *params):
-        L = _lib.lib()
+        L = _lib.api()
         sp = _sa_plan(blk)
         N, Cin, H, W = x.shape
         Cw, A, G = sp.conv.out_channels, sp.fc1.out_channels, sp.conv.groups
@@ -113,7 +114,7 @@ class _SplitAttnBlockNode(Function):
         new = lambda c, h=H, w=W: torch.empty((N, c, h, w), dtype=x.dtype, device=dev)  # noqa: E731
         stat = lambda c, nws: torch.empty(2 * c + nws, dtype=torch.float32, device=dev)  # noqa: E731
         c1, a1 = new(Cw), _new_guarded(N, Cw, H, W, x.dtype, dev)  # (the 3x3 weight gradient reads a1 shifted: margins)
-        _ck(L.cot_conv1x1_forward(_p(x), None, Cin, _p(sp.conv1.weight), None, _p(c1), N, Cin, Cw, HW, BF16, st), "cot_conv1x1_forward")
+        L.cot_conv1x1_forward(_p(x), None, Cin, _p(sp.conv1.weight), None, _p(c1), N, Cin, Cw, HW, BF16, st)
         s_1 = stat(Cw, nws_w)
         _bn_fwd(L, c1, a1, sp.bn1, s_1, 2 * Cw, N, Cw, HW, 1)
         c2, b2 = new(Cw), new(Cw)
@@ -126,29 +127,29 @@ class _SplitAttnBlockNode(Function):
         # 174 launches + their bias-gradient reductions per SE-CoTNetD-152 step)
         row = lambda c: torch.empty((c, N), dtype=x.dtype, device=dev)  # noqa: E731
         gap, hpre, h, logitsT = row(Cw), row(A), row(A), row(Cw)
-        _ck(L.cot_radix_gap_t(_p(b2), None, _p(gap), N, Cw, HW, BF16, st), "cot_radix_gap_t")
-        _ck(L.cot_conv1x1_forward(_p(gap), None, Cw, _p(sp.fc1.weight), _p(sp.fc1.bias), _p(hpre), 1, Cw, A, N, BF16, st), "cot_conv1x1_forward")
+        L.cot_radix_gap_t(_p(b2), None, _p(gap), N, Cw, HW, BF16, st)
+        L.cot_conv1x1_forward(_p(gap), None, Cw, _p(sp.fc1.weight), _p(sp.fc1.bias), _p(hpre), 1, Cw, A, N, BF16, st)
         s_s = stat(A, nws_a)
         _bn_fwd(L, hpre, h, sp.sbn, s_s, 2 * A, 1, A, N, sp.act1)  # (one image, N pixels: the statistics run over the batch)
-        _ck(L.cot_conv1x1_forward(_p(h), None, A, _p(sp.fc2.weight), _p(sp.fc2.bias), _p(logitsT), 1, A, Cw, N, BF16, st), "cot_conv1x1_forward")
+        L.cot_conv1x1_forward(_p(h), None, A, _p(sp.fc2.weight), _p(sp.fc2.bias), _p(logitsT), 1, A, Cw, N, BF16, st)
         logits = logitsT.t().contiguous()  # [N][Cw]: the gate kernels index it by plane n * Cw + c
         out2 = new(Cw)
-        _ck(L.cot_se_gate(_p(b2), _p(logits), _p(out2), N * Cw, HW, BF16, st), "cot_se_gate")
+        L.cot_se_gate(_p(b2), _p(logits), _p(out2), N * Cw, HW, BF16, st)
         if sp.avd_post:  # anti-aliased down-sampling behind conv2 (cotnet_hybrid.py:196-199; blur_pool.py:53-58)
             out2p = new(Cw, Ho, Wo)
-            _ck(L.cot_blurpool3x3s2_forward(_p(out2), _p(out2p), N * Cw, H, W, BF16, st), "cot_blurpool3x3s2_forward")
+            L.cot_blurpool3x3s2_forward(_p(out2), _p(out2p), N * Cw, H, W, BF16, st)
         else:
             out2p = out2
         c3, y = new(Cout, Ho, Wo), new(Cout, Ho, Wo)
-        _ck(L.cot_conv1x1_forward(_p(out2p), None, Cw, _p(sp.conv3.weight), None, _p(c3), N, Cw, Cout, HWo, BF16, st), "cot_conv1x1_forward")
+        L.cot_conv1x1_forward(_p(out2p), None, Cw, _p(sp.conv3.weight), None, _p(c3), N, Cw, Cout, HWo, BF16, st)
         if sp.ds_conv is not None:  # projection shortcut: bn(conv1x1([avgpool2x2](x)))
             if sp.ds_pool2:
                 xs = new(Cin, Ho, Wo)
-                _ck(L.cot_avgpool2x2s2_forward(_p(x), _p(xs), N * Cin, H, W, BF16, st), "cot_avgpool2x2s2_forward")
+                L.cot_avgpool2x2s2_forward(_p(x), _p(xs), N * Cin, H, W, BF16, st)
             else:
                 xs = x
             d0, res = new(Cout, Ho, Wo), new(Cout, Ho, Wo)
-            _ck(L.cot_conv1x1_forward(_p(xs), None, Cin, _p(sp.ds_conv.weight), None, _p(d0), N, Cin, Cout, HWo, BF16, st), "cot_conv1x1_forward")
+            L.cot_conv1x1_forward(_p(xs), None, Cin, _p(sp.ds_conv.weight), None, _p(d0), N, Cin, Cout, HWo, BF16, st)
             s_d = stat(Cout, nws_o)
             _bn_fwd(L, d0, res, sp.ds_bn, s_d, 2 * Cout, N, Cout, HWo, 0)
         else:
@@ -166,7 +167,7 @@ class _SplitAttnBlockNode(Function):
     @staticmethod
     @_one_stream_query
     def backward(ctx, gout):
-        L = _lib.lib()
+        L = _lib.api()
         blk = ctx.blk
         sp = _sa_plan(blk)
         t = ctx.saved_tensors
@@ -189,33 +190,32 @@ class _SplitAttnBlockNode(Function):
         g_c3, g_res = torch.empty_like(c3), (None if fold else torch.empty_like(c3))  # (fold: the residual's gradient goes into conv1's data gradient)
         d_bn3_w, d_bn3_b = _bn_bwd(L, gout, c3, y, g_c3, sp.bn3, s_3, N, Cout, HWo, 1, nws_o, dres=g_res, ps=ps, mask=m3)
         g_out2p = torch.empty_like(out2p)
-        _ck(L.cot_conv1x1_backward_data(_p(g_c3), _p(sp.conv3.weight), _p(g_out2p), None, Cw, 0, _p(ws), N, Cw, Cout, HWo, BF16, st),
-            "cot_conv1x1_backward_data")
+        L.cot_conv1x1_backward_data(_p(g_c3), _p(sp.conv3.weight), _p(g_out2p), None, Cw, 0, _p(ws), N, Cw, Cout, HWo, BF16, st)
         g_w3 = grad_sink.out_like(sp.conv3.weight)
-        side.run(lambda st_, a_=(_p(g_c3), _p(out2p), None, Cw, _p(g_w3), None, _p(side.ws), N, Cw, Cout, HWo, BF16): _ck(L.cot_conv1x1_backward_weight(*a_, st_), "cot_conv1x1_backward_weight"), g_c3, out2p)
+        side.run(lambda st_, a_=(_p(g_c3), _p(out2p), None, Cw, _p(g_w3), None, _p(side.ws), N, Cw, Cout, HWo, BF16): L.cot_conv1x1_backward_weight(*a_, st_), g_c3, out2p)
         if sp.avd_post:
             g_out2 = torch.empty_like(out2)
-            _ck(L.cot_blurpool3x3s2_backward(_p(g_out2p), _p(g_out2), N * Cw, H, W, BF16, st), "cot_blurpool3x3s2_backward")
+            L.cot_blurpool3x3s2_backward(_p(g_out2p), _p(g_out2), N * Cw, H, W, BF16, st)
         else:
             g_out2 = g_out2p
         # gate: dx of x * sigmoid(l) and dl in one pass; then the two fc layers (GEMMs on [N, .] descriptors) and their BatchNorm
         g_b2, g_log = torch.empty_like(b2), torch.empty_like(logits)
-        _ck(L.cot_se_gate_backward(_p(g_out2), _p(b2), _p(logits), _p(g_b2), _p(g_log), N * Cw, HW, BF16, st), "cot_se_gate_backward")
+        L.cot_se_gate_backward(_p(g_out2), _p(b2), _p(logits), _p(g_b2), _p(g_log), N * Cw, HW, BF16, st)
         row = lambda c: torch.empty((c, N), dtype=x.dtype, device=dev)  # noqa: E731
         g_logT = g_log.t().contiguous()  # [Cw][N]
         g_h, g_hpre, g_gapT = row(A), row(A), row(Cw)
-        _ck(L.cot_conv1x1_backward_data(_p(g_logT), _p(sp.fc2.weight), _p(g_h), None, A, 0, _p(ws), 1, A, Cw, N, BF16, st), "cot_conv1x1_backward_data")
+        L.cot_conv1x1_backward_data(_p(g_logT), _p(sp.fc2.weight), _p(g_h), None, A, 0, _p(ws), 1, A, Cw, N, BF16, st)
         g_fc2_w, g_fc2_b = grad_sink.out_like(sp.fc2.weight), grad_sink.out_like(sp.fc2.bias)
-        side.run(lambda st_, a_=(_p(g_logT), _p(h), None, A, _p(g_fc2_w), _p(g_fc2_b), _p(side.ws), 1, A, Cw, N, BF16): _ck(L.cot_conv1x1_backward_weight(*a_, st_), "cot_conv1x1_backward_weight"), g_logT, h)
+        side.run(lambda st_, a_=(_p(g_logT), _p(h), None, A, _p(g_fc2_w), _p(g_fc2_b), _p(side.ws), 1, A, Cw, N, BF16): L.cot_conv1x1_backward_weight(*a_, st_), g_logT, h)
         d_sbn_w, d_sbn_b = _bn_bwd(L, g_h, hpre, None, g_hpre, sp.sbn, s_s, 1, A, N, sp.act1, nws_a)
-        _ck(L.cot_conv1x1_backward_data(_p(g_hpre), _p(sp.fc1.weight), _p(g_gapT), None, Cw, 0, _p(ws), 1, Cw, A, N, BF16, st), "cot_conv1x1_backward_data")
+        L.cot_conv1x1_backward_data(_p(g_hpre), _p(sp.fc1.weight), _p(g_gapT), None, Cw, 0, _p(ws), 1, Cw, A, N, BF16, st)
         g_fc1_w, g_fc1_b = grad_sink.out_like(sp.fc1.weight), grad_sink.out_like(sp.fc1.bias)
-        side.run(lambda st_, a_=(_p(g_hpre), _p(gap), None, Cw, _p(g_fc1_w), _p(g_fc1_b), _p(side.ws), 1, Cw, A, N, BF16): _ck(L.cot_conv1x1_backward_weight(*a_, st_), "cot_conv1x1_backward_weight"), g_hpre, gap)
+        side.run(lambda st_, a_=(_p(g_hpre), _p(gap), None, Cw, _p(g_fc1_w), _p(g_fc1_b), _p(side.ws), 1, Cw, A, N, BF16): L.cot_conv1x1_backward_weight(*a_, st_), g_hpre, gap)
         g_b2.add_((g_gapT.t().float() / HW).to(g_b2.dtype).reshape(N, Cw, 1, 1))  # d mean_hw: the same value for every pixel of a plane
         g_c2 = g_out2  # (reuse: consumed by the gate's backward)
         d_bn0_w, d_bn0_b = _bn_bwd(L, g_b2, c2, None, g_c2, sp.bn0, s_0, N, Cw, HW, sp.act0, nws_w)
         g_wc = grad_sink.out_like(sp.conv.weight)
-        side.run(lambda st_, a_=(_p(g_c2), _p(a1), _p(g_wc), _p(masks), _p(side.ws), N, Cw, Cw, G, H, W, BF16, _guard_elems(a1)): _ck(L.cot_conv3x3g_backward_weight_guarded(*a_, st_), "cot_conv3x3g_backward_weight"), g_c2, a1, masks)
+        side.run(lambda st_, a_=(_p(g_c2), _p(a1), _p(g_wc), _p(masks), _p(side.ws), N, Cw, Cw, G, H, W, BF16, _guard_elems(a1)): L.cot_conv3x3g_backward_weight_guarded(*a_, st_), g_c2, a1, masks)
         g_a1 = g_b2  # (reuse: consumed by bn0's backward)
         _conv3x3_dgrad(L, sp.conv, g_c2, g_a1, 0, masks, ws, N, Cw, G, H, W)
         g_c1 = torch.empty_like(c1)
@@ -225,27 +225,24 @@ class _SplitAttnBlockNode(Function):
             g_d0 = torch.empty_like(g_c3) if side.on else g_c3  # (g_c3 is still read by conv3's weight gradient on the side stream)
             d_ds_w, d_ds_b = _bn_bwd(L, g_res, d0, None, g_d0, sp.ds_bn, s_d, N, Cout, HWo, 0, nws_o)
             g_xs = torch.empty_like(xs)
-            _ck(L.cot_conv1x1_backward_data(_p(g_d0), _p(sp.ds_conv.weight), _p(g_xs), None, Cin, 0, _p(ws), N, Cin, Cout, HWo, BF16, st),
-                "cot_conv1x1_backward_data")
+            L.cot_conv1x1_backward_data(_p(g_d0), _p(sp.ds_conv.weight), _p(g_xs), None, Cin, 0, _p(ws), N, Cin, Cout, HWo, BF16, st)
             if sp.ds_pool2:
                 gx = torch.empty_like(x)
-                _ck(L.cot_avgpool2x2s2_backward(_p(g_xs), _p(gx), N * Cin, H, W, BF16, st), "cot_avgpool2x2s2_backward")
+                L.cot_avgpool2x2s2_backward(_p(g_xs), _p(gx), N * Cin, H, W, BF16, st)
             else:
                 gx = g_xs
             g_wd = grad_sink.out_like(sp.ds_conv.weight)
-            side.run(lambda st_, a_=(_p(g_d0), _p(xs), None, Cin, _p(g_wd), None, _p(side.ws), N, Cin, Cout, HWo, BF16): _ck(L.cot_conv1x1_backward_weight(*a_, st_), "cot_conv1x1_backward_weight"), g_d0, xs)
+            side.run(lambda st_, a_=(_p(g_d0), _p(xs), None, Cin, _p(g_wd), None, _p(side.ws), N, Cin, Cout, HWo, BF16): L.cot_conv1x1_backward_weight(*a_, st_), g_d0, xs)
             g_ds = (g_wd, d_ds_w, d_ds_b)
         else:
             gx = g_res  # identity shortcut: the residual's gradient is the first contribution to dx
         g_w1 = grad_sink.out_like(sp.conv1.weight)
-        side.run(lambda st_, a_=(_p(g_c1), _p(x), None, Cin, _p(g_w1), None, _p(side.ws), N, Cin, Cw, HW, BF16): _ck(L.cot_conv1x1_backward_weight(*a_, st_), "cot_conv1x1_backward_weight"), g_c1, x)
+        side.run(lambda st_, a_=(_p(g_c1), _p(x), None, Cin, _p(g_w1), None, _p(side.ws), N, Cin, Cw, HW, BF16): L.cot_conv1x1_backward_weight(*a_, st_), g_c1, x)
         if fold:
             gx = torch.empty_like(x)
-            _ck(L.cot_conv1x1_backward_data_relu_res(_p(g_c1), _p(sp.conv1.weight), _p(gx), _p(gout), _p(m3), N, Cin, Cw, HW, BF16, st),
-                "cot_conv1x1_backward_data_relu_res")
+            L.cot_conv1x1_backward_data_relu_res(_p(g_c1), _p(sp.conv1.weight), _p(gx), _p(gout), _p(m3), N, Cin, Cw, HW, BF16, st)
         else:
-            _ck(L.cot_conv1x1_backward_data(_p(g_c1), _p(sp.conv1.weight), _p(gx), None, Cin, 1, _p(ws), N, Cin, Cw, HW, BF16, st),
-                "cot_conv1x1_backward_data")
+            L.cot_conv1x1_backward_data(_p(g_c1), _p(sp.conv1.weight), _p(gx), None, Cin, 1, _p(ws), N, Cin, Cw, HW, BF16, st)
         side.join()
         return (None, gx, g_w1, d_bn1_w, d_bn1_b, g_wc, d_bn0_w, d_bn0_b, g_fc1_w, g_fc1_b, d_sbn_w, d_sbn_b, g_fc2_w, g_fc2_b, g_w3,
                 d_bn3_w, d_bn3_b) + g_ds
@@ -253,7 +250,7 @@ class _SplitAttnBlockNode(Function):
 
 def sa_block_eligible(blk, x):
     """training-mode cotnet_hybrid.CoTBottleneck with a SplitAttnConv2d(radix=1) conv2, identity shortcut, on a bf16 NCHW tensor"""
-    if not (clf.ENABLED and blk.training and (x.is_cuda or not clf._DEVICE_ONLY) and x.dim() == 4 and x.dtype == torch.bfloat16
+    if not (clf.ENABLED and blk.training and (x.is_cuda or not _lib.DEVICE_ONLY) and x.dim() == 4 and x.dtype == torch.bfloat16
             and x.is_contiguous() and x.data_ptr() % 16 == 0):
         return False
     sp = _sa_plan(blk)

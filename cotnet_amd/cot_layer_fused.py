@@ -20,8 +20,6 @@ interleaved once and the group -> batch fold is a view); anything else takes the
 MI355X: ~1290 launches and 19.1 ms per step with every kernel from cotnet_amd/csrc.
 """
 import ctypes
-import functools
-import threading
 import os
 import weakref
 
@@ -30,46 +28,10 @@ from torch import nn
 from torch.autograd import Function
 
 from . import _lib, grad_sink
+from ._lib import one_stream_query as _one_stream_query, ptr as _p, stream as _stream
 
 ENABLED = os.environ.get("COT_FUSED_LAYER", "1") != "0"  # default on; COT_FUSED_LAYER=0 = one autograd node per op
-_DEVICE_ONLY = True  # tests drive the node on CPU tensors through the host-emulated kernels
 BF16 = _lib.COT_BF16
-
-
-def _p(t):
-    # a plain int is accepted for a c_void_p parameter and skips building a ctypes object per argument (~1000 per step)
-    return t.data_ptr() if t is not None else None
-
-
-_TLS = threading.local()  # .st: the compute stream's handle for the node invocation running on this thread
-
-
-def _stream():
-    if not _DEVICE_ONLY:
-        return None
-    st = getattr(_TLS, "st", None)
-    return st if st is not None else ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _one_stream_query(fn):
-    """torch.cuda.current_stream() costs ~9 us and a node makes ~100 launches: ask once per forward / backward of a node (the
-    current stream cannot change inside one; forward and backward run on different threads, hence thread-local).  Measured:
-    1.3 ms of a step's ~12 ms of host time (gpurun_out/r3_cpu_profile.log)"""
-    @functools.wraps(fn)
-    def wrapped(*a, **k):
-        if not _DEVICE_ONLY or getattr(_TLS, "st", None) is not None:
-            return fn(*a, **k)
-        _TLS.st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        try:
-            return fn(*a, **k)
-        finally:
-            _TLS.st = None
-    return wrapped
-
-
-def _ck(rc, what):
-    if rc:
-        _lib.check(rc, what)
 
 
 # ---- weight gradients on a side stream.  A parameter gradient is needed only when the step's backward is over, while the
@@ -120,7 +82,7 @@ class _Side:
     __slots__ = ("on", "main", "stream", "st", "ws", "keep", "lazy", "queue", "dev", "fresh0", "params")
 
     def __init__(self, dev, ws_bytes, main_ws, params=()):
-        self.on = SIDE_WGRAD and _DEVICE_ONLY and dev.type == "cuda"
+        self.on = SIDE_WGRAD and _lib.DEVICE_ONLY and dev.type == "cuda"
         self.lazy = self.on and LAZY_WGRAD
         self.keep, self.queue, self.dev = [], [], dev
         self.fresh0, self.params = grad_sink.fresh_count(), params
@@ -237,32 +199,33 @@ def _agg_fwd_stats(L, v, w_or_logits, a, gn, gn_mean, gn_rstd, geom, bn, stats, 
     key = (geom.N, geom.C, H, W, geom.wC, gn is not None)
     if AGG_ROWSTATS and _ROWSTATS_OK.get(key, True):
         rows = torch.empty(int(L.cot_agg_rowstats_floats(N, C, H)), dtype=torch.float32, device=a.device)
-        rc = L.cot_agg_forward_rowstats(_p(v), _p(w_or_logits), _p(a), _p(rows), _p(gn_mean) if gn is not None else None,
-                                        _p(gn_rstd) if gn is not None else None, _p(gn.weight) if gn is not None else None,
-                                        _p(gn.bias) if gn is not None else None, gn.num_groups if gn is not None else 0,
-                                        ctypes.byref(geom), BF16, st)
-        if rc == 0:
-            _ck(L.cot_bn_rowstats_finalize(_p(rows), _p(stats), _p(stats[C:]), _p(bn.running_mean), _p(bn.running_var),
-                                           _p(bn.num_batches_tracked), N, C, H, W, float(bn.eps), float(bn.momentum), st),
-                "cot_bn_rowstats_finalize")
+        try:
+            L.cot_agg_forward_rowstats(_p(v), _p(w_or_logits), _p(a), _p(rows), _p(gn_mean) if gn is not None else None,
+                                       _p(gn_rstd) if gn is not None else None, _p(gn.weight) if gn is not None else None,
+                                       _p(gn.bias) if gn is not None else None, gn.num_groups if gn is not None else 0,
+                                       ctypes.byref(geom), BF16, st)
+        except _lib.CotError as e:
+            if e.status != _lib.COT_ERR_UNSUPPORTED:
+                raise
+        else:
+            L.cot_bn_rowstats_finalize(_p(rows), _p(stats), _p(stats[C:]), _p(bn.running_mean), _p(bn.running_var),
+                                       _p(bn.num_batches_tracked), N, C, H, W, float(bn.eps), float(bn.momentum), st)
             return True
-        if rc != _lib.COT_ERR_UNSUPPORTED:
-            _ck(rc, "cot_agg_forward_rowstats")
         _ROWSTATS_OK[key] = False  # (geometry off the LDS forward kernel: the plain forward + a statistics pass, from now on without asking)
     if gn is not None:
-        _ck(L.cot_agg_gn9_forward(_p(v), _p(w_or_logits), _p(gn_mean), _p(gn_rstd), _p(gn.weight), _p(gn.bias), gn.num_groups, _p(a),
-                                  ctypes.byref(geom), BF16, st), "cot_agg_gn9_forward")
+        L.cot_agg_gn9_forward(_p(v), _p(w_or_logits), _p(gn_mean), _p(gn_rstd), _p(gn.weight), _p(gn.bias), gn.num_groups, _p(a),
+                              ctypes.byref(geom), BF16, st)
     else:
-        _ck(L.cot_agg_forward(_p(v), _p(w_or_logits), _p(a), ctypes.byref(geom), BF16, _lib.COT_NCHW, st), "cot_agg_forward")
-    _ck(L.cot_bn_stats_sums(_p(a), _p(stats[2 * C:]), N, C, H * W, BF16, st), "cot_bn_stats_sums")
+        L.cot_agg_forward(_p(v), _p(w_or_logits), _p(a), ctypes.byref(geom), BF16, _lib.COT_NCHW, st)
+    L.cot_bn_stats_sums(_p(a), _p(stats[2 * C:]), N, C, H * W, BF16, st)
     return False
 
 
 def _tail_gap(L, a, k, gapT, bn, stats, final, N, C, HW, lay):
     """gapT = mean_hw(silu(bn(a)) + k); final False: stats[2C:] holds cot_bn_stats_sums' chunk sums and this launch finalizes them"""
-    _ck(L.cot_radix_gap_t_bn(_p(a), _p(k), _p(gapT), _p(bn.weight), _p(bn.bias), _p(stats), _p(stats[C:]), _p(bn.running_mean),
-                             _p(bn.running_var), _p(bn.num_batches_tracked), None if final else _p(stats[2 * C:]), N, C, HW, float(bn.eps),
-                             float(bn.momentum), lay, BF16, _stream()), "cot_radix_gap_t_bn")
+    L.cot_radix_gap_t_bn(_p(a), _p(k), _p(gapT), _p(bn.weight), _p(bn.bias), _p(stats), _p(stats[C:]), _p(bn.running_mean),
+                         _p(bn.running_var), _p(bn.num_batches_tracked), None if final else _p(stats[2 * C:]), N, C, HW, float(bn.eps),
+                         float(bn.momentum), lay, BF16, _stream())
 
 _SIZES = _lib.register_cache({})  # (N, C, H, W, A) -> (workspace bytes, bn workspace floats for C, C/2 and the se branch's A channels)
 _MASKS = {}
@@ -292,7 +255,7 @@ def _masks(L, H, W, device):
     m = _MASKS.get(k)
     if m is None:
         m = torch.empty(int(L.cot_conv3x3g_masks_bytes(H, W)), dtype=torch.uint8, device=device)
-        _ck(L.cot_conv3x3g_masks(_p(m), H, W, _stream()), "cot_conv3x3g_masks")
+        L.cot_conv3x3g_masks(_p(m), H, W, _stream())
         _MASKS[k] = m
     return m
 
@@ -315,13 +278,13 @@ _PACK_EVENT = {}                       # device index -> event the compute strea
 
 
 def _capturing():
-    return _DEVICE_ONLY and torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
+    return _lib.DEVICE_ONLY and torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
 
 
 def _pack_for(L, conv, mode, N, C, G, H, W):
     """-> the valid packing of conv.weight for this call, or None (the caller then packs inline through the ordinary entry point).
     Also remembers the geometry for after_optimizer_step."""
-    if not (PREPACK and _DEVICE_ONLY):
+    if not (PREPACK and _lib.DEVICE_ONLY):
         return None
     e = _PACKS.get(conv)
     if e is None:
@@ -356,12 +319,12 @@ def after_optimizer_step(device):
     """called by FlatSGD.step() once its kernels are issued: the parameters have changed (PARAM_EPOCH), and the 3x3 weights of the
     layers the last forward ran are packed for the next step on the side stream"""
     PARAM_EPOCH[0] += 1
-    if not (PREPACK and ENABLED and SIDE_WGRAD and _DEVICE_ONLY and device.type == "cuda") or _capturing():
+    if not (PREPACK and ENABLED and SIDE_WGRAD and _lib.DEVICE_ONLY and device.type == "cuda") or _capturing():
         return
     ent = _SIDE_STREAMS.get(device.index)
     if ent is None or not _PACKS:
         return
-    L = _lib.lib()
+    L = _lib.lib()  # (the raw handle: a status other than COT_OK is an answer here, not an error)
     side, cur = ent[0], torch.cuda.current_stream(device)
     side.wait_stream(cur)  # behind the SGD kernels (and with them behind the whole backward pass that read the old packings)
     st = ctypes.c_void_p(side.cuda_stream)
@@ -426,28 +389,25 @@ def _conv3x3_ws_groups(C, G):
 def _conv3x3_fwd(L, conv, x, y, masks, ws, N, C, G, H, W):
     if _merge12(C, G):
         wm = _merged_weight(conv, C, G, True)
-        _ck(L.cot_conv3x3g_forward(_p(x), _p(wm), _p(y), _p(masks), _p(ws), N, C, C, G // 2, H, W, BF16, _stream()), "cot_conv3x3g_forward")
+        L.cot_conv3x3g_forward(_p(x), _p(wm), _p(y), _p(masks), _p(ws), N, C, C, G // 2, H, W, BF16, _stream())
         return
     pk = _pack_for(L, conv, 0, N, C, G, H, W)
     if pk is not None:
-        _ck(L.cot_conv3x3g_forward_packed(_p(x), _p(pk), _p(y), N, C, C, G, H, W, BF16, _stream()), "cot_conv3x3g_forward_packed")
+        L.cot_conv3x3g_forward_packed(_p(x), _p(pk), _p(y), N, C, C, G, H, W, BF16, _stream())
     else:
-        _ck(L.cot_conv3x3g_forward(_p(x), _p(conv.weight), _p(y), _p(masks), _p(ws), N, C, C, G, H, W, BF16, _stream()), "cot_conv3x3g_forward")
+        L.cot_conv3x3g_forward(_p(x), _p(conv.weight), _p(y), _p(masks), _p(ws), N, C, C, G, H, W, BF16, _stream())
 
 
 def _conv3x3_dgrad(L, conv, gy, gx, accumulate, masks, ws, N, C, G, H, W):
     if _merge12(C, G):
         wm = _merged_weight(conv, C, G, False)
-        _ck(L.cot_conv3x3g_backward_data(_p(gy), _p(wm), _p(gx), accumulate, _p(masks), _p(ws), N, C, C, G // 2, H, W, BF16, _stream()),
-            "cot_conv3x3g_backward_data")
+        L.cot_conv3x3g_backward_data(_p(gy), _p(wm), _p(gx), accumulate, _p(masks), _p(ws), N, C, C, G // 2, H, W, BF16, _stream())
         return
     pk = _pack_for(L, conv, 1, N, C, G, H, W)
     if pk is not None:
-        _ck(L.cot_conv3x3g_backward_data_packed(_p(gy), _p(pk), _p(gx), accumulate, N, C, C, G, H, W, BF16, _stream()),
-            "cot_conv3x3g_backward_data_packed")
+        L.cot_conv3x3g_backward_data_packed(_p(gy), _p(pk), _p(gx), accumulate, N, C, C, G, H, W, BF16, _stream())
     else:
-        _ck(L.cot_conv3x3g_backward_data(_p(gy), _p(conv.weight), _p(gx), accumulate, _p(masks), _p(ws), N, C, C, G, H, W, BF16, _stream()),
-            "cot_conv3x3g_backward_data")
+        L.cot_conv3x3g_backward_data(_p(gy), _p(conv.weight), _p(gx), accumulate, _p(masks), _p(ws), N, C, C, G, H, W, BF16, _stream())
 
 
 class _Plan:
@@ -548,20 +508,18 @@ def _bn_fwd(L, x, y, bn, stats, nws_off, N, C, HW, act, residual=None, ps=None, 
     """stats: fp32 [2*C + workspace] -> mean = stats[:C], rstd = stats[C:2C].  ps: per-sample scale of the normalised branch
     (stochastic depth: 0 or 1 / keep, fp32 [N]) or None.  mask: `_relu_mask` tensor to fill (act = ReLU with a residual)"""
     if mask is not None:
-        _ck(L.cot_bn_act_forward_mask(_p(x), _p(residual), _p(y), _p(mask), _p(bn.weight), _p(bn.bias), _p(stats), _p(stats[C:]),
-                                      _p(bn.running_mean), _p(bn.running_var), _p(bn.num_batches_tracked), _p(stats[nws_off:]),
-                                      _p(ps), N, C, HW, float(bn.eps), float(bn.momentum), act, BF16, _stream()),
-            "cot_bn_act_forward_mask")
+        L.cot_bn_act_forward_mask(_p(x), _p(residual), _p(y), _p(mask), _p(bn.weight), _p(bn.bias), _p(stats), _p(stats[C:]),
+                                  _p(bn.running_mean), _p(bn.running_var), _p(bn.num_batches_tracked), _p(stats[nws_off:]),
+                                  _p(ps), N, C, HW, float(bn.eps), float(bn.momentum), act, BF16, _stream())
         return
     if ps is not None:
-        _ck(L.cot_bn_act_forward_ps(_p(x), _p(residual), _p(y), _p(bn.weight), _p(bn.bias), _p(stats), _p(stats[C:]),
-                                    _p(bn.running_mean), _p(bn.running_var), _p(bn.num_batches_tracked), _p(stats[nws_off:]),
-                                    _p(ps), N, C, HW, float(bn.eps), float(bn.momentum), act, BF16, _stream()),
-            "cot_bn_act_forward_ps")
+        L.cot_bn_act_forward_ps(_p(x), _p(residual), _p(y), _p(bn.weight), _p(bn.bias), _p(stats), _p(stats[C:]),
+                                _p(bn.running_mean), _p(bn.running_var), _p(bn.num_batches_tracked), _p(stats[nws_off:]),
+                                _p(ps), N, C, HW, float(bn.eps), float(bn.momentum), act, BF16, _stream())
         return
-    _ck(L.cot_bn_act_forward(_p(x), _p(residual), _p(y), _p(bn.weight), _p(bn.bias), _p(stats), _p(stats[C:]),
-                             _p(bn.running_mean), _p(bn.running_var), _p(bn.num_batches_tracked), _p(stats[nws_off:]),
-                             N, C, HW, float(bn.eps), float(bn.momentum), act, BF16, _stream()), "cot_bn_act_forward")
+    L.cot_bn_act_forward(_p(x), _p(residual), _p(y), _p(bn.weight), _p(bn.bias), _p(stats), _p(stats[C:]),
+                         _p(bn.running_mean), _p(bn.running_var), _p(bn.num_batches_tracked), _p(stats[nws_off:]),
+                         N, C, HW, float(bn.eps), float(bn.momentum), act, BF16, _stream())
 
 
 # BatchNorm statistics out of the producing 1x1 convolution's epilogue (SURVEY 7.6 / DESIGN 4.9c; opt-in COT_BN_EPILOGUE=1): on
@@ -586,15 +544,13 @@ def _conv_bn_fwd(L, x1, x2, c1, conv, y_pre, y, bn, stats, nws_off, N, Ci, Co, H
     bias = conv.bias
     if BN_EPILOGUE and ps is None and _epi_ok(L, Ci, c1, x2 is not None, HW):
         part = torch.empty(int(L.cot_gn9_stats_floats(N, Co, HW)), dtype=torch.float32, device=y.device)
-        _ck(L.cot_conv1x1_forward_stats(_p(x1), _p(x2), c1, _p(conv.weight), _p(bias), _p(y_pre), _p(part), N, Ci, Co, HW, BF16, st),
-            "cot_conv1x1_forward_stats")
-        _ck(L.cot_bn_tile_stats_finalize(_p(part), _p(stats), _p(stats[Co:]), _p(bn.running_mean), _p(bn.running_var),
-                                         _p(bn.num_batches_tracked), N, Co, HW, float(bn.eps), float(bn.momentum), st),
-            "cot_bn_tile_stats_finalize")
-        _ck(L.cot_bn_act_apply_forward(_p(y_pre), _p(residual), _p(y), _p(mask), _p(bn.weight), _p(bn.bias), _p(stats), _p(stats[Co:]),
-                                       N, Co, HW, act, BF16, st), "cot_bn_act_apply_forward")
+        L.cot_conv1x1_forward_stats(_p(x1), _p(x2), c1, _p(conv.weight), _p(bias), _p(y_pre), _p(part), N, Ci, Co, HW, BF16, st)
+        L.cot_bn_tile_stats_finalize(_p(part), _p(stats), _p(stats[Co:]), _p(bn.running_mean), _p(bn.running_var),
+                                     _p(bn.num_batches_tracked), N, Co, HW, float(bn.eps), float(bn.momentum), st)
+        L.cot_bn_act_apply_forward(_p(y_pre), _p(residual), _p(y), _p(mask), _p(bn.weight), _p(bn.bias), _p(stats), _p(stats[Co:]),
+                                   N, Co, HW, act, BF16, st)
         return
-    _ck(L.cot_conv1x1_forward(_p(x1), _p(x2), c1, _p(conv.weight), _p(bias), _p(y_pre), N, Ci, Co, HW, BF16, st), "cot_conv1x1_forward")
+    L.cot_conv1x1_forward(_p(x1), _p(x2), c1, _p(conv.weight), _p(bias), _p(y_pre), N, Ci, Co, HW, BF16, st)
     _bn_fwd(L, y_pre, y, bn, stats, nws_off, N, Co, HW, act, residual=residual, ps=ps, mask=mask)
 
 
@@ -604,18 +560,15 @@ def _bn_bwd(L, dy, x, y, dx, bn, stats, N, C, HW, act, nws, dres=None, ps=None, 
     dg, db = grad_sink.out_like(bn.weight), grad_sink.out_like(bn.bias)
     ws = torch.empty(max(nws, 1), dtype=torch.float32, device=dy.device)
     if mask is not None:
-        _ck(L.cot_bn_act_backward_mask(_p(dy), _p(x), _p(mask), _p(dx), _p(dres), _p(bn.weight), _p(bn.bias), _p(stats),
-                                       _p(stats[C:]), _p(dg), _p(db), _p(ws), _p(ps), N, C, HW, act, BF16, _stream()),
-            "cot_bn_act_backward_mask")
+        L.cot_bn_act_backward_mask(_p(dy), _p(x), _p(mask), _p(dx), _p(dres), _p(bn.weight), _p(bn.bias), _p(stats),
+                                   _p(stats[C:]), _p(dg), _p(db), _p(ws), _p(ps), N, C, HW, act, BF16, _stream())
         return dg, db
     if ps is not None:
-        _ck(L.cot_bn_act_backward_ps(_p(dy), _p(x), _p(y), _p(dx), _p(dres), _p(bn.weight), _p(bn.bias), _p(stats),
-                                     _p(stats[C:]), _p(dg), _p(db), _p(ws), _p(ps), N, C, HW, act, BF16, _stream()),
-            "cot_bn_act_backward_ps")
+        L.cot_bn_act_backward_ps(_p(dy), _p(x), _p(y), _p(dx), _p(dres), _p(bn.weight), _p(bn.bias), _p(stats),
+                                 _p(stats[C:]), _p(dg), _p(db), _p(ws), _p(ps), N, C, HW, act, BF16, _stream())
         return dg, db
-    _ck(L.cot_bn_act_backward(_p(dy), _p(x), _p(y), _p(dx), _p(dres), _p(bn.weight), _p(bn.bias), _p(stats), _p(stats[C:]),
-                              _p(dg), _p(db), _p(ws), N, C, HW, act, BF16, _stream()),
-        "cot_bn_act_backward")
+    L.cot_bn_act_backward(_p(dy), _p(x), _p(y), _p(dx), _p(dres), _p(bn.weight), _p(bn.bias), _p(stats), _p(stats[C:]),
+                          _p(dg), _p(db), _p(ws), N, C, HW, act, BF16, _stream())
     return dg, db
 
 
@@ -684,7 +637,7 @@ def _cot_forward(L, layer, x):
     qk = None
     if GX:  # CoXtLayer: [x0, k0, x1, k1, ...] so that each of the two groups sees matching halves of x and k (ref :153-154)
         qk = torch.stack([x, k], dim=2).view(N, 2 * C, H, W)
-        _ck(L.cot_conv1x1g_forward(_p(qk), _p(pl.em0.weight), None, _p(e0), N, 2 * C, Ch, 2, HW, BF16, st), "cot_conv1x1g_forward")
+        L.cot_conv1x1g_forward(_p(qk), _p(pl.em0.weight), None, _p(e0), N, 2 * C, Ch, 2, HW, BF16, st)
     s_e = stat(Ch, nws_h)
     if GX:
         _bn_fwd(L, e0, e1, pl.em1, s_e, 2 * Ch, N, Ch, HW, 1)
@@ -696,32 +649,29 @@ def _cot_forward(L, layer, x):
     # aggregation's prologue -- the normalised tensor `w` is never materialised (stages with planes of more than 256 pixels)
     fused_gn = GN_FUSED and not GX and _gn_fused_ok(L, Ch, HW, W)
     if GX:
-        _ck(L.cot_conv1x1g_forward(_p(e1), _p(pl.em3.weight), _p(pl.em3.bias), _p(e3), N, Ch, Ce, 2, HW, BF16, st),
-            "cot_conv1x1g_forward")
+        L.cot_conv1x1g_forward(_p(e1), _p(pl.em3.weight), _p(pl.em3.bias), _p(e3), N, Ch, Ce, 2, HW, BF16, st)
     elif fused_gn:
         part = torch.empty(int(L.cot_gn9_stats_floats(N, Ce, HW)), dtype=torch.float32, device=dev)
-        _ck(L.cot_conv1x1_forward_gn9(_p(e1), None, Ch, _p(pl.em3.weight), _p(pl.em3.bias), _p(e3), _p(part), N, Ch, Ce, HW, BF16, st),
-            "cot_conv1x1_forward_gn9")
+        L.cot_conv1x1_forward_gn9(_p(e1), None, Ch, _p(pl.em3.weight), _p(pl.em3.bias), _p(e3), _p(part), N, Ch, Ce, HW, BF16, st)
     else:
-        _ck(L.cot_conv1x1_forward(_p(e1), None, Ch, _p(pl.em3.weight), _p(pl.em3.bias), _p(e3), N, Ch, Ce, HW, BF16, st),
-            "cot_conv1x1_forward")
+        L.cot_conv1x1_forward(_p(e1), None, Ch, _p(pl.em3.weight), _p(pl.em3.bias), _p(e3), N, Ch, Ce, HW, BF16, st)
     if fused_gn:
         w = None
         gn_mean = torch.empty(2 * N * gn.num_groups, dtype=torch.float32, device=dev)
         gn_rstd = gn_mean[N * gn.num_groups:]
-        _ck(L.cot_gn9_stats_finalize(_p(part), _p(gn_mean), _p(gn_rstd), N, Ce, HW, float(gn.eps), st), "cot_gn9_stats_finalize")
+        L.cot_gn9_stats_finalize(_p(part), _p(gn_mean), _p(gn_rstd), N, Ce, HW, float(gn.eps), st)
     elif HW <= 8192:  # one (image, group) fits a workgroup's registers: 1 read + 1 write (csrc/group_norm9.hip)
         w = new(Ce)
         gn_mean = torch.empty(2 * N * gn.num_groups, dtype=torch.float32, device=dev)
         gn_rstd = gn_mean[N * gn.num_groups:]
-        _ck(L.cot_group_norm9_forward(_p(e3), _p(gn.weight), _p(gn.bias), _p(w), _p(gn_mean), _p(gn_rstd), N, Ce, HW,
-                                      float(gn.eps), BF16, st), "cot_group_norm9_forward")
+        L.cot_group_norm9_forward(_p(e3), _p(gn.weight), _p(gn.bias), _p(w), _p(gn_mean), _p(gn_rstd), N, Ce, HW,
+                                  float(gn.eps), BF16, st)
     else:
         w, gn_mean, gn_rstd = torch.native_group_norm(e3, gn.weight, gn.bias, N, Ce, HW, gn.num_groups, gn.eps)
     # values                                                                                     (ref :87)
     v_pre, v = new(C), new(C)
     if GX:
-        _ck(L.cot_conv1x1g_forward(_p(x), _p(pl.cv0.weight), None, _p(v_pre), N, C, C, 2, HW, BF16, st), "cot_conv1x1g_forward")
+        L.cot_conv1x1g_forward(_p(x), _p(pl.cv0.weight), None, _p(v_pre), N, C, C, 2, HW, BF16, st)
     s_v = stat(C, nws_c)
     if GX:
         _bn_fwd(L, v_pre, v, pl.cv1, s_v, 2 * C, N, C, HW, 0)
@@ -738,10 +688,10 @@ def _cot_forward(L, layer, x):
         y_final = _agg_fwd_stats(L, v, e3 if fused_gn else w, a, gn if fused_gn else None, gn_mean, gn_rstd, geom, bnl, s_y, N, C, H, W)
     else:
         if fused_gn:
-            _ck(L.cot_agg_gn9_forward(_p(v), _p(e3), _p(gn_mean), _p(gn_rstd), _p(gn.weight), _p(gn.bias), gn.num_groups, _p(a),
-                                      ctypes.byref(geom), BF16, st), "cot_agg_gn9_forward")
+            L.cot_agg_gn9_forward(_p(v), _p(e3), _p(gn_mean), _p(gn_rstd), _p(gn.weight), _p(gn.bias), gn.num_groups, _p(a),
+                                  ctypes.byref(geom), BF16, st)
         else:
-            _ck(L.cot_agg_forward(_p(v), _p(w), _p(a), ctypes.byref(geom), BF16, _lib.COT_NCHW, st), "cot_agg_forward")
+            L.cot_agg_forward(_p(v), _p(w), _p(a), ctypes.byref(geom), BF16, _lib.COT_NCHW, st)
         _bn_fwd(L, a, y, bnl, s_y, 2 * C, N, C, HW, 2)
     # radix-2 split attention                                                                    (ref :92-104)
     # descriptors are kept channel-major ([C][N]) so that the se branch runs on the 1x1-convolution / BatchNorm
@@ -751,21 +701,19 @@ def _cot_forward(L, layer, x):
     if BN_TAIL:
         _tail_gap(L, a, k, gapT, bnl, s_y, y_final, N, C, HW, 0)
     else:
-        _ck(L.cot_radix_gap_t(_p(y), _p(k), _p(gapT), N, C, HW, BF16, st), "cot_radix_gap_t")
-    _ck(L.cot_conv1x1_forward(_p(gapT), None, C, _p(pl.se0.weight), _p(pl.se0.bias), _p(hpre), 1, C, A, N, BF16, st),
-        "cot_conv1x1_forward")
+        L.cot_radix_gap_t(_p(y), _p(k), _p(gapT), N, C, HW, BF16, st)
+    L.cot_conv1x1_forward(_p(gapT), None, C, _p(pl.se0.weight), _p(pl.se0.bias), _p(hpre), 1, C, A, N, BF16, st)
     s_a = stat(A, nws_a)
     _bn_fwd(L, hpre, h, pl.sebn, s_a, 2 * A, 1, A, N, 1)
-    _ck(L.cot_conv1x1_forward(_p(h), None, A, _p(pl.se3.weight), _p(pl.se3.bias), _p(logitsT), 1, A, 2 * C, N, BF16,
-                              st), "cot_conv1x1_forward")
+    L.cot_conv1x1_forward(_p(h), None, A, _p(pl.se3.weight), _p(pl.se3.bias), _p(logitsT), 1, A, 2 * C, N, BF16,
+                          st)
     attn = torch.empty((N, C, 2), dtype=x.dtype, device=dev)
     out = new(C)
     if BN_TAIL:
-        _ck(L.cot_radix_mix_logits_bn(_p(a), _p(k), _p(logitsT), _p(out), _p(attn), _p(bnl.weight), _p(bnl.bias), _p(s_y), _p(s_y[C:]),
-                                      N, C, HW, 0, BF16, st), "cot_radix_mix_logits_bn")
+        L.cot_radix_mix_logits_bn(_p(a), _p(k), _p(logitsT), _p(out), _p(attn), _p(bnl.weight), _p(bnl.bias), _p(s_y), _p(s_y[C:]),
+                                  N, C, HW, 0, BF16, st)
     else:
-        _ck(L.cot_radix_mix_logits(_p(y), _p(k), _p(logitsT), _p(out), _p(attn), N, C, HW, BF16, st),
-            "cot_radix_mix_logits")
+        L.cot_radix_mix_logits(_p(y), _p(k), _p(logitsT), _p(out), _p(attn), N, C, HW, BF16, st)
 
     return out, (x, k_pre, k, e0, e1, e3, w, gn_mean, gn_rstd, v_pre, v, a, y, attn, s_k, s_e, s_v, s_y, gapT, hpre, h,
                  s_a, qk), geom
@@ -802,62 +750,55 @@ def _cot_backward(L, layer, saved, geom, gout, side=None):
     bnl = pl.bn
     if y is None:  # (the forward folded bn + swish into the tail: so does the backward)
         tsum = torch.empty(N * C * 4, dtype=torch.float32, device=dev)
-        _ck(L.cot_radix_mix_backward_reduce_bn(_p(gout), _p(a), _p(k), _p(attn), _p(glogT), _p(tsum), _p(bnl.weight), _p(bnl.bias),
-                                               _p(s_y), _p(s_y[C:]), N, C, HW, 0, BF16, st), "cot_radix_mix_backward_reduce_bn")
+        L.cot_radix_mix_backward_reduce_bn(_p(gout), _p(a), _p(k), _p(attn), _p(glogT), _p(tsum), _p(bnl.weight), _p(bnl.bias),
+                                           _p(s_y), _p(s_y[C:]), N, C, HW, 0, BF16, st)
     else:
-        _ck(L.cot_radix_mix_backward_reduce(_p(gout), _p(y), _p(k), _p(attn), _p(glogT), N, C, HW, BF16, st),
-            "cot_radix_mix_backward_reduce")
-    _ck(L.cot_conv1x1_backward_data(_p(glogT), _p(se3.weight), _p(gh), None, A, 0, _p(ws), 1, A, 2 * C, N, BF16, st),
-        "cot_conv1x1_backward_data")
+        L.cot_radix_mix_backward_reduce(_p(gout), _p(y), _p(k), _p(attn), _p(glogT), N, C, HW, BF16, st)
+    L.cot_conv1x1_backward_data(_p(glogT), _p(se3.weight), _p(gh), None, A, 0, _p(ws), 1, A, 2 * C, N, BF16, st)
     g_w3, g_b3 = grad_sink.out_like(se3.weight), grad_sink.out_like(se3.bias)
-    side.run(lambda st_, a_=(_p(glogT), _p(h), None, A, _p(g_w3), _p(g_b3), _p(side.ws), 1, A, 2 * C, N, BF16): _ck(L.cot_conv1x1_backward_weight(*a_, st_), "cot_conv1x1_backward_weight"), glogT, h)
+    side.run(lambda st_, a_=(_p(glogT), _p(h), None, A, _p(g_w3), _p(g_b3), _p(side.ws), 1, A, 2 * C, N, BF16): L.cot_conv1x1_backward_weight(*a_, st_), glogT, h)
     ghpre = row(A)
     d_sa_w, d_sa_b = _bn_bwd(L, gh, hpre, None, ghpre, sebn, s_a, 1, A, N, 1, nws_a)
-    _ck(L.cot_conv1x1_backward_data(_p(ghpre), _p(se0.weight), _p(ggapT), None, C, 0, _p(ws), 1, C, A, N, BF16, st),
-        "cot_conv1x1_backward_data")
+    L.cot_conv1x1_backward_data(_p(ghpre), _p(se0.weight), _p(ggapT), None, C, 0, _p(ws), 1, C, A, N, BF16, st)
     g_w0, g_b0 = grad_sink.out_like(se0.weight), grad_sink.out_like(se0.bias)
-    side.run(lambda st_, a_=(_p(ghpre), _p(gapT), None, C, _p(g_w0), _p(g_b0), _p(side.ws), 1, C, A, N, BF16): _ck(L.cot_conv1x1_backward_weight(*a_, st_), "cot_conv1x1_backward_weight"), ghpre, gapT)
+    side.run(lambda st_, a_=(_p(ghpre), _p(gapT), None, C, _p(g_w0), _p(g_b0), _p(side.ws), 1, C, A, N, BF16): L.cot_conv1x1_backward_weight(*a_, st_), ghpre, gapT)
     # bn + swish, aggregation
     ga, gk = torch.empty_like(a), torch.empty_like(k)
     if y is None:
         d_bn_w, d_bn_b = grad_sink.out_like(bnl.weight), grad_sink.out_like(bnl.bias)
-        _ck(L.cot_radix_mix_backward_apply_bn(_p(gout), _p(a), _p(attn), _p(ggapT), _p(tsum), _p(ga), _p(gk), _p(bnl.weight), _p(bnl.bias),
-                                              _p(s_y), _p(s_y[C:]), _p(d_bn_w), _p(d_bn_b), N, C, HW, 0, BF16, st),
-            "cot_radix_mix_backward_apply_bn")
+        L.cot_radix_mix_backward_apply_bn(_p(gout), _p(a), _p(attn), _p(ggapT), _p(tsum), _p(ga), _p(gk), _p(bnl.weight), _p(bnl.bias),
+                                          _p(s_y), _p(s_y[C:]), _p(d_bn_w), _p(d_bn_b), N, C, HW, 0, BF16, st)
     else:
         gy = torch.empty_like(y)
-        _ck(L.cot_radix_mix_backward_apply(_p(gout), _p(attn), _p(ggapT), _p(gy), _p(gk), N, C, HW, BF16, st),
-            "cot_radix_mix_backward_apply")
+        L.cot_radix_mix_backward_apply(_p(gout), _p(attn), _p(ggapT), _p(gy), _p(gk), N, C, HW, BF16, st)
         d_bn_w, d_bn_b = _bn_bwd(L, gy, a, None, ga, bnl, s_y, N, C, HW, 2, nws_c)
     gv, gw = torch.empty_like(v), torch.empty_like(e3)
     if w is None:  # (the forward normalised the logits inside the aggregation: so does the backward; gw = d / d normalised weights)
         gn_ = pl.gn
-        _ck(L.cot_agg_gn9_backward(_p(ga), _p(v), _p(e3), _p(gn_mean), _p(gn_rstd), _p(gn_.weight), _p(gn_.bias), gn_.num_groups,
-                                   _p(gv), _p(gw), ctypes.byref(geom), BF16, st), "cot_agg_gn9_backward")
+        L.cot_agg_gn9_backward(_p(ga), _p(v), _p(e3), _p(gn_mean), _p(gn_rstd), _p(gn_.weight), _p(gn_.bias), gn_.num_groups,
+                               _p(gv), _p(gw), ctypes.byref(geom), BF16, st)
     else:
-        _ck(L.cot_agg_backward(_p(ga), _p(v), _p(w), _p(gv), _p(gw), ctypes.byref(geom), BF16, _lib.COT_NCHW, st),
-            "cot_agg_backward")
+        L.cot_agg_backward(_p(ga), _p(v), _p(w), _p(gv), _p(gw), ctypes.byref(geom), BF16, _lib.COT_NCHW, st)
     # values branch: bn, conv1x1 -> first contribution to dx
     gv_pre = ga  # (reuse: ga is dead)
     d_cv_w, d_cv_b = _bn_bwd(L, gv, v_pre, None, gv_pre, cv1, s_v, N, C, HW, 0, nws_c)
     gx = torch.empty_like(x)
     g_wv = grad_sink.out_like(cv0.weight)
     if GX:
-        _ck(L.cot_conv1x1g_backward_data(_p(gv_pre), _p(cv0.weight), _p(gx), 0, N, C, C, 2, HW, BF16, st), "cot_conv1x1g_backward_data")
-        side.run(lambda st_, a_=(_p(gv_pre), _p(x), _p(g_wv), None, _p(side.ws), N, C, C, 2, HW, BF16): _ck(L.cot_conv1x1g_backward_weight(*a_, st_), "cot_conv1x1g_backward_weight"), gv_pre, x)
+        L.cot_conv1x1g_backward_data(_p(gv_pre), _p(cv0.weight), _p(gx), 0, N, C, C, 2, HW, BF16, st)
+        side.run(lambda st_, a_=(_p(gv_pre), _p(x), _p(g_wv), None, _p(side.ws), N, C, C, 2, HW, BF16): L.cot_conv1x1g_backward_weight(*a_, st_), gv_pre, x)
     else:
-        _ck(L.cot_conv1x1_backward_data(_p(gv_pre), _p(cv0.weight), _p(gx), None, C, 0, _p(ws), N, C, C, HW, BF16, st),
-            "cot_conv1x1_backward_data")
-        side.run(lambda st_, a_=(_p(gv_pre), _p(x), None, C, _p(g_wv), None, _p(side.ws), N, C, C, HW, BF16): _ck(L.cot_conv1x1_backward_weight(*a_, st_), "cot_conv1x1_backward_weight"), gv_pre, x)
+        L.cot_conv1x1_backward_data(_p(gv_pre), _p(cv0.weight), _p(gx), None, C, 0, _p(ws), N, C, C, HW, BF16, st)
+        side.run(lambda st_, a_=(_p(gv_pre), _p(x), None, C, _p(g_wv), None, _p(side.ws), N, C, C, HW, BF16): L.cot_conv1x1_backward_weight(*a_, st_), gv_pre, x)
     # logits branch: GroupNorm, conv1x1(+bias), bn+relu, conv1x1 on [x | k] -> dx +=, dk +=
     gn = pl.gn
     if HW <= 8192:
         ge3, g_gn_w, g_gn_b = torch.empty_like(e3), grad_sink.out_like(gn.weight), grad_sink.out_like(gn.bias)
         gn_ws = torch.empty(2 * N * Ce, dtype=torch.float32, device=dev)
         # (dx here; dgamma / dbeta -- a launch of their own -- beside the weight gradients)
-        _ck(L.cot_group_norm9_backward(_p(gw), _p(e3), _p(gn_mean), _p(gn_rstd), _p(gn.weight), _p(ge3), None, None, _p(gn_ws), N, Ce, HW,
-                                       BF16, st), "cot_group_norm9_backward")
-        side.run(lambda st_, a_=(_p(gn_ws), _p(g_gn_w), _p(g_gn_b), N, Ce, BF16): _ck(L.cot_group_norm9_backward_params(*a_, st_), "cot_group_norm9_backward_params"), gn_ws)
+        L.cot_group_norm9_backward(_p(gw), _p(e3), _p(gn_mean), _p(gn_rstd), _p(gn.weight), _p(ge3), None, None, _p(gn_ws), N, Ce, HW,
+                                   BF16, st)
+        side.run(lambda st_, a_=(_p(gn_ws), _p(g_gn_w), _p(g_gn_b), N, Ce, BF16): L.cot_group_norm9_backward_params(*a_, st_), gn_ws)
     else:
         ge3, g_gn_w, g_gn_b = torch.ops.aten.native_group_norm_backward(
             gw, e3, gn_mean, gn_rstd, gn.weight, N, Ce, HW, gn.num_groups, [True, True, True])
@@ -865,33 +806,33 @@ def _cot_backward(L, layer, saved, geom, gout, side=None):
     ge1 = torch.empty_like(e1)
     g_we3, g_be3 = grad_sink.out_like(em3.weight), grad_sink.out_like(em3.bias)
     if GX:
-        _ck(L.cot_conv1x1g_backward_data(_p(ge3), _p(em3.weight), _p(ge1), 0, N, Ch, Ce, 2, HW, BF16, st), "cot_conv1x1g_backward_data")
-        side.run(lambda st_, a_=(_p(ge3), _p(e1), _p(g_we3), _p(g_be3), _p(side.ws), N, Ch, Ce, 2, HW, BF16): _ck(L.cot_conv1x1g_backward_weight(*a_, st_), "cot_conv1x1g_backward_weight"), ge3, e1)
+        L.cot_conv1x1g_backward_data(_p(ge3), _p(em3.weight), _p(ge1), 0, N, Ch, Ce, 2, HW, BF16, st)
+        side.run(lambda st_, a_=(_p(ge3), _p(e1), _p(g_we3), _p(g_be3), _p(side.ws), N, Ch, Ce, 2, HW, BF16): L.cot_conv1x1g_backward_weight(*a_, st_), ge3, e1)
     else:
-        _ck(L.cot_conv1x1_backward_data(_p(ge3), _p(em3.weight), _p(ge1), None, Ch, 0, _p(ws), N, Ch, Ce, HW, BF16,
-                                        st), "cot_conv1x1_backward_data")
-        side.run(lambda st_, a_=(_p(ge3), _p(e1), None, Ch, _p(g_we3), _p(g_be3), _p(side.ws), N, Ch, Ce, HW, BF16): _ck(L.cot_conv1x1_backward_weight(*a_, st_), "cot_conv1x1_backward_weight"), ge3, e1)
+        L.cot_conv1x1_backward_data(_p(ge3), _p(em3.weight), _p(ge1), None, Ch, 0, _p(ws), N, Ch, Ce, HW, BF16,
+                                    st)
+        side.run(lambda st_, a_=(_p(ge3), _p(e1), None, Ch, _p(g_we3), _p(g_be3), _p(side.ws), N, Ch, Ce, HW, BF16): L.cot_conv1x1_backward_weight(*a_, st_), ge3, e1)
     ge0 = torch.empty_like(e0)
     d_em_w, d_em_b = _bn_bwd(L, ge1, e0, None, ge0, em1, s_e, N, Ch, HW, 1, nws_h)  # (ReLU mask recomputed from e0)
     g_we0 = grad_sink.out_like(em0.weight)
     if GX:  # gradient of the interleaved [x0, k0, x1, k1, ...]: de-interleaved into dx / dk (two strided adds)
         gqk = torch.empty_like(qk)
-        _ck(L.cot_conv1x1g_backward_data(_p(ge0), _p(em0.weight), _p(gqk), 0, N, 2 * C, Ch, 2, HW, BF16, st), "cot_conv1x1g_backward_data")
+        L.cot_conv1x1g_backward_data(_p(ge0), _p(em0.weight), _p(gqk), 0, N, 2 * C, Ch, 2, HW, BF16, st)
         gq5 = gqk.view(N, C, 2, H, W)
         gx.add_(gq5[:, :, 0])
         gk.add_(gq5[:, :, 1])
-        side.run(lambda st_, a_=(_p(ge0), _p(qk), _p(g_we0), None, _p(side.ws), N, 2 * C, Ch, 2, HW, BF16): _ck(L.cot_conv1x1g_backward_weight(*a_, st_), "cot_conv1x1g_backward_weight"), ge0, qk)
+        side.run(lambda st_, a_=(_p(ge0), _p(qk), _p(g_we0), None, _p(side.ws), N, 2 * C, Ch, 2, HW, BF16): L.cot_conv1x1g_backward_weight(*a_, st_), ge0, qk)
     else:
-        _ck(L.cot_conv1x1_backward_data(_p(ge0), _p(em0.weight), _p(gx), _p(gk), C, 3, _p(ws), N, 2 * C, Ch, HW, BF16,
-                                        st), "cot_conv1x1_backward_data")
-        side.run(lambda st_, a_=(_p(ge0), _p(x), _p(k), C, _p(g_we0), None, _p(side.ws), N, 2 * C, Ch, HW, BF16): _ck(L.cot_conv1x1_backward_weight(*a_, st_), "cot_conv1x1_backward_weight"), ge0, x, k)
+        L.cot_conv1x1_backward_data(_p(ge0), _p(em0.weight), _p(gx), _p(gk), C, 3, _p(ws), N, 2 * C, Ch, HW, BF16,
+                                    st)
+        side.run(lambda st_, a_=(_p(ge0), _p(x), _p(k), C, _p(g_we0), None, _p(side.ws), N, 2 * C, Ch, HW, BF16): L.cot_conv1x1_backward_weight(*a_, st_), ge0, x, k)
     # key branch: bn+relu, grouped 3x3 -> dx +=
     gk_pre = gv  # (reuse: gv is dead)
     d_ke_w, d_ke_b = _bn_bwd(L, gk, k_pre, None, gk_pre, ke1, s_k, N, C, HW, 1, nws_c)
     G = ke0.groups
     g_wk = grad_sink.out_like(ke0.weight)
     side.run(lambda st_, a_=(_p(gk_pre), _p(x), _p(g_wk), _p(masks), _p(side.ws), N, C, C, G, H, W, BF16,
-                                               _guard_elems(x)): _ck(L.cot_conv3x3g_backward_weight_guarded(*a_, st_), "cot_conv3x3g_backward_weight"), gk_pre, x, masks)
+                                               _guard_elems(x)): L.cot_conv3x3g_backward_weight_guarded(*a_, st_), gk_pre, x, masks)
     _conv3x3_dgrad(L, ke0, gk_pre, gx, 1, masks, ws, N, C, G, H, W)
     if own_side:
         side.join()
@@ -905,7 +846,7 @@ class _CotLayerNode(Function):
     @_one_stream_query
     def forward(ctx, layer, x, *params):
         # params (_Plan.params) are only here so that autograd routes their gradients; values are read off `layer`
-        out, saved, geom = _cot_forward(_lib.lib(), layer, x)
+        out, saved, geom = _cot_forward(_lib.api(), layer, x)
         ctx.layer, ctx.geom = layer, geom
         ctx.save_for_backward(*saved)
         return out
@@ -913,7 +854,7 @@ class _CotLayerNode(Function):
     @staticmethod
     @_one_stream_query
     def backward(ctx, gout):
-        gx, gparams = _cot_backward(_lib.lib(), ctx.layer, ctx.saved_tensors, ctx.geom, gout)
+        gx, gparams = _cot_backward(_lib.api(), ctx.layer, ctx.saved_tensors, ctx.geom, gout)
         return (None, gx) + gparams
 
 
@@ -930,7 +871,7 @@ def _conv_ok(conv, k, groups=None):
 def eligible(layer, x):
     """training-mode CotLayer on a bf16 NCHW tensor whose every piece the kernels cover (mixed precision as
     cotnet_amd.flat_sgd.to_mixed_bf16 sets it up: bf16 convolution / GroupNorm parameters, fp32 BatchNorm parameters)"""
-    if not (ENABLED and layer.training and (x.is_cuda or not _DEVICE_ONLY) and x.dim() == 4
+    if not (ENABLED and layer.training and (x.is_cuda or not _lib.DEVICE_ONLY) and x.dim() == 4
             and x.dtype == torch.bfloat16 and x.is_contiguous() and x.data_ptr() % 16 == 0
             and x.shape[1] == layer.dim):
         return False
@@ -1032,7 +973,7 @@ class _BottleneckNode(Function):
     @staticmethod
     @_one_stream_query
     def forward(ctx, blk, x, *params):
-        L = _lib.lib()
+        L = _lib.api()
         bp = _block_plan(blk)
         N, Cin, H, W = x.shape
         Cw, Cout = bp.conv1.out_channels, bp.conv3.out_channels
@@ -1049,22 +990,22 @@ class _BottleneckNode(Function):
         _conv_bn_fwd(L, x, None, Cin, bp.conv1, c1, a1, bp.bn1, s_1, 2 * Cw, N, Cin, Cw, HW, 1)
         if bp.avd:
             p1 = _new_guarded(N, Cw, Ho, Wo, x.dtype, dev)
-            _ck(L.cot_avgpool3x3s2_forward(_p(a1), _p(p1), N * Cw, H, W, BF16, st), "cot_avgpool3x3s2_forward")
+            L.cot_avgpool3x3s2_forward(_p(a1), _p(p1), N * Cw, H, W, BF16, st)
         else:
             p1 = a1
         cot_out, saved, geom = _cot_forward(L, bp.cot, p1)
         if bp.avd_post:  # anti-aliased down-sampling behind the layer (cotnet_hybrid.py:196-199; blur_pool.py:53-58)
             cot_full = cot_out
             cot_out = new(Cw, Ho, Wo)
-            _ck(L.cot_blurpool3x3s2_forward(_p(cot_full), _p(cot_out), N * Cw, H, W, BF16, st), "cot_blurpool3x3s2_forward")
+            L.cot_blurpool3x3s2_forward(_p(cot_full), _p(cot_out), N * Cw, H, W, BF16, st)
         c3, y = new(Cout, Ho, Wo), new(Cout, Ho, Wo)
         if bp.ds_conv is not None:  # projection shortcut: bn(conv1x1(x)), on every second pixel in a stride-2 block
             if bp.ds_pool2:  # `avg_down`: 2 x 2 average pooling, then the stride-1 projection
                 xs = torch.empty((N, Cin, H // 2, W // 2), dtype=x.dtype, device=dev)
-                _ck(L.cot_avgpool2x2s2_forward(_p(x), _p(xs), N * Cin, H, W, BF16, st), "cot_avgpool2x2s2_forward")
+                L.cot_avgpool2x2s2_forward(_p(x), _p(xs), N * Cin, H, W, BF16, st)
             elif bp.ds_stride == 2 and H % 2 == 0 and W % 2 == 0:  # every second pixel: one pass, 16-byte accesses (pool3x3.hip)
                 xs = torch.empty((N, Cin, H // 2, W // 2), dtype=x.dtype, device=dev)
-                _ck(L.cot_subsample2_forward(_p(x), _p(xs), N * Cin, H, W, BF16, st), "cot_subsample2_forward")
+                L.cot_subsample2_forward(_p(x), _p(xs), N * Cin, H, W, BF16, st)
             else:
                 xs = x[:, :, ::2, ::2].contiguous() if bp.ds_stride == 2 else x
             d0, res = new(Cout, Ho, Wo), new(Cout, Ho, Wo)
@@ -1085,7 +1026,7 @@ class _BottleneckNode(Function):
     @staticmethod
     @_one_stream_query
     def backward(ctx, gout):
-        L = _lib.lib()
+        L = _lib.api()
         blk = ctx.blk
         bp = _block_plan(blk)
         t = ctx.saved_tensors
@@ -1112,20 +1053,20 @@ class _BottleneckNode(Function):
         g_c3, g_res = torch.empty_like(c3), (None if fold else torch.empty_like(c3))
         d_bn3_w, d_bn3_b = _bn_bwd(L, gout, c3, y, g_c3, bp.bn3, s_3, N, Cout, HWo, 1, nws_o, dres=g_res, ps=ps, mask=m3)
         g_cot_out = torch.empty_like(cot_out)
-        _ck(L.cot_conv1x1_backward_data(_p(g_c3), _p(bp.conv3.weight), _p(g_cot_out), None, Cw, 0, _p(ws), N, Cw, Cout, HWo,
-                                        BF16, st), "cot_conv1x1_backward_data")
+        L.cot_conv1x1_backward_data(_p(g_c3), _p(bp.conv3.weight), _p(g_cot_out), None, Cw, 0, _p(ws), N, Cw, Cout, HWo,
+                                    BF16, st)
         g_w3 = grad_sink.out_like(bp.conv3.weight)
-        side.run(lambda st_, a_=(_p(g_c3), _p(cot_out), None, Cw, _p(g_w3), None, _p(side.ws), N, Cw, Cout, HWo, BF16): _ck(L.cot_conv1x1_backward_weight(*a_, st_), "cot_conv1x1_backward_weight"), g_c3, cot_out)
+        side.run(lambda st_, a_=(_p(g_c3), _p(cot_out), None, Cw, _p(g_w3), None, _p(side.ws), N, Cw, Cout, HWo, BF16): L.cot_conv1x1_backward_weight(*a_, st_), g_c3, cot_out)
         if bp.avd_post:  # (cot_out at the output resolution was the pooled tensor: its gradient goes back through the blur)
             g_full = torch.empty((N, Cw, H, W), dtype=x.dtype, device=dev)
-            _ck(L.cot_blurpool3x3s2_backward(_p(g_cot_out), _p(g_full), N * Cw, H, W, BF16, st), "cot_blurpool3x3s2_backward")
+            L.cot_blurpool3x3s2_backward(_p(g_cot_out), _p(g_full), N * Cw, H, W, BF16, st)
             g_layer_out = g_full
         else:
             g_layer_out = g_cot_out
         g_p1, g_cot = _cot_backward(L, bp.cot, saved, ctx.geom, g_layer_out, side)
         if bp.avd:
             g_a1 = torch.empty_like(a1)
-            _ck(L.cot_avgpool3x3s2_backward(_p(g_p1), _p(g_a1), N * Cw, H, W, BF16, st), "cot_avgpool3x3s2_backward")
+            L.cot_avgpool3x3s2_backward(_p(g_p1), _p(g_a1), N * Cw, H, W, BF16, st)
             g_c1 = torch.empty_like(c1)
         else:
             g_a1 = g_p1
@@ -1139,45 +1080,44 @@ class _BottleneckNode(Function):
             d_ds_w, d_ds_b = _bn_bwd(L, g_res, d0, None, g_d0, bp.ds_bn, s_d, N, Cout, HWo, 0, nws_o)
             if bp.ds_pool2:  # the projection saw 2 x 2 averages: its data gradient is spread over the four pixels of each window
                 g_xs = torch.empty_like(xs)
-                _ck(L.cot_conv1x1_backward_data(_p(g_d0), _p(bp.ds_conv.weight), _p(g_xs), None, Cin, 0, _p(ws), N, Cin,
-                                                Cout, HWo, BF16, st), "cot_conv1x1_backward_data")
+                L.cot_conv1x1_backward_data(_p(g_d0), _p(bp.ds_conv.weight), _p(g_xs), None, Cin, 0, _p(ws), N, Cin,
+                                            Cout, HWo, BF16, st)
                 gx = torch.empty_like(x)
-                _ck(L.cot_avgpool2x2s2_backward(_p(g_xs), _p(gx), N * Cin, H, W, BF16, st), "cot_avgpool2x2s2_backward")
+                L.cot_avgpool2x2s2_backward(_p(g_xs), _p(gx), N * Cin, H, W, BF16, st)
             elif bp.ds_stride == 2:  # the projection saw every second pixel: its data gradient lands there, zeros elsewhere
                 g_xs = torch.empty_like(xs)
-                _ck(L.cot_conv1x1_backward_data(_p(g_d0), _p(bp.ds_conv.weight), _p(g_xs), None, Cin, 0, _p(ws), N, Cin,
-                                                Cout, HWo, BF16, st), "cot_conv1x1_backward_data")
+                L.cot_conv1x1_backward_data(_p(g_d0), _p(bp.ds_conv.weight), _p(g_xs), None, Cin, 0, _p(ws), N, Cin,
+                                            Cout, HWo, BF16, st)
                 if H % 2 == 0 and W % 2 == 0:  # values back in place and the zeros around them in one pass
                     gx = torch.empty_like(x)
-                    _ck(L.cot_subsample2_backward(_p(g_xs), _p(gx), N * Cin, H, W, BF16, st), "cot_subsample2_backward")
+                    L.cot_subsample2_backward(_p(g_xs), _p(gx), N * Cin, H, W, BF16, st)
                 else:
                     gx = torch.zeros_like(x)
                     gx[:, :, ::2, ::2] = g_xs
             else:
                 gx = torch.empty_like(x)
-                _ck(L.cot_conv1x1_backward_data(_p(g_d0), _p(bp.ds_conv.weight), _p(gx), None, Cin, 0, _p(ws), N, Cin,
-                                                Cout, HWo, BF16, st), "cot_conv1x1_backward_data")
+                L.cot_conv1x1_backward_data(_p(g_d0), _p(bp.ds_conv.weight), _p(gx), None, Cin, 0, _p(ws), N, Cin,
+                                            Cout, HWo, BF16, st)
             g_wd = grad_sink.out_like(bp.ds_conv.weight)
-            side.run(lambda st_, a_=(_p(g_d0), _p(xs), None, Cin, _p(g_wd), None, _p(side.ws), N, Cin, Cout, HWo, BF16): _ck(L.cot_conv1x1_backward_weight(*a_, st_), "cot_conv1x1_backward_weight"), g_d0, xs)
+            side.run(lambda st_, a_=(_p(g_d0), _p(xs), None, Cin, _p(g_wd), None, _p(side.ws), N, Cin, Cout, HWo, BF16): L.cot_conv1x1_backward_weight(*a_, st_), g_d0, xs)
             g_ds = (g_wd, d_ds_w, d_ds_b)
         else:
             gx = g_res  # identity shortcut: the residual's gradient is the first contribution to dx
         g_w1 = grad_sink.out_like(bp.conv1.weight)  # (issued before its data gradient: the two overlap)
-        side.run(lambda st_, a_=(_p(g_c1), _p(x), None, Cin, _p(g_w1), None, _p(side.ws), N, Cin, Cw, HW, BF16): _ck(L.cot_conv1x1_backward_weight(*a_, st_), "cot_conv1x1_backward_weight"), g_c1, x)
+        side.run(lambda st_, a_=(_p(g_c1), _p(x), None, Cin, _p(g_w1), None, _p(side.ws), N, Cin, Cw, HW, BF16): L.cot_conv1x1_backward_weight(*a_, st_), g_c1, x)
         if fold:
             gx = torch.empty_like(x)
-            _ck(L.cot_conv1x1_backward_data_relu_res(_p(g_c1), _p(bp.conv1.weight), _p(gx), _p(gout), _p(m3), N, Cin, Cw, HW, BF16, st),
-                "cot_conv1x1_backward_data_relu_res")
+            L.cot_conv1x1_backward_data_relu_res(_p(g_c1), _p(bp.conv1.weight), _p(gx), _p(gout), _p(m3), N, Cin, Cw, HW, BF16, st)
         else:
-            _ck(L.cot_conv1x1_backward_data(_p(g_c1), _p(bp.conv1.weight), _p(gx), None, Cin, 1, _p(ws), N, Cin, Cw, HW, BF16,
-                                            st), "cot_conv1x1_backward_data")
+            L.cot_conv1x1_backward_data(_p(g_c1), _p(bp.conv1.weight), _p(gx), None, Cin, 1, _p(ws), N, Cin, Cw, HW, BF16,
+                                        st)
         side.join()
         return (None, gx, g_w1, d_bn1_w, d_bn1_b) + g_cot + (g_w3, d_bn3_w, d_bn3_b) + g_ds
 
 
 def block_eligible(blk, x):
     """training-mode cotnet.Bottleneck (no avd pooling, no drop-block/path) whose CotLayer is eligible"""
-    if not (ENABLED and blk.training and (x.is_cuda or not _DEVICE_ONLY) and x.dim() == 4
+    if not (ENABLED and blk.training and (x.is_cuda or not _lib.DEVICE_ONLY) and x.dim() == 4
             and x.dtype == torch.bfloat16 and x.is_contiguous() and x.data_ptr() % 16 == 0):
         return False
     bp = _block_plan(blk)

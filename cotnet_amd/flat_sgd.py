@@ -14,16 +14,11 @@ On MI355X the step is bound by HBM passes and launch count, so this module
 Arithmetic = torch.optim.SGD (dampening 0) evaluated in fp32 on the master weights; checked against it in
 tests/test_flat_sgd_gpu.py.
 """
-import ctypes
-
 import torch
 from torch import nn
 
 from . import _lib
 from .data_parallel import GradBucketReducer
-
-
-_DEVICE_ONLY = True  # tests drive the optimizer on CPU tensors through the host-emulated kernels
 
 
 def to_mixed_bf16(model):
@@ -90,22 +85,20 @@ class FlatSGD:
             self.reducer.allreduce_all()
         else:
             self.reducer.finish()
-        L = _lib.lib()
-        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream) if _DEVICE_ONLY else None
+        L = _lib.api()
+        stream = _lib.stream()
         for b, st in zip(self.reducer.buckets, self.state):
             key = b.key
             wd = self.weight_decay if key == "decay" else 0.0
-            rc = L.cot_sgd_step(ctypes.c_void_p(b.pflat.data_ptr()),
-                                ctypes.c_void_p(st["master"].data_ptr()) if st["master"] is not None else None,
-                                ctypes.c_void_p(st["mom"].data_ptr()), ctypes.c_void_p(self.reducer.reduced(b).data_ptr()),
-                                b.pflat.numel(), self.lr, self.momentum, wd, 1.0, 1 if self.nesterov else 0,
-                                _lib.dtype_code(b.pflat.dtype), _lib.dtype_code(self.reducer.reduced(b).dtype), stream)
-            _lib.check(rc, "cot_sgd_step")
+            L.cot_sgd_step(b.pflat.data_ptr(),
+                           st["master"].data_ptr() if st["master"] is not None else None,
+                           st["mom"].data_ptr(), self.reducer.reduced(b).data_ptr(),
+                           b.pflat.numel(), self.lr, self.momentum, wd, 1.0, 1 if self.nesterov else 0,
+                           _lib.dtype_code(b.pflat.dtype), _lib.dtype_code(self.reducer.reduced(b).dtype), stream)
             if self.ema_decay is not None:
                 src = st["master"] if st["master"] is not None else b.pflat
-                rc = L.cot_ema_step(ctypes.c_void_p(st["ema"].data_ptr()), ctypes.c_void_p(src.data_ptr()), src.numel(),
-                                    self.ema_decay, _lib.dtype_code(src.dtype), stream)
-                _lib.check(rc, "cot_ema_step")
+                L.cot_ema_step(st["ema"].data_ptr(), src.data_ptr(), src.numel(),
+                               self.ema_decay, _lib.dtype_code(src.dtype), stream)
         if self.ema_decay is not None and self._buf_src:
             torch._foreach_lerp_(self._buf_ema, [bf.float() if bf.dtype != torch.float32 else bf for bf in self._buf_src],
                                  1.0 - self.ema_decay)

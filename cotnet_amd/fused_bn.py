@@ -10,7 +10,6 @@ The fused path is taken for training-mode NCHW-contiguous fp32 / bf16 CUDA tenso
 for eval-mode modules under torch.no_grad() (cot_bn_act_inference); anything else (eval mode with autograd, channels_last,
 fp64, momentum=None, CPU) takes the plain torch modules, so results and state are identical either way.
 """
-import ctypes
 import os
 
 import torch
@@ -18,20 +17,10 @@ import torch.nn.functional as F
 from torch.autograd import Function
 
 from . import _lib
+from ._lib import ptr as _p, stream as _stream
 
 ENABLED = os.environ.get("COT_FUSED_BN", "1") != "0"  # A/B switch: 0 = always take the plain torch modules
 _ACTS = {None: 0, "none": 0, "relu": 1, "silu": 2}
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-_DEVICE_ONLY = True  # tests drive the autograd wiring on CPU tensors through the host-emulated kernels
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream) if _DEVICE_ONLY else None
 
 
 _WS = _lib.register_cache({})  # (N, C) -> workspace floats (pure function of the shape; avoids a library call per launch)
@@ -50,7 +39,7 @@ class _BNAct(Function):
     @staticmethod
     def forward(ctx, x, residual, weight, bias, running_mean, running_var, nbt, eps, momentum, act):
         N, C, H, W = x.shape
-        L = _lib.lib()
+        L = _lib.api()
         # (with a row's worth of margins inside its own allocation: a 3x3 convolution that consumes y -- a deep stem's, SplitAttn's --
         # then takes the LDS-staged weight gradient, cot_conv3x3g_backward_weight_guarded)
         from .conv3x3g import new_guarded
@@ -59,11 +48,9 @@ class _BNAct(Function):
         nws = _ws_floats(N, C)
         scratch = torch.empty(2 * C + nws, dtype=torch.float32, device=x.device)
         mean, rstd, ws = scratch[:C], scratch[C:2 * C], scratch[2 * C:]
-        rc = L.cot_bn_act_forward(_p(x), _p(residual), _p(y), _p(weight), _p(bias), _p(mean), _p(rstd),
-                                  _p(running_mean), _p(running_var), _p(nbt), _p(ws), N, C, H * W, eps, momentum, act,
-                                  _DT[x.dtype], _stream())
-        if rc:
-            _lib.check(rc, "cot_bn_act_forward")
+        L.cot_bn_act_forward(_p(x), _p(residual), _p(y), _p(weight), _p(bias), _p(mean), _p(rstd),
+                             _p(running_mean), _p(running_var), _p(nbt), _p(ws), N, C, H * W, eps, momentum, act,
+                             _DT[x.dtype], _stream())
         ctx.act, ctx.has_res = act, residual is not None
         ctx.save_for_backward(x, y if act == 1 else None, weight, bias, mean, rstd)
         return y
@@ -72,16 +59,14 @@ class _BNAct(Function):
     def backward(ctx, dy):
         x, y, weight, bias, mean, rstd = ctx.saved_tensors
         N, C, H, W = x.shape
-        L = _lib.lib()
+        L = _lib.api()
         dy = dy.contiguous()
         dx = torch.empty_like(x)
         dres = torch.empty_like(x) if (ctx.has_res and ctx.needs_input_grad[1]) else None
         scratch = torch.empty(2 * C + _ws_floats(N, C), dtype=torch.float32, device=x.device)
         dgamma, dbeta, ws = scratch[:C], scratch[C:2 * C], scratch[2 * C:]
-        rc = L.cot_bn_act_backward(_p(dy), _p(x), _p(y), _p(dx), _p(dres), _p(weight), _p(bias), _p(mean), _p(rstd),
-                                   _p(dgamma), _p(dbeta), _p(ws), N, C, H * W, ctx.act, _DT[x.dtype], _stream())
-        if rc:
-            _lib.check(rc, "cot_bn_act_backward")
+        L.cot_bn_act_backward(_p(dy), _p(x), _p(y), _p(dx), _p(dres), _p(weight), _p(bias), _p(mean), _p(rstd),
+                              _p(dgamma), _p(dbeta), _p(ws), N, C, H * W, ctx.act, _DT[x.dtype], _stream())
         return dx, dres, dgamma, dbeta, None, None, None, None, None, None
 
 
@@ -100,23 +85,21 @@ def _inference(x, bn, act, residual):
     """eval-mode BatchNorm (running statistics) + activation (+ residual) as one pass; no autograd (the caller checked)"""
     N, C, H, W = x.shape
     y = torch.empty_like(x)
-    rc = _lib.lib().cot_bn_act_inference(_p(x), _p(residual), _p(y), _p(bn.weight), _p(bn.bias), _p(bn.running_mean),
-                                         _p(bn.running_var), N, C, H * W, float(bn.eps), _ACTS[act], _DT[x.dtype], _stream())
-    if rc:
-        _lib.check(rc, "cot_bn_act_inference")
+    _lib.api().cot_bn_act_inference(_p(x), _p(residual), _p(y), _p(bn.weight), _p(bn.bias), _p(bn.running_mean),
+                                    _p(bn.running_var), N, C, H * W, float(bn.eps), _ACTS[act], _DT[x.dtype], _stream())
     return y
 
 
 def fused_bn_act(x, bn, act=None, residual=None):
     """act(bn(x) [+ residual]) with `bn` an nn.BatchNorm2d.  Fused HIP kernels when eligible, torch otherwise."""
-    if (ENABLED and not bn.training and not torch.is_grad_enabled() and (x.is_cuda or not _DEVICE_ONLY) and x.dim() == 4
+    if (ENABLED and not bn.training and not torch.is_grad_enabled() and (x.is_cuda or not _lib.DEVICE_ONLY) and x.dim() == 4
             and x.dtype in _DT and x.is_contiguous() and bn.affine and bn.track_running_stats and bn.running_mean is not None
             and bn.weight.dtype == torch.float32 and bn.running_mean.dtype == torch.float32 and x.data_ptr() % 16 == 0
             and (residual is None or (residual.shape == x.shape and residual.dtype == x.dtype and residual.is_contiguous()
                                       and residual.data_ptr() % 16 == 0))):
         return _inference(x, bn, act, residual)  # forward-only evaluation under torch.no_grad()
     # (tensors are assumed to live on the current device, as everywhere in a one-process-per-GPU job)
-    ok = (ENABLED and bn.training and (x.is_cuda or not _DEVICE_ONLY) and x.dim() == 4 and x.dtype in (torch.float32, torch.bfloat16)
+    ok = (ENABLED and bn.training and (x.is_cuda or not _lib.DEVICE_ONLY) and x.dim() == 4 and x.dtype in (torch.float32, torch.bfloat16)
           and x.is_contiguous() and bn.affine and bn.track_running_stats and bn.momentum is not None
           and bn.weight.dtype == torch.float32 and x.data_ptr() % 16 == 0
           and bn.num_batches_tracked is not None and bn.num_batches_tracked.dtype == torch.int64

@@ -5,24 +5,15 @@ with one read and one write forward, two reads and one write backward (torch: 2R
 Eligible: bf16 (H*W <= 8192) or fp32 NCHW-contiguous tensors, affine parameters of the same dtype, 9 channels per group;
 otherwise the module.
 """
-import ctypes
 import os
 
 import torch
 from torch.autograd import Function
 
 from . import _lib
+from ._lib import ptr as _p, stream as _stream
 
 MODE = os.environ.get("COT_GN9", "hip")  # default: the library's kernel; COT_GN9=module opts out
-_DEVICE_ONLY = True  # tests drive the autograd wiring on CPU tensors through the host-emulated kernels
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream) if _DEVICE_ONLY else None
 
 
 class _GroupNorm9(Function):
@@ -32,10 +23,8 @@ class _GroupNorm9(Function):
         G = C // 9
         y = torch.empty_like(x)
         stats = torch.empty(2 * N * G, dtype=torch.float32, device=x.device)
-        rc = _lib.lib().cot_group_norm9_forward(_p(x), _p(weight), _p(bias), _p(y), _p(stats), _p(stats[N * G:]), N, C,
-                                                H * W, eps, _lib.dtype_code(x.dtype), _stream())
-        if rc:
-            _lib.check(rc, "cot_group_norm9_forward")
+        _lib.api().cot_group_norm9_forward(_p(x), _p(weight), _p(bias), _p(y), _p(stats), _p(stats[N * G:]), N, C,
+                                           H * W, eps, _lib.dtype_code(x.dtype), _stream())
         ctx.save_for_backward(x, weight, stats)
         return y
 
@@ -47,16 +36,14 @@ class _GroupNorm9(Function):
         dy = dy.contiguous()
         dx, dg, db = torch.empty_like(x), torch.empty_like(weight), torch.empty_like(weight)
         ws = torch.empty(2 * N * C, dtype=torch.float32, device=x.device)
-        rc = _lib.lib().cot_group_norm9_backward(_p(dy), _p(x), _p(stats), _p(stats[N * G:]), _p(weight), _p(dx), _p(dg),
-                                                 _p(db), _p(ws), N, C, H * W, _lib.dtype_code(x.dtype), _stream())
-        if rc:
-            _lib.check(rc, "cot_group_norm9_backward")
+        _lib.api().cot_group_norm9_backward(_p(dy), _p(x), _p(stats), _p(stats[N * G:]), _p(weight), _p(dx), _p(dg),
+                                            _p(db), _p(ws), N, C, H * W, _lib.dtype_code(x.dtype), _stream())
         return dx, dg, db, None
 
 
 def eligible(gn, x):
     return (MODE == "hip" and isinstance(gn, torch.nn.GroupNorm) and gn.affine and gn.num_groups * 9 == gn.num_channels
-            and (x.is_cuda or not _DEVICE_ONLY) and x.dim() == 4 and x.dtype in (torch.bfloat16, torch.float32)
+            and (x.is_cuda or not _lib.DEVICE_ONLY) and x.dim() == 4 and x.dtype in (torch.bfloat16, torch.float32)
             and x.is_contiguous() and x.shape[1] == gn.num_channels and gn.weight.dtype == x.dtype
             and (x.dtype == torch.float32 or x.shape[2] * x.shape[3] <= 8192) and x.data_ptr() % 16 == 0)
 

@@ -7,7 +7,6 @@
 the launch count, this keeps the whole step free of library kernels that accumulate into pre-zeroed buffers, which is what
 HIP-graph replay tripped over in round 1.  Same parameters / state_dict as the modules it is applied to.
 """
-import ctypes
 import os
 
 import torch
@@ -15,36 +14,23 @@ from torch import nn
 from torch.autograd import Function
 
 from . import _lib, grad_sink
+from ._lib import ptr as _p, stream as _stream
 
 MODE = os.environ.get("COT_HEAD", "hip")  # default: the library's kernels; COT_HEAD=module opts out
-_DEVICE_ONLY = True  # tests drive the autograd wiring on CPU tensors through the host-emulated kernels
 BF16 = _lib.COT_BF16
 _WS = _lib.register_cache({})
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream) if _DEVICE_ONLY else None
-
-
-def _ck(rc, what):
-    if rc:
-        _lib.check(rc, what)
 
 
 class _Head(Function):
     @staticmethod
     def forward(ctx, x, weight, bias, drop_p=0.0):
-        L = _lib.lib()
+        L = _lib.api()
         N, C, H, W = x.shape
         O = weight.shape[0]
         st = _stream()
         gapT = torch.empty((C, N), dtype=x.dtype, device=x.device)
         dt = _lib.dtype_code(x.dtype)
-        _ck(L.cot_radix_gap_t(_p(x), None, _p(gapT), N, C, H * W, dt, st), "cot_radix_gap_t")
+        L.cot_radix_gap_t(_p(x), None, _p(gapT), N, C, H * W, dt, st)
         ctx.mask = None
         if drop_p > 0.0:  # F.dropout on the pooled descriptor (reference recipe: drop 0.25): C x N elements, two tiny launches
             # 0/1 keep mask, the 1/(1-p) scale applied in fp32 and the product rounded once -- as F.dropout does (a bf16 mask
@@ -52,8 +38,7 @@ class _Head(Function):
             ctx.mask, ctx.scale = torch.rand((C, N), dtype=torch.float32, device=x.device) >= drop_p, 1.0 / (1.0 - drop_p)
             gapT = (gapT.float() * ctx.mask * ctx.scale).to(x.dtype)
         logT = torch.empty((O, N), dtype=x.dtype, device=x.device)
-        _ck(L.cot_conv1x1_forward(_p(gapT), None, C, _p(weight), _p(bias), _p(logT), 1, C, O, N, dt, st),
-            "cot_conv1x1_forward")
+        L.cot_conv1x1_forward(_p(gapT), None, C, _p(weight), _p(bias), _p(logT), 1, C, O, N, dt, st)
         ctx.save_for_backward(gapT, weight)
         ctx.shape, ctx.has_bias = x.shape, bias is not None
         return logT.t().contiguous()
@@ -61,7 +46,7 @@ class _Head(Function):
     @staticmethod
     def backward(ctx, g):
         gapT, weight = ctx.saved_tensors
-        L = _lib.lib()
+        L = _lib.api()
         N, C, H, W = ctx.shape
         O = weight.shape[0]
         st = _stream()
@@ -73,12 +58,10 @@ class _Head(Function):
             nb = _WS[key] = int(L.cot_convg_workspace(1, C, O, 1, N, 1, 1)) if dt == _lib.COT_F32 else int(L.cot_conv1x1_workspace(1, C, O, N, 1))
         ws = torch.empty(nb, dtype=torch.uint8, device=g.device)
         ggapT = torch.empty_like(gapT)
-        _ck(L.cot_conv1x1_backward_data(_p(gT), _p(weight), _p(ggapT), None, C, 0, _p(ws), 1, C, O, N, dt, st),
-            "cot_conv1x1_backward_data")
+        L.cot_conv1x1_backward_data(_p(gT), _p(weight), _p(ggapT), None, C, 0, _p(ws), 1, C, O, N, dt, st)
         gw = grad_sink.out_like(weight)
         gb = torch.empty(O, dtype=weight.dtype, device=g.device) if ctx.has_bias else None
-        _ck(L.cot_conv1x1_backward_weight(_p(gT), _p(gapT), None, C, _p(gw), _p(gb), _p(ws), 1, C, O, N, dt, st),
-            "cot_conv1x1_backward_weight")
+        L.cot_conv1x1_backward_weight(_p(gT), _p(gapT), None, C, _p(gw), _p(gb), _p(ws), 1, C, O, N, dt, st)
         gf = ggapT.t().float()
         if ctx.mask is not None:
             gf = gf * (ctx.mask.t() * ctx.scale)
@@ -88,7 +71,7 @@ class _Head(Function):
 
 def eligible(pool, fc, x):
     return (MODE == "hip" and isinstance(fc, nn.Linear) and getattr(pool, "pool_type", None) == "avg"
-            and getattr(pool, "flatten", False) and (x.is_cuda or not _DEVICE_ONLY) and x.dim() == 4
+            and getattr(pool, "flatten", False) and (x.is_cuda or not _lib.DEVICE_ONLY) and x.dim() == 4
             and x.dtype in (torch.bfloat16, torch.float32) and x.is_contiguous() and fc.weight.dtype == x.dtype
             and (fc.bias is None or fc.bias.dtype == x.dtype)
             and fc.weight.is_contiguous() and fc.in_features == x.shape[1] and fc.in_features % 8 == 0

@@ -9,15 +9,12 @@ bf16 model); the side stream, the non-blocking copy and the one-batch look-ahead
 bit-identical to the reference's (IEEE subtract, then IEEE divide).  Random erasing (`re_prob`) is data augmentation and
 out of scope: a non-zero `re_prob` raises.
 """
-import ctypes
-
 import torch
 
 from . import _lib
 
 IMAGENET_DEFAULT_MEAN = (0.485, 0.456, 0.406)
 IMAGENET_DEFAULT_STD = (0.229, 0.224, 0.225)
-_DEVICE_ONLY = True  # tests drive the wrapper on CPU tensors through the host-emulated kernels
 
 
 def normalize_uint8(x, mean, std, dtype=torch.float32, out=None):
@@ -25,16 +22,14 @@ def normalize_uint8(x, mean, std, dtype=torch.float32, out=None):
     -> (x - mean[c]) / std[c] as `dtype`, one kernel on the current stream"""
     if x.dtype != torch.uint8 or x.dim() != 4 or not x.is_contiguous():
         raise TypeError("normalize_uint8: expects a contiguous uint8 NCHW tensor")
-    if _DEVICE_ONLY and not x.is_cuda:
+    if _lib.DEVICE_ONLY and not x.is_cuda:
         raise RuntimeError("normalize_uint8: cotnet_amd has no CPU path (input must be on the GPU)")
     N, C, H, W = x.shape
     if mean.numel() != C or std.numel() != C or mean.dtype != torch.float32 or std.dtype != torch.float32:
         raise ValueError("normalize_uint8: mean / std must be fp32 tensors with one entry per channel")
     y = torch.empty((N, C, H, W), dtype=dtype, device=x.device) if out is None else out
-    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream) if _DEVICE_ONLY else None
-    rc = _lib.lib().cot_input_normalize(x.data_ptr(), y.data_ptr(), mean.data_ptr(), std.data_ptr(), N * C, C, H * W,
-                                        _lib.dtype_code(dtype), stream)
-    _lib.check(rc, "cot_input_normalize")
+    _lib.api().cot_input_normalize(x.data_ptr(), y.data_ptr(), mean.data_ptr(), std.data_ptr(), N * C, C, H * W,
+                                   _lib.dtype_code(dtype), _lib.stream())
     return y
 
 

@@ -19,10 +19,11 @@ import torch.nn.functional as F
 from torch.autograd import Function
 
 from . import _lib
-from .aggregation_zeropad import _aligned, _ptr, _stream, aggregation_zeropad_softmax
+from ._lib import ptr as _ptr, stream as _stream
+from .aggregation_zeropad import _aligned, aggregation_zeropad_softmax
 
 _DT = (torch.float32, torch.bfloat16)
-_WS = _lib.register_cache({})  # (N, C, H, W, dtype) -> workspace bytes (< 0: not covered)
+_WS = _lib.register_cache({})  # (N, C, H, W, dtype) -> workspace bytes (< 0: geometry off the fused kernels)
 
 
 def _geom(q):
@@ -52,10 +53,8 @@ class _LocalRelation(Function):
         geom = _geom(q)
         out = torch.empty_like(v)
         probs = torch.empty((N, 1, C // 8, 9, H, W), dtype=q.dtype, device=q.device)
-        rc = _lib.lib().cot_local_relation_forward(_ptr(q), _ptr(k), _ptr(v), _ptr(pos), _ptr(out), _ptr(probs),
-                                                   ctypes.byref(geom), _lib.dtype_code(q.dtype), _stream())
-        if rc:
-            _lib.check(rc, "cot_local_relation_forward")
+        _lib.api().cot_local_relation_forward(_ptr(q), _ptr(k), _ptr(v), _ptr(pos), _ptr(out), _ptr(probs),
+                                              ctypes.byref(geom), _lib.dtype_code(q.dtype), _stream())
         ctx.geom, ctx.pos_dtype = geom, pos_dtype
         ctx.save_for_backward(q, k, v, pos, probs)
         return out
@@ -67,11 +66,9 @@ class _LocalRelation(Function):
         gq, gk, gv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
         gpos = torch.empty_like(pos)
         ws = torch.empty(_ws_bytes(q), dtype=torch.uint8, device=q.device)
-        rc = _lib.lib().cot_local_relation_backward(_ptr(gout), _ptr(q), _ptr(k), _ptr(v), _ptr(pos), _ptr(probs), _ptr(gq),
-                                                    _ptr(gk), _ptr(gv), _ptr(gpos), _ptr(ws), ctypes.byref(ctx.geom),
-                                                    _lib.dtype_code(q.dtype), _stream())
-        if rc:
-            _lib.check(rc, "cot_local_relation_backward")
+        _lib.api().cot_local_relation_backward(_ptr(gout), _ptr(q), _ptr(k), _ptr(v), _ptr(pos), _ptr(probs), _ptr(gq),
+                                               _ptr(gk), _ptr(gv), _ptr(gpos), _ptr(ws), ctypes.byref(ctx.geom),
+                                               _lib.dtype_code(q.dtype), _stream())
         return gq, gk, gv, gpos.to(ctx.pos_dtype)
 
 

@@ -8,7 +8,6 @@ of an int64 index tensor (or x).
 Also `nn.AvgPool2d(2, 2)` on even planes (the pooling of an `avg_down` shortcut, models/resnet.py:380-394).
 Any other module or tensor (other geometry, ceil_mode, fp64, channels-last, CPU) takes the module itself.
 """
-import ctypes
 import os
 
 import torch
@@ -16,18 +15,10 @@ from torch import nn
 from torch.autograd import Function
 
 from . import _lib
+from ._lib import ptr as _p, stream as _stream
 
 MODE = os.environ.get("COT_POOL", "hip")  # default: the library's kernels; COT_POOL=module opts out
-_DEVICE_ONLY = True  # tests drive the autograd wiring on CPU tensors through the host-emulated kernels
 _DT = {torch.float32: _lib.COT_F32, torch.bfloat16: _lib.COT_BF16}
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr())
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream) if _DEVICE_ONLY else None
 
 
 def _out(x):
@@ -40,9 +31,7 @@ class _AvgPool(Function):
     def forward(ctx, x):
         N, C, H, W = x.shape
         y = _out(x)
-        rc = _lib.lib().cot_avgpool3x3s2_forward(_p(x), _p(y), N * C, H, W, _DT[x.dtype], _stream())
-        if rc:
-            _lib.check(rc, "cot_avgpool3x3s2_forward")
+        _lib.api().cot_avgpool3x3s2_forward(_p(x), _p(y), N * C, H, W, _DT[x.dtype], _stream())
         ctx.shape = x.shape
         return y
 
@@ -51,9 +40,7 @@ class _AvgPool(Function):
         N, C, H, W = ctx.shape
         gy = gy.contiguous()
         gx = torch.empty(ctx.shape, dtype=gy.dtype, device=gy.device)
-        rc = _lib.lib().cot_avgpool3x3s2_backward(_p(gy), _p(gx), N * C, H, W, _DT[gy.dtype], _stream())
-        if rc:
-            _lib.check(rc, "cot_avgpool3x3s2_backward")
+        _lib.api().cot_avgpool3x3s2_backward(_p(gy), _p(gx), N * C, H, W, _DT[gy.dtype], _stream())
         return gx
 
 
@@ -63,9 +50,7 @@ class _AvgPool2(Function):
     def forward(ctx, x):
         N, C, H, W = x.shape
         y = torch.empty((N, C, H // 2, W // 2), dtype=x.dtype, device=x.device)
-        rc = _lib.lib().cot_avgpool2x2s2_forward(_p(x), _p(y), N * C, H, W, _DT[x.dtype], _stream())
-        if rc:
-            _lib.check(rc, "cot_avgpool2x2s2_forward")
+        _lib.api().cot_avgpool2x2s2_forward(_p(x), _p(y), N * C, H, W, _DT[x.dtype], _stream())
         ctx.shape = x.shape
         return y
 
@@ -74,9 +59,7 @@ class _AvgPool2(Function):
         N, C, H, W = ctx.shape
         gy = gy.contiguous()
         gx = torch.empty(ctx.shape, dtype=gy.dtype, device=gy.device)
-        rc = _lib.lib().cot_avgpool2x2s2_backward(_p(gy), _p(gx), N * C, H, W, _DT[gy.dtype], _stream())
-        if rc:
-            _lib.check(rc, "cot_avgpool2x2s2_backward")
+        _lib.api().cot_avgpool2x2s2_backward(_p(gy), _p(gx), N * C, H, W, _DT[gy.dtype], _stream())
         return gx
 
 
@@ -86,9 +69,7 @@ class _MaxPool(Function):
         N, C, H, W = x.shape
         y = _out(x)
         taps = torch.empty(y.shape, dtype=torch.uint8, device=x.device)  # winning element of every window, one byte
-        rc = _lib.lib().cot_maxpool3x3s2_forward_taps(_p(x), _p(y), _p(taps), N * C, H, W, _DT[x.dtype], _stream())
-        if rc:
-            _lib.check(rc, "cot_maxpool3x3s2_forward_taps")
+        _lib.api().cot_maxpool3x3s2_forward_taps(_p(x), _p(y), _p(taps), N * C, H, W, _DT[x.dtype], _stream())
         ctx.save_for_backward(taps)
         ctx.shape = x.shape
         return y
@@ -99,9 +80,7 @@ class _MaxPool(Function):
         N, C, H, W = ctx.shape
         gy = gy.contiguous()
         gx = torch.empty(ctx.shape, dtype=gy.dtype, device=gy.device)
-        rc = _lib.lib().cot_maxpool3x3s2_backward_taps(_p(gy), _p(taps), _p(gx), N * C, H, W, _DT[gy.dtype], _stream())
-        if rc:
-            _lib.check(rc, "cot_maxpool3x3s2_backward_taps")
+        _lib.api().cot_maxpool3x3s2_backward_taps(_p(gy), _p(taps), _p(gx), N * C, H, W, _DT[gy.dtype], _stream())
         return gx
 
 
@@ -112,9 +91,7 @@ class _BlurPool(Function):
     def forward(ctx, x):
         N, C, H, W = x.shape
         y = _out(x)
-        rc = _lib.lib().cot_blurpool3x3s2_forward(_p(x), _p(y), N * C, H, W, _DT[x.dtype], _stream())
-        if rc:
-            _lib.check(rc, "cot_blurpool3x3s2_forward")
+        _lib.api().cot_blurpool3x3s2_forward(_p(x), _p(y), N * C, H, W, _DT[x.dtype], _stream())
         ctx.shape = x.shape
         return y
 
@@ -123,14 +100,12 @@ class _BlurPool(Function):
         N, C, H, W = ctx.shape
         gy = gy.contiguous()
         gx = torch.empty(ctx.shape, dtype=gy.dtype, device=gy.device)
-        rc = _lib.lib().cot_blurpool3x3s2_backward(_p(gy), _p(gx), N * C, H, W, _DT[gy.dtype], _stream())
-        if rc:
-            _lib.check(rc, "cot_blurpool3x3s2_backward")
+        _lib.api().cot_blurpool3x3s2_backward(_p(gy), _p(gx), N * C, H, W, _DT[gy.dtype], _stream())
         return gx
 
 
 def blur_eligible(x):
-    return ((x.is_cuda or not _DEVICE_ONLY) and x.dim() == 4 and x.dtype in _DT and x.is_contiguous() and x.shape[2] >= 2
+    return ((x.is_cuda or not _lib.DEVICE_ONLY) and x.dim() == 4 and x.dtype in _DT and x.is_contiguous() and x.shape[2] >= 2
             and x.shape[3] >= 2)
 
 
@@ -143,7 +118,7 @@ def _pair(v):
 
 
 def eligible(module, x):
-    if not (MODE == "hip" and (x.is_cuda or not _DEVICE_ONLY) and x.dim() == 4 and x.dtype in _DT and x.is_contiguous()):
+    if not (MODE == "hip" and (x.is_cuda or not _lib.DEVICE_ONLY) and x.dim() == 4 and x.dtype in _DT and x.is_contiguous()):
         return False
     if isinstance(module, nn.MaxPool2d):
         return (_pair(module.kernel_size) == (3, 3) and _pair(module.stride) == (2, 2) and _pair(module.padding) == (1, 1)

@@ -10,26 +10,16 @@ replace adaptive_avg_pool2d + sigmoid + the broadcast multiply; the backward of 
 in one pass over (g, x).  The two fc layers and bn1 act on [B, C] descriptors (`se_mlp` below).  Eligible: NCHW-
 contiguous fp32 / bf16 tensors on the device when COT_FUSED_TAIL is on (default); anything else takes the torch formula.
 """
-import ctypes
-
 import torch
 import torch.nn.functional as F
 from torch import nn
 from torch.autograd import Function
 
 from . import _lib, radix_tail
+from ._lib import ptr as _p, stream as _stream
 from .fused_bn import fused_bn_act
 
 _DT = {torch.float32: _lib.COT_F32, torch.bfloat16: _lib.COT_BF16}
-_DEVICE_ONLY = True  # tests drive the autograd wiring on CPU tensors through the host-emulated kernels
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr())
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream) if _DEVICE_ONLY else None
 
 
 class _SeGap(Function):
@@ -37,9 +27,7 @@ class _SeGap(Function):
     def forward(ctx, x):
         B, C, H, W = x.shape
         gap = torch.empty((B, C, 1, 1), dtype=x.dtype, device=x.device)
-        rc = _lib.lib().cot_se_gap(_p(x), _p(gap), B * C, H * W, _DT[x.dtype], _stream())
-        if rc:
-            _lib.check(rc, "cot_se_gap")
+        _lib.api().cot_se_gap(_p(x), _p(gap), B * C, H * W, _DT[x.dtype], _stream())
         ctx.shape = x.shape
         return gap
 
@@ -54,9 +42,7 @@ class _SeGate(Function):
     def forward(ctx, x, logits):
         B, C, H, W = x.shape
         out = torch.empty_like(x)
-        rc = _lib.lib().cot_se_gate(_p(x), _p(logits), _p(out), B * C, H * W, _DT[x.dtype], _stream())
-        if rc:
-            _lib.check(rc, "cot_se_gate")
+        _lib.api().cot_se_gate(_p(x), _p(logits), _p(out), B * C, H * W, _DT[x.dtype], _stream())
         ctx.save_for_backward(x, logits)
         return out
 
@@ -66,14 +52,12 @@ class _SeGate(Function):
         B, C, H, W = x.shape
         g = g.contiguous()
         gx, gl = torch.empty_like(x), torch.empty_like(logits)
-        rc = _lib.lib().cot_se_gate_backward(_p(g), _p(x), _p(logits), _p(gx), _p(gl), B * C, H * W, _DT[x.dtype], _stream())
-        if rc:
-            _lib.check(rc, "cot_se_gate_backward")
+        _lib.api().cot_se_gate_backward(_p(g), _p(x), _p(logits), _p(gx), _p(gl), B * C, H * W, _DT[x.dtype], _stream())
         return gx, gl
 
 
 def eligible(x):
-    return (radix_tail.ENABLED and (x.is_cuda or not _DEVICE_ONLY) and x.dim() == 4 and x.dtype in _DT and x.is_contiguous()
+    return (radix_tail.ENABLED and (x.is_cuda or not _lib.DEVICE_ONLY) and x.dim() == 4 and x.dtype in _DT and x.is_contiguous()
             and x.data_ptr() % 16 == 0)
 
 

@@ -7,19 +7,14 @@ stem's two stride-1 3x3 convolutions go through cotnet_amd.conv3x3g (groups = 1)
 vendor convolution.  Eligible: bf16 NCHW-contiguous input that does not require grad, 32 or 64 output channels, output width a
 multiple of 8; anything else takes the module (counted by _lib.fallback).
 """
-import ctypes
-
 import torch
 from torch import nn
 from torch.autograd import Function
 
 from . import _lib, grad_sink, stem7x7
+from ._lib import stream as _stream
 
 _WS = _lib.register_cache({})
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream) if stem7x7._DEVICE_ONLY else None
 
 
 def _ws_bytes(N, H, W, Co):
@@ -36,9 +31,7 @@ class _Stem3x3(Function):
         N, _, H, W = x.shape
         Co = weight.shape[0]
         y = torch.empty((N, Co, (H - 1) // 2 + 1, (W - 1) // 2 + 1), dtype=x.dtype, device=x.device)
-        rc = _lib.lib().cot_stem3x3s2_forward(x.data_ptr(), weight.data_ptr(), y.data_ptr(), N, H, W, Co, _lib.COT_BF16, _stream())
-        if rc:
-            _lib.check(rc, "cot_stem3x3s2_forward")
+        _lib.api().cot_stem3x3s2_forward(x.data_ptr(), weight.data_ptr(), y.data_ptr(), N, H, W, Co, _lib.COT_BF16, _stream())
         ctx.save_for_backward(x, weight)
         return y
 
@@ -50,17 +43,15 @@ class _Stem3x3(Function):
         gy = gy.contiguous()
         ws = torch.empty(_ws_bytes(N, H, W, Co), dtype=torch.uint8, device=gy.device)
         gw = grad_sink.out_like(weight)
-        rc = _lib.lib().cot_stem3x3s2_backward_weight(gy.data_ptr(), x.data_ptr(), gw.data_ptr(), ws.data_ptr(), N, H, W, Co,
-                                                      _lib.COT_BF16, _stream())
-        if rc:
-            _lib.check(rc, "cot_stem3x3s2_backward_weight")
+        _lib.api().cot_stem3x3s2_backward_weight(gy.data_ptr(), x.data_ptr(), gw.data_ptr(), ws.data_ptr(), N, H, W, Co,
+                                                 _lib.COT_BF16, _stream())
         return None, gw
 
 
 def eligible(conv, x):
     return (stem7x7.MODE == "hip" and isinstance(conv, nn.Conv2d) and conv.in_channels == 3 and conv.out_channels in (32, 64)
             and conv.kernel_size == (3, 3) and conv.stride == (2, 2) and conv.padding == (1, 1) and conv.dilation == (1, 1)
-            and conv.groups == 1 and conv.bias is None and (x.is_cuda or not stem7x7._DEVICE_ONLY) and x.dim() == 4
+            and conv.groups == 1 and conv.bias is None and (x.is_cuda or not _lib.DEVICE_ONLY) and x.dim() == 4
             and x.shape[1] == 3 and x.dtype == torch.bfloat16 and conv.weight.dtype == torch.bfloat16
             and x.is_contiguous() and conv.weight.is_contiguous() and not x.requires_grad
             and x.data_ptr() % 16 == 0 and _ws_bytes(x.shape[0], x.shape[2], x.shape[3], conv.out_channels) > 0)

@@ -8,7 +8,6 @@ Eligible: bf16 (MFMA implicit GEMM) or fp32 (plain fp32 kernels, csrc/stem7x7_f3
 input that does not require grad, output width a multiple of 8 (224 / 256 / 288 / 320
 inputs); anything else takes the module.
 """
-import ctypes
 import os
 
 import torch
@@ -16,14 +15,10 @@ from torch import nn
 from torch.autograd import Function
 
 from . import _lib, grad_sink
+from ._lib import stream as _stream
 
 MODE = os.environ.get("COT_STEM", "hip")  # default: the library's kernels; COT_STEM=module opts out
-_DEVICE_ONLY = True  # tests drive the autograd wiring on CPU tensors through the host-emulated kernels
 _WS = _lib.register_cache({})
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream) if _DEVICE_ONLY else None
 
 
 def _ws_bytes(N, H, W):
@@ -39,10 +34,8 @@ class _Stem(Function):
     def forward(ctx, x, weight):
         N, _, H, W = x.shape
         y = torch.empty((N, 64, (H - 1) // 2 + 1, (W - 1) // 2 + 1), dtype=x.dtype, device=x.device)
-        rc = _lib.lib().cot_stem7x7s2_forward(x.data_ptr(), weight.data_ptr(), y.data_ptr(), N, H, W, _lib.dtype_code(x.dtype),
-                                              _stream())
-        if rc:
-            _lib.check(rc, "cot_stem7x7s2_forward")
+        _lib.api().cot_stem7x7s2_forward(x.data_ptr(), weight.data_ptr(), y.data_ptr(), N, H, W, _lib.dtype_code(x.dtype),
+                                         _stream())
         ctx.save_for_backward(x, weight)
         return y
 
@@ -53,17 +46,15 @@ class _Stem(Function):
         gy = gy.contiguous()
         ws = torch.empty(_ws_bytes(N, H, W), dtype=torch.uint8, device=gy.device)
         gw = grad_sink.out_like(weight)
-        rc = _lib.lib().cot_stem7x7s2_backward_weight(gy.data_ptr(), x.data_ptr(), gw.data_ptr(), ws.data_ptr(), N, H, W,
-                                                      _lib.dtype_code(x.dtype), _stream())
-        if rc:
-            _lib.check(rc, "cot_stem7x7s2_backward_weight")
+        _lib.api().cot_stem7x7s2_backward_weight(gy.data_ptr(), x.data_ptr(), gw.data_ptr(), ws.data_ptr(), N, H, W,
+                                                 _lib.dtype_code(x.dtype), _stream())
         return None, gw
 
 
 def eligible(conv, x):
     return (MODE == "hip" and isinstance(conv, nn.Conv2d) and conv.in_channels == 3 and conv.out_channels == 64
             and conv.kernel_size == (7, 7) and conv.stride == (2, 2) and conv.padding == (3, 3) and conv.dilation == (1, 1)
-            and conv.groups == 1 and conv.bias is None and (x.is_cuda or not _DEVICE_ONLY) and x.dim() == 4
+            and conv.groups == 1 and conv.bias is None and (x.is_cuda or not _lib.DEVICE_ONLY) and x.dim() == 4
             and x.shape[1] == 3 and x.dtype in (torch.bfloat16, torch.float32) and conv.weight.dtype == x.dtype
             and x.is_contiguous() and conv.weight.is_contiguous() and not x.requires_grad
             and x.data_ptr() % 16 == 0 and _ws_bytes(x.shape[0], x.shape[2], x.shape[3]) > 0)

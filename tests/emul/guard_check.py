@@ -13,9 +13,7 @@ import torch  # noqa: E402
 from cotnet_amd import _lib  # noqa: E402
 from tests.emul import build_emul  # noqa: E402
 
-E = ctypes.CDLL(build_emul.build())
-for _n, (_r, _a) in _lib.SYMBOLS.items():
-    getattr(E, _n).restype, getattr(E, _n).argtypes = _r, _a
+E = _lib.bind(ctypes.CDLL(build_emul.build()))
 libc = ctypes.CDLL(None, use_errno=True)
 PAGE = mmap.PAGESIZE
 _keep = []

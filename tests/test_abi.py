@@ -59,6 +59,54 @@ def test_validation_errors_without_touching_the_gpu():
         _lib.check(-1, "probe")
 
 
+def test_not_status_set_matches_the_header():
+    """_lib.NOT_STATUS names exactly the `int` returns that are values; every other `int` entry point is one the header declares,
+    i.e. one under its convention "return value: COT_OK (0) or a negative cot_status" """
+    ints = {n for n, (res, _) in _lib.SYMBOLS.items() if res is ctypes.c_int}
+    assert _lib.NOT_STATUS <= ints, sorted(_lib.NOT_STATUS - ints)
+    assert {n for n in ints if n.endswith("_covers")} <= _lib.NOT_STATUS
+    declared = set(header_functions())
+    for n in ints - _lib.NOT_STATUS:
+        assert n in declared, n
+
+
+def test_checked_view_raises_with_entry_and_status():
+    """_lib.api(): a status other than COT_OK raises CotError naming the entry point; values pass through unchecked"""
+    A = _lib.api()
+    fake = ctypes.c_void_p(0x1000)  # never dereferenced: validation fails first
+    g = _lib.AggGeom(2, 10, 8, 8, 1, 4, 3, 3, 1, 1, 1, 1, 1, 1)  # C % wC != 0
+    with pytest.raises(_lib.CotError, match="cot_agg_forward failed: invalid argument -- .*not divisible") as e:
+        A.cot_agg_forward(fake, fake, fake, ctypes.byref(g), _lib.COT_F32, _lib.COT_NCHW, None)
+    assert isinstance(e.value, RuntimeError) and e.value.status == -1 and e.value.entry == "cot_agg_forward"
+    g = _lib.AggGeom(2, 8, 8, 8, 1, 4, 3, 3, 1, 1, 1, 1, 1, 1)
+    with pytest.raises(_lib.CotError) as e:
+        A.cot_agg_forward(fake, fake, fake, ctypes.byref(g), 99, _lib.COT_NCHW, None)
+    assert e.value.status == _lib.COT_ERR_UNSUPPORTED and e.value.entry == "cot_agg_forward"
+    with pytest.raises(_lib.CotError) as e:
+        _lib.check(-1, "probe")
+    assert (e.value.status, e.value.entry) == (-1, "probe")
+    assert A.cot_conv1x1_lds_covers(256, 256, 0, 3136) == 1 and A.cot_conv1x1_lds_covers(7, 7, 0, 3136) == 0  # predicates: no raise
+    assert A.cot_abi_version() == 1 and A.cot_agg_out_size(8, 3, 1, 1, 1) == 8
+    assert A.cot_status_string(-1) == b"invalid argument"
+    assert _lib.api() is A and A._raw is _lib.lib()  # one view per handle
+
+
+def test_checked_view_follows_lib(monkeypatch):
+    """the view is resolved from _lib.lib() at use: a test that swaps the library swaps what the wrappers launch"""
+    class Other:
+        def cot_agg_forward(self, *a):
+            return 0
+
+        def cot_abi_version(self):
+            return 7
+    other = Other()
+    real = _lib.api()
+    monkeypatch.setattr(_lib, "lib", lambda: other)
+    assert _lib.api()._raw is other and _lib.api().cot_abi_version() == 7 and _lib.api().cot_agg_forward(1, 2) is None
+    monkeypatch.undo()
+    assert _lib.api()._raw is real._raw
+
+
 def test_product_has_no_cpu_fallback():
     """CPU tensors take the reference's route (copy to the GPU); without a GPU that must raise, not compute."""
     import torch

@@ -106,8 +106,7 @@ def _emulated_probe(monkeypatch, lib_wrapper=None):
         pytest.skip("host emulation build unavailable")
     L = lib_wrapper(tke._EMUL) if lib_wrapper else tke._EMUL
     monkeypatch.setattr(_lib, "lib", lambda: L)
-    for mod in (clf, c1, c3, fused_bn, radix_tail, g9, flat_sgd, p3, hf, s7):
-        monkeypatch.setattr(mod, "_DEVICE_ONLY", False)
+    monkeypatch.setattr(_lib, "DEVICE_ONLY", False)
     for mod, attr in ((clf, "ENABLED"), (c1, "MODE"), (c3, "MODE"), (g9, "MODE"), (p3, "MODE"), (hf, "MODE"), (s7, "MODE")):
         monkeypatch.setattr(mod, attr, getattr(mod, attr))
     monkeypatch.setattr(az, "aggregation_zeropad",

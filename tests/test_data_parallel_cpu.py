@@ -357,8 +357,7 @@ def _worker_fused_nodes(rank, world, port, q):
             q.put((rank, 0, "skip"))
             return
         _lib.lib = lambda: tke._EMUL
-        for mod in (clf, c1, c3, fused_bn, radix_tail, g9, flat_sgd, p3, hf, s7):
-            mod._DEVICE_ONLY = False
+        _lib.DEVICE_ONLY = False
         clf.ENABLED = True
         c1.MODE = c3.MODE = g9.MODE = p3.MODE = hf.MODE = s7.MODE = "hip"
         az.aggregation_zeropad = lambda i, w, kernel_size=3, stride=1, padding=0, dilation=1: tke._EmulAggregation.apply(i, w)
@@ -455,7 +454,7 @@ def test_default_buckets_leave_only_the_stem_exposed():
     last -- the one holding the stem's weight -- is the smallest share, so >= 3 all-reduces are launched while backward is
     still running (VERDICT r2 missing #1: 48 MiB made one bucket that completed with conv1.weight)"""
     import cotnet_amd
-    from cotnet_amd.flat_sgd import FlatSGD, to_mixed_bf16, _DEVICE_ONLY  # noqa: F401
+    from cotnet_amd.flat_sgd import FlatSGD, to_mixed_bf16
     from cotnet_amd import flat_sgd
     torch.manual_seed(0)
     model = to_mixed_bf16(cotnet_amd.create_model("cotnet50", num_classes=1000))

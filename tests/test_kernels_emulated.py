@@ -15,10 +15,7 @@ from tests.emul import build_emul
 from tests.bn_tail_cases import bn_tail_case, relu_res_case, rowstats_case
 
 try:
-    _EMUL = ctypes.CDLL(build_emul.build())
-    for _name, (_res, _args) in _lib.SYMBOLS.items():
-        getattr(_EMUL, _name).restype = _res
-        getattr(_EMUL, _name).argtypes = _args
+    _EMUL = _lib.bind(ctypes.CDLL(build_emul.build()))
 except FileNotFoundError as e:  # no host compiler: skip, the GPU tests still gate parity
     _EMUL = None
     _WHY = repr(e)
@@ -473,7 +470,7 @@ def test_bn_silu_after_a_residual_add_has_no_backward(monkeypatch):
     assert _EMUL.cot_bn_act_backward(P(dy), P(x), P(y), P(dx), None, P(gamma), P(beta), P(mean), P(rstd), P(dg), P(db), P(ws),
                                      N, C, HW, 2, 0, None) == 0
     monkeypatch.setattr(_lib, "lib", lambda: _EMUL)
-    monkeypatch.setattr(fused_bn, "_DEVICE_ONLY", False)
+    monkeypatch.setattr(_lib, "DEVICE_ONLY", False)
     monkeypatch.setattr(fused_bn, "ENABLED", True)
     bn = torch.nn.BatchNorm2d(C)
     xa, ra = x.clone().requires_grad_(True), res.clone().requires_grad_(True)
@@ -1175,7 +1172,7 @@ def test_conv1x1_autograd_wiring_on_emulated_kernels(split, bias, monkeypatch):
     from torch import nn
     from cotnet_amd import conv1x1 as c1
     monkeypatch.setattr(c1, "MODE", "hip")
-    monkeypatch.setattr(c1, "_DEVICE_ONLY", False)
+    monkeypatch.setattr(_lib, "DEVICE_ONLY", False)
     monkeypatch.setattr(_lib, "lib", lambda: _EMUL)
     c1._WS.clear()
     torch.manual_seed(2)
@@ -1464,7 +1461,7 @@ def test_conv3x3_autograd_wiring_on_emulated_kernels(monkeypatch):
     from torch import nn
     from cotnet_amd import conv3x3g as c3
     monkeypatch.setattr(c3, "MODE", "hip")
-    monkeypatch.setattr(c3, "_DEVICE_ONLY", False)
+    monkeypatch.setattr(_lib, "DEVICE_ONLY", False)
     monkeypatch.setattr(_lib, "lib", lambda: _EMUL)
     c3._WS.clear()
     c3._MASKS.clear()
@@ -1599,7 +1596,7 @@ def test_fused_cot_layer_node_on_emulated_kernels(cls, C, H, monkeypatch):
     two must agree to a few bf16 ulps (the only difference: dx / dk are summed in fp32 inside the kernels)."""
     import copy
     import cotnet_amd.aggregation_zeropad as az
-    from cotnet_amd import cot_layer_fused as clf, conv1x1 as c1, conv3x3g as c3, cotnet as cn, fused_bn, radix_tail
+    from cotnet_amd import cot_layer_fused as clf, conv1x1 as c1, conv3x3g as c3, cotnet as cn, fused_bn, group_norm9 as g9, radix_tail
     from cotnet_amd.flat_sgd import to_mixed_bf16
     torch.manual_seed(4)
     if isinstance(H, tuple):
@@ -1617,10 +1614,10 @@ def test_fused_cot_layer_node_on_emulated_kernels(cls, C, H, monkeypatch):
     g = torch.randn(N, C, H, W).bfloat16()
 
     monkeypatch.setattr(_lib, "lib", lambda: _EMUL)
-    for mod in (clf, c1, c3, fused_bn, radix_tail):
-        monkeypatch.setattr(mod, "_DEVICE_ONLY", False)
+    monkeypatch.setattr(_lib, "DEVICE_ONLY", False)
     monkeypatch.setattr(c1, "MODE", "hip")
     monkeypatch.setattr(c3, "MODE", "hip")
+    monkeypatch.setattr(g9, "MODE", "module")  # (the per-op side keeps torch's GroupNorm, as a CPU tensor always did there)
     monkeypatch.setattr(az, "aggregation_zeropad",
                         lambda i, w, kernel_size=3, stride=1, padding=0, dilation=1: _EmulAggregation.apply(i, w))
     for cache in (clf._SIZES, clf._MASKS, c1._WS, c3._WS, c3._MASKS, fused_bn._WS):
@@ -1818,13 +1815,13 @@ def test_fused_bottleneck_node_on_emulated_kernels(project, monkeypatch):
     x = torch.randn(N, inpl, H, W).bfloat16()
     g = torch.randn(N, 256, (H - 1) // stride + 1, (W - 1) // stride + 1).bfloat16()
 
-    from cotnet_amd import pool3x3 as p3
+    from cotnet_amd import group_norm9 as g9, pool3x3 as p3
     monkeypatch.setattr(_lib, "lib", lambda: _EMUL)
-    for mod in (clf, c1, c3, fused_bn, radix_tail, p3):
-        monkeypatch.setattr(mod, "_DEVICE_ONLY", False)
+    monkeypatch.setattr(_lib, "DEVICE_ONLY", False)
     monkeypatch.setattr(c1, "MODE", "hip")
     monkeypatch.setattr(c3, "MODE", "hip")
     monkeypatch.setattr(p3, "MODE", "hip")
+    monkeypatch.setattr(g9, "MODE", "module")  # (the per-op side keeps torch's GroupNorm, as a CPU tensor always did there)
     monkeypatch.setattr(az, "aggregation_zeropad",
                         lambda i, w, kernel_size=3, stride=1, padding=0, dilation=1: _EmulAggregation.apply(i, w))
     caches = (clf._SIZES, clf._MASKS, clf._BSIZES, c1._WS, c3._WS, c3._MASKS, fused_bn._WS)
@@ -1888,8 +1885,7 @@ def test_fused_split_attn_block_node_on_emulated_kernels(act, monkeypatch):
     x = torch.randn(N, 256, H, W).bfloat16()
     g = torch.randn(N, 256, H, W).bfloat16()
     monkeypatch.setattr(_lib, "lib", lambda: _EMUL)
-    for mod in (clf, c1, c3, fused_bn, radix_tail, se_gate):
-        monkeypatch.setattr(mod, "_DEVICE_ONLY", False)
+    monkeypatch.setattr(_lib, "DEVICE_ONLY", False)
     monkeypatch.setattr(c1, "MODE", "hip")
     monkeypatch.setattr(c3, "MODE", "hip")
     caches = (clf._SIZES, clf._MASKS, clf._BSIZES, clf._SASIZES, c1._WS, c3._WS, c3._MASKS, fused_bn._WS)
@@ -1943,8 +1939,7 @@ def test_residual_gradient_folded_into_conv1_data_gradient(monkeypatch):
     x = torch.randn(2, 256, 8, 8).bfloat16()
     g = torch.randn(2, 256, 8, 8).bfloat16()
     monkeypatch.setattr(_lib, "lib", lambda: _EMUL)
-    for mod in (clf, c1, c3, fused_bn, radix_tail):
-        monkeypatch.setattr(mod, "_DEVICE_ONLY", False)
+    monkeypatch.setattr(_lib, "DEVICE_ONLY", False)
     monkeypatch.setattr(c1, "MODE", "hip")
     monkeypatch.setattr(c3, "MODE", "hip")
     import cotnet_amd.aggregation_zeropad as az
@@ -2003,8 +1998,7 @@ def test_se_cotnetd_stage_opening_blocks_as_single_nodes(kind, monkeypatch):
     x = torch.randn(N, inpl, H, W).bfloat16()
     g = torch.randn(N, planes * 4, H // 2, W // 2).bfloat16()
     monkeypatch.setattr(_lib, "lib", lambda: _EMUL)
-    for mod in (clf, c1, c3, fused_bn, radix_tail, se_gate, g9, p3):
-        monkeypatch.setattr(mod, "_DEVICE_ONLY", False)
+    monkeypatch.setattr(_lib, "DEVICE_ONLY", False)
     for mod in (c1, c3, g9, p3):
         monkeypatch.setattr(mod, "MODE", "hip")
     import cotnet_amd.aggregation_zeropad as az
@@ -2068,8 +2062,7 @@ def test_whole_cotnet50_forward_backward_with_every_opt_in_on_emulated_kernels(m
     target = torch.tensor([1, 7, 3, 3])
 
     monkeypatch.setattr(_lib, "lib", lambda: _EMUL)
-    for mod in (clf, c1, c3, fused_bn, radix_tail, g9, p3, hf, s7):
-        monkeypatch.setattr(mod, "_DEVICE_ONLY", False)
+    monkeypatch.setattr(_lib, "DEVICE_ONLY", False)
     monkeypatch.setattr(az, "aggregation_zeropad",
                         lambda i, w, kernel_size=3, stride=1, padding=0, dilation=1: _EmulAggregation.apply(i, w))
     caches = (clf._SIZES, clf._MASKS, clf._BSIZES, c1._WS, c3._WS, c3._MASKS, fused_bn._WS, hf._WS)
@@ -2128,8 +2121,7 @@ def test_whole_model_with_folded_batchnorm_finalize(monkeypatch):
     x = torch.randn(2, 256, 6, 6).bfloat16()
     g = torch.randn(2, 256, 6, 6).bfloat16()
     monkeypatch.setattr(_lib, "lib", lambda: _EMUL)
-    for mod in (clf, c1, c3, fused_bn, radix_tail):
-        monkeypatch.setattr(mod, "_DEVICE_ONLY", False)
+    monkeypatch.setattr(_lib, "DEVICE_ONLY", False)
     monkeypatch.setattr(clf, "ENABLED", True)
     outs = []
     for fold in (0, 1):
@@ -2274,8 +2266,7 @@ def test_strided_projection_shortcut_on_emulated_kernels(monkeypatch):
     from cotnet_amd.flat_sgd import to_mixed_bf16
     from cotnet_amd.resnet import downsample_conv
     monkeypatch.setattr(_lib, "lib", lambda: _EMUL)
-    monkeypatch.setattr(c1, "_DEVICE_ONLY", False)
-    monkeypatch.setattr(fused_bn, "_DEVICE_ONLY", False)
+    monkeypatch.setattr(_lib, "DEVICE_ONLY", False)
     monkeypatch.setattr(c1, "MODE", "hip")
     c1._WS.clear()
     fused_bn._WS.clear()
@@ -2305,7 +2296,7 @@ def test_classifier_head_on_emulated_kernels(monkeypatch):
     from cotnet_amd import head_fused as hf
     from cotnet_amd.layers import create_classifier
     monkeypatch.setattr(_lib, "lib", lambda: _EMUL)
-    monkeypatch.setattr(hf, "_DEVICE_ONLY", False)
+    monkeypatch.setattr(_lib, "DEVICE_ONLY", False)
     monkeypatch.setattr(hf, "MODE", "hip")
     hf._WS.clear()
     torch.manual_seed(14)
@@ -2428,8 +2419,7 @@ def test_fp32_step_pieces_on_emulated_kernels(monkeypatch):
     from cotnet_amd import conv1x1 as c1, fused_bn, head_fused as hf, stem7x7 as s7
     from cotnet_amd.layers import create_classifier
     monkeypatch.setattr(_lib, "lib", lambda: _EMUL)
-    for mod in (c1, hf, s7, fused_bn):
-        monkeypatch.setattr(mod, "_DEVICE_ONLY", False)
+    monkeypatch.setattr(_lib, "DEVICE_ONLY", False)
     monkeypatch.setattr(c1, "MODE", "hip")
     monkeypatch.setattr(hf, "MODE", "hip")
     monkeypatch.setattr(s7, "MODE", "hip")
@@ -2522,8 +2512,7 @@ def test_deep_stem_runs_on_the_library_kernels(monkeypatch):
     from cotnet_amd import conv3x3g, fused_bn, resnet, stem3x3, stem7x7
     from cotnet_amd.flat_sgd import to_mixed_bf16
     monkeypatch.setattr(_lib, "_lib", _EMUL)
-    for mod in (conv3x3g, stem7x7, fused_bn):
-        monkeypatch.setattr(mod, "_DEVICE_ONLY", False)
+    monkeypatch.setattr(_lib, "DEVICE_ONLY", False)
     monkeypatch.setattr(conv3x3g, "MODE", "hip")
     monkeypatch.setattr(stem7x7, "MODE", "hip")
     torch.manual_seed(29)
@@ -2598,7 +2587,7 @@ def test_flat_sgd_weight_averaging_matches_the_reference_formula(monkeypatch):
     from cotnet_amd import flat_sgd
     from torch import nn
     monkeypatch.setattr(_lib, "lib", lambda: _EMUL)
-    monkeypatch.setattr(flat_sgd, "_DEVICE_ONLY", False)
+    monkeypatch.setattr(_lib, "DEVICE_ONLY", False)
     torch.manual_seed(5)
     model = flat_sgd.to_mixed_bf16(nn.Sequential(nn.Conv2d(4, 8, 3, padding=1), nn.BatchNorm2d(8), nn.ReLU(),
                                                  nn.Conv2d(8, 6, 1))).train()
@@ -2852,12 +2841,12 @@ def test_coxt_layer_on_emulated_kernels(dtype, monkeypatch):
     reference trains, and the mixed-precision form (bf16 convolutions, fp32 BatchNorm parameters) of bench.py"""
     import copy
     import cotnet_amd.aggregation_zeropad as az
-    from cotnet_amd import conv1x1 as c1, conv3x3g as c3, group_norm9 as g9, fused_bn, radix_tail
+    from cotnet_amd import cot_layer_fused as clf, conv1x1 as c1, conv3x3g as c3, group_norm9 as g9, fused_bn, radix_tail
     from cotnet_amd.cotnet import CoXtLayer
     from cotnet_amd.flat_sgd import to_mixed_bf16
     monkeypatch.setattr(_lib, "lib", lambda: _EMUL)
-    for mod in (c1, c3, g9, fused_bn, radix_tail):
-        monkeypatch.setattr(mod, "_DEVICE_ONLY", False)
+    monkeypatch.setattr(_lib, "DEVICE_ONLY", False)
+    monkeypatch.setattr(clf, "ENABLED", False)  # (one autograd node per op is what this test checks: the layer is not folded into the single node)
     for mod in (c1, c3, g9):
         monkeypatch.setattr(mod, "MODE", "hip")
     monkeypatch.setattr(az, "aggregation_zeropad",
@@ -2968,7 +2957,7 @@ def test_avgpool2x2_kernels_match_the_module(N, C, H, W, dtype, monkeypatch):
     assert _EMUL.cot_avgpool2x2s2_backward(P(gy), P(gx), N * C, H, W - 1, dt, None) == -2
     # module routing
     monkeypatch.setattr(_lib, "lib", lambda: _EMUL)
-    monkeypatch.setattr(p3, "_DEVICE_ONLY", False)
+    monkeypatch.setattr(_lib, "DEVICE_ONLY", False)
     monkeypatch.setattr(p3, "MODE", "hip")
     assert p3.eligible(mod, x) and not p3.eligible(mod, x[:, :, :-1]) and not p3.eligible(torch.nn.AvgPool2d(2, 1), x)
     xa = x.clone().requires_grad_(True)
@@ -3010,8 +2999,7 @@ def test_split_attn_radix1_and_blurpool_modules_on_emulated_kernels(monkeypatch)
     from cotnet_amd import conv3x3g as c3, fused_bn, pool3x3 as p3, radix_tail, se_gate
     from cotnet_amd.layers import BlurPool2d, SplitAttnConv2d
     monkeypatch.setattr(_lib, "lib", lambda: _EMUL)
-    for mod in (c3, fused_bn, p3, se_gate):
-        monkeypatch.setattr(mod, "_DEVICE_ONLY", False)
+    monkeypatch.setattr(_lib, "DEVICE_ONLY", False)
     monkeypatch.setattr(c3, "MODE", "hip")
     monkeypatch.setattr(p3, "MODE", "hip")
     for cache in (c3._WS, c3._MASKS, fused_bn._WS):

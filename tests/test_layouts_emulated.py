@@ -8,10 +8,7 @@ from tests import layout_cases as lc
 from tests.emul import build_emul
 
 try:
-    _EMUL = ctypes.CDLL(build_emul.build())
-    for _name, (_res, _args) in _lib.SYMBOLS.items():
-        getattr(_EMUL, _name).restype = _res
-        getattr(_EMUL, _name).argtypes = _args
+    _EMUL = _lib.bind(ctypes.CDLL(build_emul.build()))
 except FileNotFoundError:
     _EMUL = None
 
@@ -80,8 +77,7 @@ def test_channel_major_bottlenecks_against_the_nchw_single_node(H, blocks, coxt,
     x = torch.randn(N, inpl, H, W).bfloat16()
     g = torch.randn(N, inpl, H, W).bfloat16()
     monkeypatch.setattr(_lib, "lib", lambda: _EMUL)
-    for mod in (clf, c1, c3, fused_bn, radix_tail):
-        monkeypatch.setattr(mod, "_DEVICE_ONLY", False)
+    monkeypatch.setattr(_lib, "DEVICE_ONLY", False)
     caches = (clf._SIZES, clf._MASKS, clf._BSIZES, clf._CM_SIZES, clf._CM_OK)
     for cache in caches:
         cache.clear()
@@ -141,7 +137,7 @@ def test_eval_mode_bottleneck_as_one_call_sequence(kind, H, monkeypatch):
     import torch
 
     import cotnet_amd.aggregation_zeropad as az
-    from cotnet_amd import cot_layer_fused as clf, conv1x1 as c1, conv3x3g as c3, fused_bn, pool3x3 as p3, radix_tail
+    from cotnet_amd import cot_layer_fused as clf, conv1x1 as c1, conv3x3g as c3, fused_bn, group_norm9 as g9, pool3x3 as p3, radix_tail
     from cotnet_amd.cotnet import Bottleneck
     from cotnet_amd.flat_sgd import to_mixed_bf16
     from cotnet_amd.resnet import downsample_conv
@@ -161,8 +157,8 @@ def test_eval_mode_bottleneck_as_one_call_sequence(kind, H, monkeypatch):
     blk = to_mixed_bf16(blk).eval()
     x = torch.randn(2, inpl, H, H).bfloat16()
     monkeypatch.setattr(_lib, "lib", lambda: _EMUL)
-    for mod in (clf, c1, c3, fused_bn, radix_tail, p3):
-        monkeypatch.setattr(mod, "_DEVICE_ONLY", False)
+    monkeypatch.setattr(_lib, "DEVICE_ONLY", False)
+    monkeypatch.setattr(g9, "MODE", "module")  # (the per-op side keeps torch's GroupNorm, as a CPU tensor always did there)
     monkeypatch.setattr(az, "aggregation_zeropad", lambda i, w, kernel_size=3, stride=1, padding=0, dilation=1: _EmulAggregation.apply(i, w))
     for cache in (clf._SIZES, clf._MASKS, clf._BSIZES):
         cache.clear()
@@ -209,8 +205,7 @@ def test_channel_major_stage_with_its_opening_block(monkeypatch):
     x = torch.randn(N, 128, H, H).bfloat16()
     g = torch.randn(N, 256, H // 2, H // 2).bfloat16()
     monkeypatch.setattr(_lib, "lib", lambda: _EMUL)
-    for mod in (clf, c1, c3, fused_bn, radix_tail, p3):
-        monkeypatch.setattr(mod, "_DEVICE_ONLY", False)
+    monkeypatch.setattr(_lib, "DEVICE_ONLY", False)
     caches = (clf._SIZES, clf._MASKS, clf._BSIZES, clf._CM_SIZES, clf._CM_OK)
     for cache in caches:
         cache.clear()

@@ -13,10 +13,7 @@ from oracle import unfold_oracle
 from tests.emul import build_emul
 
 try:
-    _EMUL = ctypes.CDLL(build_emul.build())
-    for _name, (_res, _args) in _lib.SYMBOLS.items():
-        getattr(_EMUL, _name).restype = _res
-        getattr(_EMUL, _name).argtypes = _args
+    _EMUL = _lib.bind(ctypes.CDLL(build_emul.build()))
 except FileNotFoundError:  # no host compiler: the GPU tests still gate parity
     _EMUL = None
 
