@@ -5,12 +5,12 @@ import weakref
 import torch
 from torch import nn
 from torch.autograd import Function
-from . import _lib, grad_sink
+from . import _lib
 from ._lib import one_stream_query as _one_stream_query, ptr as _p, stream as _stream
 from . import cot_layer_fused as clf
 from .cot_layer_fused import (  # noqa: E402  (helpers; the switches are read as clf.NAME at call time: tests rebind them there)
-    BF16, NODE_COUNTS, _Side, _bn_bwd, _bn_fwd, _bn_static_ok, _conv3x3_dgrad, _conv3x3_fwd, _conv_ok,
-    _drop_path_scale, _guard_elems, _masks, _new_guarded, _relu_mask)
+    BF16, NODE_COUNTS, _Side, _bn_bwd, _bn_fwd, _bn_static_ok, _conv1_bwd, _conv1x1_bwd, _conv3x3_bwd, _conv3x3_fwd, _conv_ok,
+    _drop_path_scale, _masks, _new_guarded, _pack, _relu_mask, _shortcut_bwd, _shortcut_fwd, _unpack)
 
 # ---- SE-CoTNetD's OTHER block kind as one node: CoTBottleneck whose conv2 is SplitAttnConv2d(radix = 1) (models/cotnet_hybrid.py:
 # 138-146, :172-202; models/layers/split_attn.py:62-88) -- conv1 -> bn1+relu -> dense 3x3 -> bn0+act -> SE gate x * sigmoid(fc2(act(
@@ -22,7 +22,7 @@ from .cot_layer_fused import (  # noqa: E402  (helpers; the switches are read as
 # small-batch kernel.
 class _SABlockPlan:
     __slots__ = ("conv1", "bn1", "conv", "bn0", "fc1", "sbn", "fc2", "conv3", "bn3", "params", "static_ok", "act0", "act1",
-                 "ds_conv", "ds_bn", "ds_pool2", "avd_post")
+                 "ds_conv", "ds_bn", "ds_pool2", "ds_stride", "avd_post")
 
     def __init__(self, blk):
         from .layers import SplitAttnConv2d
@@ -41,7 +41,7 @@ class _SABlockPlan:
         from .layers import BlurPool2d
         ds, avd = blk.downsample, blk.avd
         self.ds_conv = self.ds_bn = None
-        self.ds_pool2 = False
+        self.ds_pool2, self.ds_stride = False, 1  # (the projection itself is always stride 1 here: _shortcut_fwd / _bwd)
         self.avd_post = (avd is not None and not getattr(blk, "avd_first", True) and isinstance(avd, BlurPool2d) and avd.filt_size == 3
                          and avd.stride == 2)
         shape_ok = ds is None and avd is None
@@ -143,25 +143,16 @@ class _SplitAttnBlockNode(Function):
         c3, y = new(Cout, Ho, Wo), new(Cout, Ho, Wo)
         L.cot_conv1x1_forward(_p(out2p), None, Cw, _p(sp.conv3.weight), None, _p(c3), N, Cw, Cout, HWo, BF16, st)
         if sp.ds_conv is not None:  # projection shortcut: bn(conv1x1([avgpool2x2](x)))
-            if sp.ds_pool2:
-                xs = new(Cin, Ho, Wo)
-                L.cot_avgpool2x2s2_forward(_p(x), _p(xs), N * Cin, H, W, BF16, st)
-            else:
-                xs = x
-            d0, res = new(Cout, Ho, Wo), new(Cout, Ho, Wo)
-            L.cot_conv1x1_forward(_p(xs), None, Cin, _p(sp.ds_conv.weight), None, _p(d0), N, Cin, Cout, HWo, BF16, st)
-            s_d = stat(Cout, nws_o)
-            _bn_fwd(L, d0, res, sp.ds_bn, s_d, 2 * Cout, N, Cout, HWo, 0)
+            xs, d0, res, s_d = _shortcut_fwd(L, sp, x, N, Cin, Cout, H, W, Ho, Wo, nws_o, epi=False)
         else:
             xs, d0, res, s_d = None, None, x, None
         s_3 = stat(Cout, nws_o)
         ps = _drop_path_scale(blk, N, dev)
         m3 = _relu_mask(L, N, Cout, HWo, dev)
         _bn_fwd(L, c3, y, sp.bn3, s_3, 2 * Cout, N, Cout, HWo, 1, residual=res, ps=ps, mask=m3)
-        ctx.blk, ctx.has_ps, ctx.has_mask = blk, ps is not None, m3 is not None
-        ctx.save_for_backward(x, c1, a1, s_1, c2, b2, s_0, gap, hpre, h, s_s, logits, out2, c3, y, s_3, out2p,
-                              *((d0, s_d, xs) if sp.ds_conv is not None else ()),
-                              *((m3,) if m3 is not None else ()), *((ps,) if ps is not None else ()))
+        ctx.blk = blk
+        _pack(ctx, dict(x=x, c1=c1, a1=a1, s_1=s_1, c2=c2, b2=b2, s_0=s_0, gap=gap, hpre=hpre, h=h, s_s=s_s, logits=logits, out2=out2,
+                        c3=c3, y=y, s_3=s_3, out2p=out2p, d0=d0, s_d=s_d, xs=xs, m3=m3, ps=ps))
         return y
 
     @staticmethod
@@ -170,12 +161,8 @@ class _SplitAttnBlockNode(Function):
         L = _lib.api()
         blk = ctx.blk
         sp = _sa_plan(blk)
-        t = ctx.saved_tensors
-        x, c1, a1, s_1, c2, b2, s_0, gap, hpre, h, s_s, logits, out2, c3, y, s_3, out2p = t[:17]
-        nds = 3 if sp.ds_conv is not None else 0
-        d0, s_d, xs = t[17:20] if nds else (None, None, None)
-        m3 = t[17 + nds] if ctx.has_mask else None
-        ps = t[-1] if ctx.has_ps else None
+        s = _unpack(ctx)
+        x, c1, a1, c2, b2, logits, out2, c3, y, out2p, m3 = s.x, s.c1, s.a1, s.c2, s.b2, s.logits, s.out2, s.c3, s.y, s.out2p, s.m3
         N, Cin, H, W = x.shape
         Cw, A, G = sp.conv.out_channels, sp.fc1.out_channels, sp.conv.groups
         Cout, Ho, Wo = y.shape[1], y.shape[2], y.shape[3]
@@ -188,11 +175,9 @@ class _SplitAttnBlockNode(Function):
         gout = gout.contiguous()
         fold = sp.ds_conv is None and m3 is not None and not sp.avd_post and clf._res_fold_ok(L, N, Cin, Cw, HW)
         g_c3, g_res = torch.empty_like(c3), (None if fold else torch.empty_like(c3))  # (fold: the residual's gradient goes into conv1's data gradient)
-        d_bn3_w, d_bn3_b = _bn_bwd(L, gout, c3, y, g_c3, sp.bn3, s_3, N, Cout, HWo, 1, nws_o, dres=g_res, ps=ps, mask=m3)
+        d_bn3_w, d_bn3_b = _bn_bwd(L, gout, c3, y, g_c3, sp.bn3, s.s_3, N, Cout, HWo, 1, nws_o, dres=g_res, ps=s.ps, mask=m3)
         g_out2p = torch.empty_like(out2p)
-        L.cot_conv1x1_backward_data(_p(g_c3), _p(sp.conv3.weight), _p(g_out2p), None, Cw, 0, _p(ws), N, Cw, Cout, HWo, BF16, st)
-        g_w3 = grad_sink.out_like(sp.conv3.weight)
-        side.run(lambda st_, a_=(_p(g_c3), _p(out2p), None, Cw, _p(g_w3), None, _p(side.ws), N, Cw, Cout, HWo, BF16): L.cot_conv1x1_backward_weight(*a_, st_), g_c3, out2p)
+        g_w3, _ = _conv1x1_bwd(L, side, ws, sp.conv3, g_c3, out2p, None, Cw, g_out2p, None, 0, N, Cw, Cout, HWo)
         if sp.avd_post:
             g_out2 = torch.empty_like(out2)
             L.cot_blurpool3x3s2_backward(_p(g_out2p), _p(g_out2), N * Cw, H, W, BF16, st)
@@ -204,45 +189,21 @@ class _SplitAttnBlockNode(Function):
         row = lambda c: torch.empty((c, N), dtype=x.dtype, device=dev)  # noqa: E731
         g_logT = g_log.t().contiguous()  # [Cw][N]
         g_h, g_hpre, g_gapT = row(A), row(A), row(Cw)
-        L.cot_conv1x1_backward_data(_p(g_logT), _p(sp.fc2.weight), _p(g_h), None, A, 0, _p(ws), 1, A, Cw, N, BF16, st)
-        g_fc2_w, g_fc2_b = grad_sink.out_like(sp.fc2.weight), grad_sink.out_like(sp.fc2.bias)
-        side.run(lambda st_, a_=(_p(g_logT), _p(h), None, A, _p(g_fc2_w), _p(g_fc2_b), _p(side.ws), 1, A, Cw, N, BF16): L.cot_conv1x1_backward_weight(*a_, st_), g_logT, h)
-        d_sbn_w, d_sbn_b = _bn_bwd(L, g_h, hpre, None, g_hpre, sp.sbn, s_s, 1, A, N, sp.act1, nws_a)
-        L.cot_conv1x1_backward_data(_p(g_hpre), _p(sp.fc1.weight), _p(g_gapT), None, Cw, 0, _p(ws), 1, Cw, A, N, BF16, st)
-        g_fc1_w, g_fc1_b = grad_sink.out_like(sp.fc1.weight), grad_sink.out_like(sp.fc1.bias)
-        side.run(lambda st_, a_=(_p(g_hpre), _p(gap), None, Cw, _p(g_fc1_w), _p(g_fc1_b), _p(side.ws), 1, Cw, A, N, BF16): L.cot_conv1x1_backward_weight(*a_, st_), g_hpre, gap)
+        g_fc2_w, g_fc2_b = _conv1x1_bwd(L, side, ws, sp.fc2, g_logT, s.h, None, A, g_h, None, 0, 1, A, Cw, N)
+        d_sbn_w, d_sbn_b = _bn_bwd(L, g_h, s.hpre, None, g_hpre, sp.sbn, s.s_s, 1, A, N, sp.act1, nws_a)
+        g_fc1_w, g_fc1_b = _conv1x1_bwd(L, side, ws, sp.fc1, g_hpre, s.gap, None, Cw, g_gapT, None, 0, 1, Cw, A, N)
         g_b2.add_((g_gapT.t().float() / HW).to(g_b2.dtype).reshape(N, Cw, 1, 1))  # d mean_hw: the same value for every pixel of a plane
         g_c2 = g_out2  # (reuse: consumed by the gate's backward)
-        d_bn0_w, d_bn0_b = _bn_bwd(L, g_b2, c2, None, g_c2, sp.bn0, s_0, N, Cw, HW, sp.act0, nws_w)
-        g_wc = grad_sink.out_like(sp.conv.weight)
-        side.run(lambda st_, a_=(_p(g_c2), _p(a1), _p(g_wc), _p(masks), _p(side.ws), N, Cw, Cw, G, H, W, BF16, _guard_elems(a1)): L.cot_conv3x3g_backward_weight_guarded(*a_, st_), g_c2, a1, masks)
+        d_bn0_w, d_bn0_b = _bn_bwd(L, g_b2, c2, None, g_c2, sp.bn0, s.s_0, N, Cw, HW, sp.act0, nws_w)
         g_a1 = g_b2  # (reuse: consumed by bn0's backward)
-        _conv3x3_dgrad(L, sp.conv, g_c2, g_a1, 0, masks, ws, N, Cw, G, H, W)
+        g_wc = _conv3x3_bwd(L, side, sp.conv, g_c2, a1, g_a1, 0, masks, ws, N, Cw, G, H, W)
         g_c1 = torch.empty_like(c1)
-        d_bn1_w, d_bn1_b = _bn_bwd(L, g_a1, c1, None, g_c1, sp.bn1, s_1, N, Cw, HW, 1, nws_w)
-        g_ds = ()
+        d_bn1_w, d_bn1_b = _bn_bwd(L, g_a1, c1, None, g_c1, sp.bn1, s.s_1, N, Cw, HW, 1, nws_w)
         if sp.ds_conv is not None:  # projection shortcut: BatchNorm, 1x1 convolution [, the 2 x 2 average] backwards -> first contribution to dx
-            g_d0 = torch.empty_like(g_c3) if side.on else g_c3  # (g_c3 is still read by conv3's weight gradient on the side stream)
-            d_ds_w, d_ds_b = _bn_bwd(L, g_res, d0, None, g_d0, sp.ds_bn, s_d, N, Cout, HWo, 0, nws_o)
-            g_xs = torch.empty_like(xs)
-            L.cot_conv1x1_backward_data(_p(g_d0), _p(sp.ds_conv.weight), _p(g_xs), None, Cin, 0, _p(ws), N, Cin, Cout, HWo, BF16, st)
-            if sp.ds_pool2:
-                gx = torch.empty_like(x)
-                L.cot_avgpool2x2s2_backward(_p(g_xs), _p(gx), N * Cin, H, W, BF16, st)
-            else:
-                gx = g_xs
-            g_wd = grad_sink.out_like(sp.ds_conv.weight)
-            side.run(lambda st_, a_=(_p(g_d0), _p(xs), None, Cin, _p(g_wd), None, _p(side.ws), N, Cin, Cout, HWo, BF16): L.cot_conv1x1_backward_weight(*a_, st_), g_d0, xs)
-            g_ds = (g_wd, d_ds_w, d_ds_b)
+            gx, g_ds = _shortcut_bwd(L, side, ws, sp, g_res, g_c3, s.d0, s.s_d, s.xs, x, N, Cin, Cout, H, W, HWo, nws_o)
         else:
-            gx = g_res  # identity shortcut: the residual's gradient is the first contribution to dx
-        g_w1 = grad_sink.out_like(sp.conv1.weight)
-        side.run(lambda st_, a_=(_p(g_c1), _p(x), None, Cin, _p(g_w1), None, _p(side.ws), N, Cin, Cw, HW, BF16): L.cot_conv1x1_backward_weight(*a_, st_), g_c1, x)
-        if fold:
-            gx = torch.empty_like(x)
-            L.cot_conv1x1_backward_data_relu_res(_p(g_c1), _p(sp.conv1.weight), _p(gx), _p(gout), _p(m3), N, Cin, Cw, HW, BF16, st)
-        else:
-            L.cot_conv1x1_backward_data(_p(g_c1), _p(sp.conv1.weight), _p(gx), None, Cin, 1, _p(ws), N, Cin, Cw, HW, BF16, st)
+            gx, g_ds = g_res, ()  # identity shortcut: the residual's gradient is the first contribution to dx (None: folded)
+        gx, g_w1 = _conv1_bwd(L, side, ws, sp.conv1, g_c1, x, gx, gout, m3, N, Cin, Cw, HW)
         side.join()
         return (None, gx, g_w1, d_bn1_w, d_bn1_b, g_wc, d_bn0_w, d_bn0_b, g_fc1_w, g_fc1_b, d_sbn_w, d_sbn_b, g_fc2_w, g_fc2_b, g_w3,
                 d_bn3_w, d_bn3_b) + g_ds

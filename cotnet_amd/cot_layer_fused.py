@@ -22,6 +22,7 @@ MI355X: ~1290 launches and 19.1 ms per step with every kernel from cotnet_amd/cs
 import ctypes
 import os
 import weakref
+from types import SimpleNamespace
 
 import torch
 from torch import nn
@@ -537,12 +538,12 @@ def _epi_ok(L, Ci, c1, two, HW):
     return v
 
 
-def _conv_bn_fwd(L, x1, x2, c1, conv, y_pre, y, bn, stats, nws_off, N, Ci, Co, HW, act, residual=None, ps=None, mask=None):
+def _conv_bn_fwd(L, x1, x2, c1, conv, y_pre, y, bn, stats, nws_off, N, Ci, Co, HW, act, residual=None, ps=None, mask=None, epi=True):
     """y_pre = conv1x1([x1 | x2]); y = act(bn(y_pre) [+ residual]) -- the models' conv -> BatchNorm pairs (models/cotnet.py:51-62,
-    :228-264).  stats: fp32 [2*Co + workspace] as for _bn_fwd."""
+    :228-264).  stats: fp32 [2*Co + workspace] as for _bn_fwd.  epi False: never the epilogue statistics (channel rows)"""
     st = _stream()
     bias = conv.bias
-    if BN_EPILOGUE and ps is None and _epi_ok(L, Ci, c1, x2 is not None, HW):
+    if epi and BN_EPILOGUE and ps is None and _epi_ok(L, Ci, c1, x2 is not None, HW):
         part = torch.empty(int(L.cot_gn9_stats_floats(N, Co, HW)), dtype=torch.float32, device=y.device)
         L.cot_conv1x1_forward_stats(_p(x1), _p(x2), c1, _p(conv.weight), _p(bias), _p(y_pre), _p(part), N, Ci, Co, HW, BF16, st)
         L.cot_bn_tile_stats_finalize(_p(part), _p(stats), _p(stats[Co:]), _p(bn.running_mean), _p(bn.running_var),
@@ -570,6 +571,107 @@ def _bn_bwd(L, dy, x, y, dx, bn, stats, N, C, HW, act, nws, dres=None, ps=None, 
     L.cot_bn_act_backward(_p(dy), _p(x), _p(y), _p(dx), _p(dres), _p(bn.weight), _p(bn.bias), _p(stats), _p(stats[C:]),
                           _p(dg), _p(db), _p(ws), N, C, HW, act, BF16, _stream())
     return dg, db
+
+
+# ---- per-tensor layouts (include/cotnet_amd.h, "per-tensor layouts for the deep stages"): the `lay` argument of the cot_*_lay /
+# cot_radix_*_bn entry points has one bit per plane tensor, set = that tensor is channel-major.  THE place that turns "which operands
+# are channel-major" into that integer: the call sites say it per operand, in the entry point's bit order --
+#     cot_bn_act_forward_lay   x, residual, y, y2             cot_bn_act_backward_lay      dy, dy2, x, y, dx, dresidual
+#     cot_radix_gap_t*         y (a), k                       cot_radix_mix_logits*        y (a), k, out
+#     cot_radix_mix_backward_reduce*  gout, y (a), k          cot_radix_mix_backward_apply*  gout, gy (a and ga), gk
+#     cot_group_norm9_forward_lay     x, y                    cot_group_norm9_backward_lay   dy, x, dx
+def _lay(*cm):
+    m = 0
+    for i, c in enumerate(cm):
+        if c:
+            m |= 1 << i
+    return m
+
+
+def _bn_fwd_lay(L, x, res, y, y2, bn, stats, N, C, HW, act, x_cm=False, res_cm=False, y_cm=False, y2_cm=False, ps=None):
+    L.cot_bn_act_forward_lay(_p(x), _p(res), _p(y), _p(y2), _p(bn.weight), _p(bn.bias), _p(stats), _p(stats[C:]),
+                             _p(bn.running_mean), _p(bn.running_var), _p(bn.num_batches_tracked), _p(ps), N, C, HW,
+                             float(bn.eps), float(bn.momentum), act, _lay(x_cm, res_cm, y_cm, y2_cm), BF16, _stream())
+
+
+def _bn_bwd_lay(L, dy, dy2, x, y, dx, dres, bn, stats, N, C, HW, act, dy_cm=False, dy2_cm=False, x_cm=False, y_cm=False, dx_cm=False,
+                dres_cm=False, ps=None):
+    dg, db = grad_sink.out_like(bn.weight), grad_sink.out_like(bn.bias)
+    L.cot_bn_act_backward_lay(_p(dy), _p(dy2), _p(x), _p(y), _p(dx), _p(dres), _p(bn.weight), _p(bn.bias), _p(stats), _p(stats[C:]),
+                              _p(dg), _p(db), _p(ps), N, C, HW, act, _lay(dy_cm, dy2_cm, x_cm, y_cm, dx_cm, dres_cm), BF16, _stream())
+    return dg, db
+
+
+# ---- the backward of a convolution: its data gradient on the compute stream, its weight (+ bias) gradient queued on the node's side
+# stream (_Side's rules above: what the queued launch reads is final when it is queued and is kept referenced until the join -- the
+# keep-alive list is derived from the operands here, once).  The pointer arguments are evaluated when the launch is QUEUED.
+def _conv1x1_wgrad(L, side, conv, gy, x1, x2, c1, N, Ci, Co, HW, groups=1, gw=None):
+    """queue d conv.weight (+ d conv.bias) of y = conv1x1([x1 | x2]) (c1: channels of x1; groups > 1: cot_conv1x1g_*, one slab) ->
+    (gw, gb): the parameters' slots in the flat gradient buckets (grad_sink), lent here.  gw given: written instead (no bias)"""
+    gb, keep = None, ((gy, x1) if x2 is None else (gy, x1, x2))
+    if gw is None:
+        gw = grad_sink.out_like(conv.weight)
+        if conv.bias is not None:
+            gb = grad_sink.out_like(conv.bias)
+    else:
+        keep += (gw,)
+    if groups == 1:
+        fn, a = L.cot_conv1x1_backward_weight, (_p(gy), _p(x1), _p(x2), c1, _p(gw), _p(gb), _p(side.ws), N, Ci, Co, HW, BF16)
+    else:
+        fn, a = L.cot_conv1x1g_backward_weight, (_p(gy), _p(x1), _p(gw), _p(gb), _p(side.ws), N, Ci, Co, groups, HW, BF16)
+    side.run(lambda st_: fn(*a, st_), *keep)
+    return gw, gb
+
+
+def _conv1x1_dgrad(L, w, gy, gx1, gx2, c1, accumulate, ws, N, Ci, Co, HW, groups=1):
+    """[gx1 | gx2] (+)= d / d[x1 | x2] of y = conv1x1([x1 | x2]; w); accumulate: bit 0 adds into gx1, bit 1 into gx2"""
+    if groups == 1:
+        L.cot_conv1x1_backward_data(_p(gy), _p(w), _p(gx1), _p(gx2), c1, accumulate, _p(ws), N, Ci, Co, HW, BF16, _stream())
+    else:
+        L.cot_conv1x1g_backward_data(_p(gy), _p(w), _p(gx1), accumulate, N, Ci, Co, groups, HW, BF16, _stream())
+
+
+def _conv1x1_bwd(L, side, ws, conv, gy, x1, x2, c1, gx1, gx2, accumulate, N, Ci, Co, HW, groups=1, wgrad_first=False, w=None, gw=None):
+    """both gradients of y = conv1x1([x1 | x2]) -> (gw, gb) as _conv1x1_wgrad.  (N, HW) = (1, N*HW) for channel-major operands.
+    wgrad_first: the weight gradient is queued before the data gradient is issued (conv1: the two overlap).  w / gw: a re-ordered
+    copy of the weight and the buffer for its gradient (the two-slab form of CoXtLayer.embed[0])"""
+    if wgrad_first:
+        g = _conv1x1_wgrad(L, side, conv, gy, x1, x2, c1, N, Ci, Co, HW, groups, gw)
+    _conv1x1_dgrad(L, conv.weight if w is None else w, gy, gx1, gx2, c1, accumulate, ws, N, Ci, Co, HW, groups)
+    if not wgrad_first:
+        g = _conv1x1_wgrad(L, side, conv, gy, x1, x2, c1, N, Ci, Co, HW, groups, gw)
+    return g
+
+
+def _conv3x3_bwd(L, side, conv, gy, x, gx, accumulate, masks, ws, N, C, G, H, W):
+    """the grouped 3x3: weight gradient queued (x carries margins: _new_guarded), then gx (+)= the data gradient -> gw"""
+    gw = grad_sink.out_like(conv.weight)
+    fn, a = L.cot_conv3x3g_backward_weight_guarded, (_p(gy), _p(x), _p(gw), _p(masks), _p(side.ws), N, C, C, G, H, W, BF16, _guard_elems(x))
+    side.run(lambda st_: fn(*a, st_), gy, x, masks)
+    _conv3x3_dgrad(L, conv, gy, gx, accumulate, masks, ws, N, C, G, H, W)
+    return gw
+
+
+def _gn9_wgrad(L, side, gn, gn_ws, N, C):
+    """GroupNorm-9's dgamma / dbeta out of the partial sums its data gradient left in gn_ws: a launch of their own, beside the weight gradients"""
+    gw, gb = grad_sink.out_like(gn.weight), grad_sink.out_like(gn.bias)
+    fn, a = L.cot_group_norm9_backward_params, (_p(gn_ws), _p(gw), _p(gb), N, C, BF16)
+    side.run(lambda st_: fn(*a, st_), gn_ws)
+    return gw, gb
+
+
+# ---- what a node keeps for its backward, by name.  Tensors go through ctx.save_for_backward (autograd's version checks); which names
+# were None is remembered on ctx, and the backward gets every name back.
+def _pack(ctx, saved):
+    ctx.saved_names = tuple(saved)
+    ctx.saved_present = present = tuple(n for n in saved if saved[n] is not None)
+    ctx.save_for_backward(*[saved[n] for n in present])
+
+
+def _unpack(ctx):
+    d = dict.fromkeys(ctx.saved_names)
+    d.update(zip(ctx.saved_present, ctx.saved_tensors))
+    return SimpleNamespace(**d)
 
 
 # ---- stochastic depth (models/cotnet.py:256-257; models/layers/drop.py:140-168: per sample, the block's branch is dropped with
@@ -612,79 +714,123 @@ def _drop_path_scale(blk, N, dev):
     return ps
 
 
-def _cot_forward(L, layer, x):
-    """the layer's forward on the library kernels -> (out, tensors to keep for backward, aggregation geometry)"""
+def _gx_slabs_ok(L, C, Ch, M):
+    """CoXtLayer.embed[0] as two two-slab 1x1 convolutions (one per group) on channel-major operands.  _cm_geometry_ok's C % 64 == 0 makes
+    every slab (C/2 rows of x or k, Ch/2 = C/4 output rows) 16-byte aligned with a reduction count the 1x1 kernels take; CoTNeXt's widths
+    (C = 384 / 768 at 14x14 / 7x7) land on the LDS kernels, narrower ones on the first-generation kernel"""
+    return GX_SLABS and C % 64 == 0 and Ch * 2 == C
+
+
+# ---- the CoT layer's launch sequence, stated once for both layouts.  `cm` None: every tensor NCHW (_CotLayerNode, _BottleneckNode).
+# `cm` given (_BottleneckCMNode, cot_block_cm.py): the operands of the 1x1 convolutions are dense channel-major buffers [C][N][H][W] and
+# those convolutions / their BatchNorm run on channel rows -- (N, HW) = (1, N*HW) --, the operands of the plane kernels (grouped 3x3,
+# aggregation) stay NCHW, and the layout changes inside the BatchNorm / GroupNorm / radix kernels between the two kinds (cot_*_lay).
+# What else the channel-major policy changes: no GroupNorm fusion (planes of at most 256 pixels), the two-slab embed[0] of a CoXtLayer
+# (_gx_slabs_ok), statistics buffers without a workspace where a _lay kernel writes them, the block's workspace instead of one of the
+# layer's own, and no buffer reuse backward (the gradients that meet are stored differently).
+def _cot_forward(L, layer, x, cm=None):
+    """the layer's forward on the library kernels -> (out, {name: tensor to keep for backward}, aggregation geometry).
+    x: the layer's input, NCHW (the grouped 3x3 reads it).  cm: (x's channel-major copy, the block's workspace, its 3x3 masks, BatchNorm
+    workspace floats for (N, C), (1, C/2) and the se branch) -- then `out` is channel-major too"""
     N, C, H, W = x.shape
     HW, Ch, Ce = H * W, C // 2, 9 * C // 8
     dev = x.device
     pl = _plan(layer)
-    A = pl.se0.out_channels
+    A, G = pl.se0.out_channels, pl.ke0.groups
     GX = pl.grouped
-    ws_bytes, nws_c, nws_h, nws_a = _sizes(L, N, C, H, W, A, pl.ke0.groups, GX)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    masks = _masks(L, H, W, dev)
+    if cm is None:
+        ws_bytes, nws_c, nws_h, nws_a = _sizes(L, N, C, H, W, A, G, GX)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        masks = _masks(L, H, W, dev)
+        x1, n1, hw1, nws_x = x, N, HW, nws_c
+    else:
+        x1, ws, masks, nws_c, nws_h, nws_a = cm
+        n1, hw1, nws_x = 1, N * HW, 0  # (1x1 convolutions on channel rows; the _lay BatchNorms need no workspace)
+    cm = cm is not None
     st = _stream()
     new = lambda c: torch.empty((N, c, H, W), dtype=x.dtype, device=dev)  # noqa: E731
+    new1 = (lambda c: torch.empty((c, N, H, W), dtype=x.dtype, device=dev)) if cm else new  # noqa: E731  (operands of the 1x1 convolutions)
     stat = lambda c, nws: torch.empty(2 * c + nws, dtype=torch.float32, device=dev)  # noqa: E731
 
     # static context k = relu(bn(conv3x3_grouped(x)))                                             (ref :80)
-    k_pre, k = new(C), new(C)
-    _conv3x3_fwd(L, pl.ke0, x, k_pre, masks, ws, N, C, pl.ke0.groups, H, W)
-    s_k = stat(C, nws_c)
-    _bn_fwd(L, k_pre, k, pl.ke1, s_k, 2 * C, N, C, HW, 1)
-    # attention logits from [x | k]                                                             (ref :81-85)
-    e0, e1 = new(Ch), new(Ch)
-    qk = None
-    if GX:  # CoXtLayer: [x0, k0, x1, k1, ...] so that each of the two groups sees matching halves of x and k (ref :153-154)
-        qk = torch.stack([x, k], dim=2).view(N, 2 * C, H, W)
-        L.cot_conv1x1g_forward(_p(qk), _p(pl.em0.weight), None, _p(e0), N, 2 * C, Ch, 2, HW, BF16, st)
-    s_e = stat(Ch, nws_h)
-    if GX:
-        _bn_fwd(L, e0, e1, pl.em1, s_e, 2 * Ch, N, Ch, HW, 1)
+    k_pre, k = new(C), new1(C)
+    _conv3x3_fwd(L, pl.ke0, x, k_pre, masks, ws, N, C, G, H, W)
+    s_k = stat(C, nws_x)
+    if cm:
+        _bn_fwd_lay(L, k_pre, None, k, None, pl.ke1, s_k, N, C, HW, 1, y_cm=True)
     else:
-        _conv_bn_fwd(L, x, k, C, pl.em0, e0, e1, pl.em1, s_e, 2 * Ch, N, 2 * C, Ch, HW, 1)
-    e3 = new(Ce)
+        _bn_fwd(L, k_pre, k, pl.ke1, s_k, 2 * C, N, C, HW, 1)
+    # attention logits from [x | k]                                                             (ref :81-85)
+    e0, e1 = new1(Ch), new1(Ch)
+    qk = None
+    s_e = stat(Ch, nws_h)
+    if GX and cm and _gx_slabs_ok(L, C, Ch, hw1):
+        # CoXtLayer's embed[0] reads the row-INTERLEAVED [x0, k0, x1, k1, ...] in two groups (ref :153-154): group g sees the rows
+        # g*C/2 .. of x and of k.  Channel-major, each of those is one contiguous slab, so a group is the two-slab 1x1 kernel on [x_g | k_g]
+        # with the group's weight columns de-interleaved to match -- a copy of the (small) weight per step instead of a copy of the
+        # activations (torch.stack: 2 C*M elements written and read) and, backward, two strided adds of C*M elements each
+        qk = pl.em0.weight.view(Ch, C // 2, 2).permute(0, 2, 1).reshape(Ch, C)  # [Ch][x-part C/2 | k-part C/2], a copy (kept for the backward)
+        Hc, Mg = C // 2, Ch // 2
+        for g_ in range(2):
+            L.cot_conv1x1_forward(_p(x1[g_ * Hc:]), _p(k[g_ * Hc:]), Hc, _p(qk[g_ * Mg:]), None, _p(e0[g_ * Mg:]), 1, C, Mg, hw1, BF16, st)
+        _bn_fwd(L, e0, e1, pl.em1, s_e, 2 * Ch, n1, Ch, hw1, 1)
+    elif GX:  # [x0, k0, x1, k1, ...] so that each of the two groups sees matching halves of x and k (ref :153-154)
+        qk = torch.stack([x1, k], dim=1).view(2 * C, N, H, W) if cm else torch.stack([x, k], dim=2).view(N, 2 * C, H, W)
+        L.cot_conv1x1g_forward(_p(qk), _p(pl.em0.weight), None, _p(e0), n1, 2 * C, Ch, 2, hw1, BF16, st)
+        _bn_fwd(L, e0, e1, pl.em1, s_e, 2 * Ch, n1, Ch, hw1, 1)
+    else:
+        _conv_bn_fwd(L, x1, k, C, pl.em0, e0, e1, pl.em1, s_e, 2 * Ch, n1, 2 * C, Ch, hw1, 1, epi=not cm)
+    e3 = new1(Ce)
     gn = pl.gn
     # GroupNorm of the logits fused into its neighbours (SURVEY 7.6): statistics out of embed[3]'s epilogue, normalisation in the
     # aggregation's prologue -- the normalised tensor `w` is never materialised (stages with planes of more than 256 pixels)
-    fused_gn = GN_FUSED and not GX and _gn_fused_ok(L, Ch, HW, W)
+    fused_gn = GN_FUSED and not GX and not cm and _gn_fused_ok(L, Ch, HW, W)
     if GX:
-        L.cot_conv1x1g_forward(_p(e1), _p(pl.em3.weight), _p(pl.em3.bias), _p(e3), N, Ch, Ce, 2, HW, BF16, st)
+        L.cot_conv1x1g_forward(_p(e1), _p(pl.em3.weight), _p(pl.em3.bias), _p(e3), n1, Ch, Ce, 2, hw1, BF16, st)
     elif fused_gn:
         part = torch.empty(int(L.cot_gn9_stats_floats(N, Ce, HW)), dtype=torch.float32, device=dev)
         L.cot_conv1x1_forward_gn9(_p(e1), None, Ch, _p(pl.em3.weight), _p(pl.em3.bias), _p(e3), _p(part), N, Ch, Ce, HW, BF16, st)
     else:
-        L.cot_conv1x1_forward(_p(e1), None, Ch, _p(pl.em3.weight), _p(pl.em3.bias), _p(e3), N, Ch, Ce, HW, BF16, st)
+        L.cot_conv1x1_forward(_p(e1), None, Ch, _p(pl.em3.weight), _p(pl.em3.bias), _p(e3), n1, Ch, Ce, hw1, BF16, st)
+    if fused_gn or HW <= 8192:
+        gn_mean = torch.empty(2 * N * gn.num_groups, dtype=torch.float32, device=dev)
+        gn_rstd = gn_mean[N * gn.num_groups:]
     if fused_gn:
         w = None
-        gn_mean = torch.empty(2 * N * gn.num_groups, dtype=torch.float32, device=dev)
-        gn_rstd = gn_mean[N * gn.num_groups:]
         L.cot_gn9_stats_finalize(_p(part), _p(gn_mean), _p(gn_rstd), N, Ce, HW, float(gn.eps), st)
+    elif cm:  # the logits channel-major in, the aggregation's weights NCHW out
+        w = new(Ce)
+        L.cot_group_norm9_forward_lay(_p(e3), _p(gn.weight), _p(gn.bias), _p(w), _p(gn_mean), _p(gn_rstd), N, Ce, HW, float(gn.eps),
+                                      _lay(True, False), BF16, st)
     elif HW <= 8192:  # one (image, group) fits a workgroup's registers: 1 read + 1 write (csrc/group_norm9.hip)
         w = new(Ce)
-        gn_mean = torch.empty(2 * N * gn.num_groups, dtype=torch.float32, device=dev)
-        gn_rstd = gn_mean[N * gn.num_groups:]
         L.cot_group_norm9_forward(_p(e3), _p(gn.weight), _p(gn.bias), _p(w), _p(gn_mean), _p(gn_rstd), N, Ce, HW,
                                   float(gn.eps), BF16, st)
     else:
         w, gn_mean, gn_rstd = torch.native_group_norm(e3, gn.weight, gn.bias, N, Ce, HW, gn.num_groups, gn.eps)
-    # values                                                                                     (ref :87)
-    v_pre, v = new(C), new(C)
+    # values; channel-major: 1x1 on channel rows, its BatchNorm writes NCHW                      (ref :87)
+    v_pre, v = new1(C), new(C)
+    s_v = stat(C, nws_x)
     if GX:
-        L.cot_conv1x1g_forward(_p(x), _p(pl.cv0.weight), None, _p(v_pre), N, C, C, 2, HW, BF16, st)
-    s_v = stat(C, nws_c)
-    if GX:
+        L.cot_conv1x1g_forward(_p(x1), _p(pl.cv0.weight), None, _p(v_pre), n1, C, C, 2, hw1, BF16, st)
+    elif cm:
+        L.cot_conv1x1_forward(_p(x1), None, C, _p(pl.cv0.weight), None, _p(v_pre), n1, C, C, hw1, BF16, st)
+    if cm:
+        _bn_fwd_lay(L, v_pre, None, v, None, pl.cv1, s_v, N, C, HW, 0, x_cm=True)
+    elif GX:
         _bn_fwd(L, v_pre, v, pl.cv1, s_v, 2 * C, N, C, HW, 0)
     else:
         _conv_bn_fwd(L, x, None, C, pl.cv0, v_pre, v, pl.cv1, s_v, 2 * C, N, C, C, HW, 0)
-    # local aggregation, bn + swish                                                              (ref :88-90)
+    # local aggregation, bn + swish (NCHW)                                                       (ref :88-90)
     # (CoXtLayer folds its two groups into the batch: [N, C] -> [2N, C/2], weights [2N, 1, C/16, 9]: views of the same memory)
     geom = _lib.AggGeom(2 * N, C // 2, H, W, 1, C // 16, 3, 3, 1, 1, 1, 1, 1, 1) if GX else \
         _lib.AggGeom(N, C, H, W, 1, C // 8, 3, 3, 1, 1, 1, 1, 1, 1)
-    a, y = new(C), (None if BN_TAIL else new(C))
+    bn_tail = BN_TAIL
+    a, y = new(C), (None if bn_tail else new(C))
     s_y = stat(C, nws_c)
     bnl = pl.bn
-    if BN_TAIL:  # (aggregation + the statistics of bn; bn + swish themselves happen inside the tail's kernels)
+    y_final = False
+    if bn_tail:  # (aggregation + the statistics of bn; bn + swish themselves happen inside the tail's kernels)
         y_final = _agg_fwd_stats(L, v, e3 if fused_gn else w, a, gn if fused_gn else None, gn_mean, gn_rstd, geom, bnl, s_y, N, C, H, W)
     else:
         if fused_gn:
@@ -693,56 +839,67 @@ def _cot_forward(L, layer, x):
         else:
             L.cot_agg_forward(_p(v), _p(w), _p(a), ctypes.byref(geom), BF16, _lib.COT_NCHW, st)
         _bn_fwd(L, a, y, bnl, s_y, 2 * C, N, C, HW, 2)
-    # radix-2 split attention                                                                    (ref :92-104)
+    # radix-2 split attention; channel-major: y NCHW, k channel-major, the mix written channel-major for conv3   (ref :92-104)
     # descriptors are kept channel-major ([C][N]) so that the se branch runs on the 1x1-convolution / BatchNorm
     # kernels with the batch as the pixel axis
     row = lambda c: torch.empty((c, N), dtype=x.dtype, device=dev)  # noqa: E731
     gapT, hpre, h, logitsT = row(C), row(A), row(A), row(2 * C)
-    if BN_TAIL:
-        _tail_gap(L, a, k, gapT, bnl, s_y, y_final, N, C, HW, 0)
+    if bn_tail:
+        _tail_gap(L, a, k, gapT, bnl, s_y, y_final, N, C, HW, _lay(False, cm))
+    elif cm:
+        L.cot_radix_gap_t_lay(_p(y), _p(k), _p(gapT), N, C, HW, _lay(False, True), BF16, st)
     else:
         L.cot_radix_gap_t(_p(y), _p(k), _p(gapT), N, C, HW, BF16, st)
     L.cot_conv1x1_forward(_p(gapT), None, C, _p(pl.se0.weight), _p(pl.se0.bias), _p(hpre), 1, C, A, N, BF16, st)
     s_a = stat(A, nws_a)
     _bn_fwd(L, hpre, h, pl.sebn, s_a, 2 * A, 1, A, N, 1)
-    L.cot_conv1x1_forward(_p(h), None, A, _p(pl.se3.weight), _p(pl.se3.bias), _p(logitsT), 1, A, 2 * C, N, BF16,
-                          st)
+    L.cot_conv1x1_forward(_p(h), None, A, _p(pl.se3.weight), _p(pl.se3.bias), _p(logitsT), 1, A, 2 * C, N, BF16, st)
     attn = torch.empty((N, C, 2), dtype=x.dtype, device=dev)
-    out = new(C)
-    if BN_TAIL:
+    out = new1(C)
+    if bn_tail:
         L.cot_radix_mix_logits_bn(_p(a), _p(k), _p(logitsT), _p(out), _p(attn), _p(bnl.weight), _p(bnl.bias), _p(s_y), _p(s_y[C:]),
-                                  N, C, HW, 0, BF16, st)
+                                  N, C, HW, _lay(False, cm, cm), BF16, st)
+    elif cm:
+        L.cot_radix_mix_logits_lay(_p(y), _p(k), _p(logitsT), _p(out), _p(attn), N, C, HW, _lay(False, True, True), BF16, st)
     else:
         L.cot_radix_mix_logits(_p(y), _p(k), _p(logitsT), _p(out), _p(attn), N, C, HW, BF16, st)
-
-    return out, (x, k_pre, k, e0, e1, e3, w, gn_mean, gn_rstd, v_pre, v, a, y, attn, s_k, s_e, s_v, s_y, gapT, hpre, h,
-                 s_a, qk), geom
-
-
-_N_SAVED = 23  # tensors _cot_forward hands back for the backward pass (the last one, qk, is None for a CotLayer)
+    return out, dict(x=x, xc=x1 if cm else None, k_pre=k_pre, k=k, e0=e0, e1=e1, e3=e3, w=w, gn_mean=gn_mean, gn_rstd=gn_rstd,
+                     v_pre=v_pre, v=v, a=a, y=y, attn=attn, s_k=s_k, s_e=s_e, s_v=s_v, s_y=s_y, gapT=gapT, hpre=hpre, h=h, s_a=s_a,
+                     qk=qk), geom
 
 
-def _cot_backward(L, layer, saved, geom, gout, side=None):
-    """-> (dx, gradients of _Plan.params in that order).  `side`: the caller's side stream for the weight gradients (a
-    Bottleneck node passes its own and joins it itself); None = this call opens and joins one."""
-    (x, k_pre, k, e0, e1, e3, w, gn_mean, gn_rstd, v_pre, v, a, y, attn, s_k, s_e, s_v, s_y, gapT, hpre, h,
-     s_a, qk) = saved
+def _cot_backward(L, layer, s, geom, gout, side=None, cm=None):
+    """-> (dx of the 1x1 convolutions' input, dx of the grouped 3x3's input, gradients of _Plan.params in that order).  NCHW: the two
+    are ONE tensor (summed inside the data-gradient kernels, `accumulate`); channel-major: a channel-major and an NCHW buffer, for the
+    caller to merge.  s: _cot_forward's tensors by name.  `side`: the caller's side stream for the weight gradients (a Bottleneck node
+    passes its own and joins it itself); None = this call opens and joins one.  cm: (the block's workspace, its 3x3 masks, BatchNorm
+    workspace floats as for _cot_forward); gout is then channel-major"""
+    x, k_pre, k, e0, e1, e3, v_pre, v, a, y, attn, qk = s.x, s.k_pre, s.k, s.e0, s.e1, s.e3, s.v_pre, s.v, s.a, s.y, s.attn, s.qk
+    gn_mean, gn_rstd, s_y = s.gn_mean, s.gn_rstd, s.s_y
     N, C, H, W = x.shape
     HW, Ch, Ce = H * W, C // 2, 9 * C // 8
     dev = x.device
     pl = _plan(layer)
-    A = pl.se0.out_channels
+    A, G = pl.se0.out_channels, pl.ke0.groups
     GX = pl.grouped
-    ws_bytes, nws_c, nws_h, nws_a = _sizes(L, N, C, H, W, A, pl.ke0.groups, GX)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    masks = _masks(L, H, W, dev)
+    if cm is None:
+        ws_bytes, nws_c, nws_h, nws_a = _sizes(L, N, C, H, W, A, G, GX)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        masks = _masks(L, H, W, dev)
+        x1, n1, hw1 = x, N, HW
+    else:
+        ws, masks, nws_c, nws_h, nws_a = cm
+        x1, n1, hw1 = s.xc, 1, N * HW
+    cm = cm is not None
+    g1 = 2 if GX else 1
     st = _stream()
     own_side = side is None
     if own_side:
         side = _Side(dev, ws_bytes, ws, pl.params)
     ke0, ke1, em0, em1, em3, cv0, cv1 = pl.ke0, pl.ke1, pl.em0, pl.em1, pl.em3, pl.cv0, pl.cv1
-    se0, sebn, se3 = pl.se0, pl.sebn, pl.se3
     gout = gout.contiguous()
+    new = lambda c: torch.empty((N, c, H, W), dtype=x.dtype, device=dev)  # noqa: E731
+    new1 = (lambda c: torch.empty((c, N, H, W), dtype=x.dtype, device=dev)) if cm else new  # noqa: E731
 
     # radix mix -> pair-softmax backward -> se branch (two 1x1 convolutions over the batch axis) -> gap
     row = lambda c: torch.empty((c, N), dtype=x.dtype, device=dev)  # noqa: E731
@@ -751,94 +908,101 @@ def _cot_backward(L, layer, saved, geom, gout, side=None):
     if y is None:  # (the forward folded bn + swish into the tail: so does the backward)
         tsum = torch.empty(N * C * 4, dtype=torch.float32, device=dev)
         L.cot_radix_mix_backward_reduce_bn(_p(gout), _p(a), _p(k), _p(attn), _p(glogT), _p(tsum), _p(bnl.weight), _p(bnl.bias),
-                                           _p(s_y), _p(s_y[C:]), N, C, HW, 0, BF16, st)
+                                           _p(s_y), _p(s_y[C:]), N, C, HW, _lay(cm, False, cm), BF16, st)
+    elif cm:
+        L.cot_radix_mix_backward_reduce_lay(_p(gout), _p(y), _p(k), _p(attn), _p(glogT), N, C, HW, _lay(True, False, True), BF16, st)
     else:
         L.cot_radix_mix_backward_reduce(_p(gout), _p(y), _p(k), _p(attn), _p(glogT), N, C, HW, BF16, st)
-    L.cot_conv1x1_backward_data(_p(glogT), _p(se3.weight), _p(gh), None, A, 0, _p(ws), 1, A, 2 * C, N, BF16, st)
-    g_w3, g_b3 = grad_sink.out_like(se3.weight), grad_sink.out_like(se3.bias)
-    side.run(lambda st_, a_=(_p(glogT), _p(h), None, A, _p(g_w3), _p(g_b3), _p(side.ws), 1, A, 2 * C, N, BF16): L.cot_conv1x1_backward_weight(*a_, st_), glogT, h)
+    g_w3, g_b3 = _conv1x1_bwd(L, side, ws, pl.se3, glogT, s.h, None, A, gh, None, 0, 1, A, 2 * C, N)
     ghpre = row(A)
-    d_sa_w, d_sa_b = _bn_bwd(L, gh, hpre, None, ghpre, sebn, s_a, 1, A, N, 1, nws_a)
-    L.cot_conv1x1_backward_data(_p(ghpre), _p(se0.weight), _p(ggapT), None, C, 0, _p(ws), 1, C, A, N, BF16, st)
-    g_w0, g_b0 = grad_sink.out_like(se0.weight), grad_sink.out_like(se0.bias)
-    side.run(lambda st_, a_=(_p(ghpre), _p(gapT), None, C, _p(g_w0), _p(g_b0), _p(side.ws), 1, C, A, N, BF16): L.cot_conv1x1_backward_weight(*a_, st_), ghpre, gapT)
-    # bn + swish, aggregation
-    ga, gk = torch.empty_like(a), torch.empty_like(k)
+    d_sa_w, d_sa_b = _bn_bwd(L, gh, s.hpre, None, ghpre, pl.sebn, s.s_a, 1, A, N, 1, nws_a)
+    g_w0, g_b0 = _conv1x1_bwd(L, side, ws, pl.se0, ghpre, s.gapT, None, C, ggapT, None, 0, 1, C, A, N)
+    # bn + swish, aggregation (NCHW)
+    ga, gk = new(C), new1(C)
     if y is None:
         d_bn_w, d_bn_b = grad_sink.out_like(bnl.weight), grad_sink.out_like(bnl.bias)
         L.cot_radix_mix_backward_apply_bn(_p(gout), _p(a), _p(attn), _p(ggapT), _p(tsum), _p(ga), _p(gk), _p(bnl.weight), _p(bnl.bias),
-                                          _p(s_y), _p(s_y[C:]), _p(d_bn_w), _p(d_bn_b), N, C, HW, 0, BF16, st)
+                                          _p(s_y), _p(s_y[C:]), _p(d_bn_w), _p(d_bn_b), N, C, HW, _lay(cm, False, cm), BF16, st)
     else:
-        gy = torch.empty_like(y)
-        L.cot_radix_mix_backward_apply(_p(gout), _p(attn), _p(ggapT), _p(gy), _p(gk), N, C, HW, BF16, st)
+        gy = new(C)
+        if cm:
+            L.cot_radix_mix_backward_apply_lay(_p(gout), _p(attn), _p(ggapT), _p(gy), _p(gk), N, C, HW, _lay(True, False, True), BF16, st)
+        else:
+            L.cot_radix_mix_backward_apply(_p(gout), _p(attn), _p(ggapT), _p(gy), _p(gk), N, C, HW, BF16, st)
         d_bn_w, d_bn_b = _bn_bwd(L, gy, a, None, ga, bnl, s_y, N, C, HW, 2, nws_c)
-    gv, gw = torch.empty_like(v), torch.empty_like(e3)
-    if w is None:  # (the forward normalised the logits inside the aggregation: so does the backward; gw = d / d normalised weights)
-        gn_ = pl.gn
-        L.cot_agg_gn9_backward(_p(ga), _p(v), _p(e3), _p(gn_mean), _p(gn_rstd), _p(gn_.weight), _p(gn_.bias), gn_.num_groups,
+    gv, gw = new(C), new(Ce)
+    gn = pl.gn
+    if s.w is None:  # (the forward normalised the logits inside the aggregation: so does the backward; gw = d / d normalised weights)
+        L.cot_agg_gn9_backward(_p(ga), _p(v), _p(e3), _p(gn_mean), _p(gn_rstd), _p(gn.weight), _p(gn.bias), gn.num_groups,
                                _p(gv), _p(gw), ctypes.byref(geom), BF16, st)
     else:
-        L.cot_agg_backward(_p(ga), _p(v), _p(w), _p(gv), _p(gw), ctypes.byref(geom), BF16, _lib.COT_NCHW, st)
-    # values branch: bn, conv1x1 -> first contribution to dx
-    gv_pre = ga  # (reuse: ga is dead)
-    d_cv_w, d_cv_b = _bn_bwd(L, gv, v_pre, None, gv_pre, cv1, s_v, N, C, HW, 0, nws_c)
-    gx = torch.empty_like(x)
-    g_wv = grad_sink.out_like(cv0.weight)
-    if GX:
-        L.cot_conv1x1g_backward_data(_p(gv_pre), _p(cv0.weight), _p(gx), 0, N, C, C, 2, HW, BF16, st)
-        side.run(lambda st_, a_=(_p(gv_pre), _p(x), _p(g_wv), None, _p(side.ws), N, C, C, 2, HW, BF16): L.cot_conv1x1g_backward_weight(*a_, st_), gv_pre, x)
+        L.cot_agg_backward(_p(ga), _p(v), _p(s.w), _p(gv), _p(gw), ctypes.byref(geom), BF16, _lib.COT_NCHW, st)
+    # values branch: bn, conv1x1 -> first contribution to dx (channel-major: NCHW gradient in, channel-major out)
+    if cm:
+        gv_pre = new1(C)
+        d_cv_w, d_cv_b = _bn_bwd_lay(L, gv, None, v_pre, None, gv_pre, None, cv1, s.s_v, N, C, HW, 0, x_cm=True, dx_cm=True)
     else:
-        L.cot_conv1x1_backward_data(_p(gv_pre), _p(cv0.weight), _p(gx), None, C, 0, _p(ws), N, C, C, HW, BF16, st)
-        side.run(lambda st_, a_=(_p(gv_pre), _p(x), None, C, _p(g_wv), None, _p(side.ws), N, C, C, HW, BF16): L.cot_conv1x1_backward_weight(*a_, st_), gv_pre, x)
+        gv_pre = ga  # (reuse: ga is dead)
+        d_cv_w, d_cv_b = _bn_bwd(L, gv, v_pre, None, gv_pre, cv1, s.s_v, N, C, HW, 0, nws_c)
+    gx1 = new1(C)
+    g_wv, _ = _conv1x1_bwd(L, side, ws, cv0, gv_pre, x1, None, C, gx1, None, 0, n1, C, C, hw1, g1)
     # logits branch: GroupNorm, conv1x1(+bias), bn+relu, conv1x1 on [x | k] -> dx +=, dk +=
-    gn = pl.gn
     if HW <= 8192:
-        ge3, g_gn_w, g_gn_b = torch.empty_like(e3), grad_sink.out_like(gn.weight), grad_sink.out_like(gn.bias)
+        ge3 = new1(Ce)
         gn_ws = torch.empty(2 * N * Ce, dtype=torch.float32, device=dev)
         # (dx here; dgamma / dbeta -- a launch of their own -- beside the weight gradients)
-        L.cot_group_norm9_backward(_p(gw), _p(e3), _p(gn_mean), _p(gn_rstd), _p(gn.weight), _p(ge3), None, None, _p(gn_ws), N, Ce, HW,
-                                   BF16, st)
-        side.run(lambda st_, a_=(_p(gn_ws), _p(g_gn_w), _p(g_gn_b), N, Ce, BF16): L.cot_group_norm9_backward_params(*a_, st_), gn_ws)
+        if cm:  # NCHW gradient in, channel-major out
+            L.cot_group_norm9_backward_lay(_p(gw), _p(e3), _p(gn_mean), _p(gn_rstd), _p(gn.weight), _p(ge3), None, None, _p(gn_ws),
+                                           N, Ce, HW, _lay(False, True, True), BF16, st)
+        else:
+            L.cot_group_norm9_backward(_p(gw), _p(e3), _p(gn_mean), _p(gn_rstd), _p(gn.weight), _p(ge3), None, None, _p(gn_ws), N, Ce, HW,
+                                       BF16, st)
+        g_gn_w, g_gn_b = _gn9_wgrad(L, side, gn, gn_ws, N, Ce)
     else:
         ge3, g_gn_w, g_gn_b = torch.ops.aten.native_group_norm_backward(
             gw, e3, gn_mean, gn_rstd, gn.weight, N, Ce, HW, gn.num_groups, [True, True, True])
         ge3 = ge3.contiguous()
-    ge1 = torch.empty_like(e1)
-    g_we3, g_be3 = grad_sink.out_like(em3.weight), grad_sink.out_like(em3.bias)
-    if GX:
-        L.cot_conv1x1g_backward_data(_p(ge3), _p(em3.weight), _p(ge1), 0, N, Ch, Ce, 2, HW, BF16, st)
-        side.run(lambda st_, a_=(_p(ge3), _p(e1), _p(g_we3), _p(g_be3), _p(side.ws), N, Ch, Ce, 2, HW, BF16): L.cot_conv1x1g_backward_weight(*a_, st_), ge3, e1)
-    else:
-        L.cot_conv1x1_backward_data(_p(ge3), _p(em3.weight), _p(ge1), None, Ch, 0, _p(ws), N, Ch, Ce, HW, BF16,
-                                    st)
-        side.run(lambda st_, a_=(_p(ge3), _p(e1), None, Ch, _p(g_we3), _p(g_be3), _p(side.ws), N, Ch, Ce, HW, BF16): L.cot_conv1x1_backward_weight(*a_, st_), ge3, e1)
-    ge0 = torch.empty_like(e0)
-    d_em_w, d_em_b = _bn_bwd(L, ge1, e0, None, ge0, em1, s_e, N, Ch, HW, 1, nws_h)  # (ReLU mask recomputed from e0)
-    g_we0 = grad_sink.out_like(em0.weight)
-    if GX:  # gradient of the interleaved [x0, k0, x1, k1, ...]: de-interleaved into dx / dk (two strided adds)
+    ge1 = new1(Ch)
+    g_we3, g_be3 = _conv1x1_bwd(L, side, ws, em3, ge3, e1, None, Ch, ge1, None, 0, n1, Ch, Ce, hw1, g1)
+    ge0 = new1(Ch)
+    d_em_w, d_em_b = _bn_bwd(L, ge1, e0, None, ge0, em1, s.s_e, n1, Ch, hw1, 1, nws_h)  # (ReLU mask recomputed from e0)
+    if GX and qk.dim() == 2:  # (the forward took the two-slab form: qk holds the de-interleaved weight)
+        Hc, Mg = C // 2, Ch // 2
+        g_we0 = grad_sink.out_like(em0.weight)
+        gwp = torch.empty_like(qk)  # gradient w.r.t. the de-interleaved weight, re-interleaved into the parameter's slot below
+        for g_ in range(2):
+            _conv1x1_bwd(L, side, ws, em0, ge0[g_ * Mg:], x1[g_ * Hc:], k[g_ * Hc:], Hc, gx1[g_ * Hc:], gk[g_ * Hc:], 3, 1, C, Mg, hw1,
+                         w=qk[g_ * Mg:], gw=gwp[g_ * Mg:])
+
+        def _interleave(st_, dst=g_we0, src=gwp, side_=side):  # [Ch][2][C/2] -> [Ch][C/2][2], behind the two launches above on their stream
+            if side_.on:
+                with torch.cuda.stream(side_.stream):
+                    dst.view(Ch, C // 2, 2).copy_(src.view(Ch, 2, C // 2).permute(0, 2, 1))
+            else:
+                dst.view(Ch, C // 2, 2).copy_(src.view(Ch, 2, C // 2).permute(0, 2, 1))
+        side.run(_interleave, gwp)
+    elif GX:  # gradient of the interleaved [x0, k0, x1, k1, ...]: de-interleaved into dx / dk (two strided adds)
         gqk = torch.empty_like(qk)
-        L.cot_conv1x1g_backward_data(_p(ge0), _p(em0.weight), _p(gqk), 0, N, 2 * C, Ch, 2, HW, BF16, st)
-        gq5 = gqk.view(N, C, 2, H, W)
-        gx.add_(gq5[:, :, 0])
-        gk.add_(gq5[:, :, 1])
-        side.run(lambda st_, a_=(_p(ge0), _p(qk), _p(g_we0), None, _p(side.ws), N, 2 * C, Ch, 2, HW, BF16): L.cot_conv1x1g_backward_weight(*a_, st_), ge0, qk)
+        _conv1x1_dgrad(L, em0.weight, ge0, gqk, None, 2 * C, 0, ws, n1, 2 * C, Ch, hw1, 2)
+        gq5, d = (gqk.view(C, 2, N, H, W), 1) if cm else (gqk.view(N, C, 2, H, W), 2)
+        gx1.add_(gq5.select(d, 0))
+        gk.add_(gq5.select(d, 1))
+        g_we0, _ = _conv1x1_wgrad(L, side, em0, ge0, qk, None, 2 * C, n1, 2 * C, Ch, hw1, 2)
     else:
-        L.cot_conv1x1_backward_data(_p(ge0), _p(em0.weight), _p(gx), _p(gk), C, 3, _p(ws), N, 2 * C, Ch, HW, BF16,
-                                    st)
-        side.run(lambda st_, a_=(_p(ge0), _p(x), _p(k), C, _p(g_we0), None, _p(side.ws), N, 2 * C, Ch, HW, BF16): L.cot_conv1x1_backward_weight(*a_, st_), ge0, x, k)
-    # key branch: bn+relu, grouped 3x3 -> dx +=
-    gk_pre = gv  # (reuse: gv is dead)
-    d_ke_w, d_ke_b = _bn_bwd(L, gk, k_pre, None, gk_pre, ke1, s_k, N, C, HW, 1, nws_c)
-    G = ke0.groups
-    g_wk = grad_sink.out_like(ke0.weight)
-    side.run(lambda st_, a_=(_p(gk_pre), _p(x), _p(g_wk), _p(masks), _p(side.ws), N, C, C, G, H, W, BF16,
-                                               _guard_elems(x)): L.cot_conv3x3g_backward_weight_guarded(*a_, st_), gk_pre, x, masks)
-    _conv3x3_dgrad(L, ke0, gk_pre, gx, 1, masks, ws, N, C, G, H, W)
+        g_we0, _ = _conv1x1_bwd(L, side, ws, em0, ge0, x1, k, C, gx1, gk, 3, n1, 2 * C, Ch, hw1)
+    # key branch: bn+relu, grouped 3x3 -> dx += (channel-major: channel-major gradient in, NCHW out: the NCHW contribution to dx)
+    if cm:
+        gk_pre, gx3 = new(C), new(C)
+        d_ke_w, d_ke_b = _bn_bwd_lay(L, gk, None, k_pre, None, gk_pre, None, ke1, s.s_k, N, C, HW, 1, dy_cm=True)
+    else:
+        gk_pre, gx3 = gv, gx1  # (reuse: gv is dead)
+        d_ke_w, d_ke_b = _bn_bwd(L, gk, k_pre, None, gk_pre, ke1, s.s_k, N, C, HW, 1, nws_c)
+    g_wk = _conv3x3_bwd(L, side, ke0, gk_pre, x, gx3, 0 if cm else 1, masks, ws, N, C, G, H, W)
     if own_side:
         side.join()
     # order = _Plan.params
-    return gx, (g_wk, d_ke_w, d_ke_b, g_we0, d_em_w, d_em_b, g_we3, g_be3, g_gn_w, g_gn_b, g_wv, d_cv_w, d_cv_b,
-                d_bn_w, d_bn_b, g_w0, g_b0, d_sa_w, d_sa_b, g_w3, g_b3)
+    return gx1, gx3, (g_wk, d_ke_w, d_ke_b, g_we0, d_em_w, d_em_b, g_we3, g_be3, g_gn_w, g_gn_b, g_wv, d_cv_w, d_cv_b,
+                      d_bn_w, d_bn_b, g_w0, g_b0, d_sa_w, d_sa_b, g_w3, g_b3)
 
 
 class _CotLayerNode(Function):
@@ -848,13 +1012,13 @@ class _CotLayerNode(Function):
         # params (_Plan.params) are only here so that autograd routes their gradients; values are read off `layer`
         out, saved, geom = _cot_forward(_lib.api(), layer, x)
         ctx.layer, ctx.geom = layer, geom
-        ctx.save_for_backward(*saved)
+        _pack(ctx, saved)
         return out
 
     @staticmethod
     @_one_stream_query
     def backward(ctx, gout):
-        gx, gparams = _cot_backward(_lib.api(), ctx.layer, ctx.saved_tensors, ctx.geom, gout)
+        gx, _, gparams = _cot_backward(_lib.api(), ctx.layer, _unpack(ctx), ctx.geom, gout)
         return (None, gx) + gparams
 
 
@@ -969,6 +1133,59 @@ def _block_sizes(L, N, Cin, Cw, Cout, HW):
     return v
 
 
+# ---- the pieces every block node shares: the projection shortcut (`p`: a block plan with ds_conv, ds_bn, ds_pool2, ds_stride) and conv1's backward
+def _shortcut_fwd(L, p, x, N, Cin, Cout, H, W, Ho, Wo, nws_o, epi=True):
+    """res = bn(conv1x1(x')), x' = x, its 2 x 2 averages (`avg_down`) or every second pixel of it (stride 2) -> (x', conv output, res, statistics)"""
+    dev, st = x.device, _stream()
+    if p.ds_pool2:  # `avg_down`: 2 x 2 average pooling, then the stride-1 projection
+        xs = torch.empty((N, Cin, H // 2, W // 2), dtype=x.dtype, device=dev)
+        L.cot_avgpool2x2s2_forward(_p(x), _p(xs), N * Cin, H, W, BF16, st)
+    elif p.ds_stride == 2 and H % 2 == 0 and W % 2 == 0:  # every second pixel: one pass, 16-byte accesses (pool3x3.hip)
+        xs = torch.empty((N, Cin, H // 2, W // 2), dtype=x.dtype, device=dev)
+        L.cot_subsample2_forward(_p(x), _p(xs), N * Cin, H, W, BF16, st)
+    else:
+        xs = x[:, :, ::2, ::2].contiguous() if p.ds_stride == 2 else x
+    d0, res = (torch.empty((N, Cout, Ho, Wo), dtype=x.dtype, device=dev) for _ in range(2))
+    s_d = torch.empty(2 * Cout + nws_o, dtype=torch.float32, device=dev)
+    _conv_bn_fwd(L, xs, None, Cin, p.ds_conv, d0, res, p.ds_bn, s_d, 2 * Cout, N, Cin, Cout, Ho * Wo, 0, epi=epi)
+    return xs, d0, res, s_d
+
+
+def _shortcut_bwd(L, side, ws, p, g_res, g_c3, d0, s_d, xs, x, N, Cin, Cout, H, W, HWo, nws_o):
+    """BatchNorm, 1x1 convolution [, pooling / sub-sampling] backwards -> (the first contribution to dx, (d weight, d gamma, d beta))"""
+    st = _stream()
+    # (g_c3 is still being read by conv3's weight gradient on the side stream: no reuse of its buffer then)
+    g_d0 = torch.empty_like(g_c3) if side.on else g_c3
+    d_ds_w, d_ds_b = _bn_bwd(L, g_res, d0, None, g_d0, p.ds_bn, s_d, N, Cout, HWo, 0, nws_o)
+    gx = torch.zeros_like(x) if (p.ds_stride == 2 and (H % 2 or W % 2)) else torch.empty_like(x)
+    if p.ds_pool2 or p.ds_stride == 2:
+        g_xs = torch.empty_like(xs)
+        _conv1x1_dgrad(L, p.ds_conv.weight, g_d0, g_xs, None, Cin, 0, ws, N, Cin, Cout, HWo)
+        if p.ds_pool2:  # the projection saw 2 x 2 averages: its data gradient is spread over the four pixels of each window
+            L.cot_avgpool2x2s2_backward(_p(g_xs), _p(gx), N * Cin, H, W, BF16, st)
+        elif H % 2 == 0 and W % 2 == 0:  # it saw every second pixel: values back in place and the zeros around them in one pass
+            L.cot_subsample2_backward(_p(g_xs), _p(gx), N * Cin, H, W, BF16, st)
+        else:
+            gx[:, :, ::2, ::2] = g_xs
+    else:
+        _conv1x1_dgrad(L, p.ds_conv.weight, g_d0, gx, None, Cin, 0, ws, N, Cin, Cout, HWo)
+    g_wd, _ = _conv1x1_wgrad(L, side, p.ds_conv, g_d0, xs, None, Cin, N, Cin, Cout, HWo)
+    return gx, (g_wd, d_ds_w, d_ds_b)
+
+
+def _conv1_bwd(L, side, ws, conv, g_c1, x, gx, gout, m3, N, Cin, Cw, HW):
+    """conv1's backward, the weight gradient queued before the data gradient is issued (the two overlap).  gx += the data gradient; gx
+    None (identity shortcut, COT_RES_FOLD): the residual's gradient gout * [block output > 0] was never written and is formed in the
+    data gradient's epilogue from gout and bn3's sign mask m3.  -> (dx, d weight)"""
+    g_w1, _ = _conv1x1_wgrad(L, side, conv, g_c1, x, None, Cin, N, Cin, Cw, HW)
+    if gx is None:
+        gx = torch.empty_like(x)
+        L.cot_conv1x1_backward_data_relu_res(_p(g_c1), _p(conv.weight), _p(gx), _p(gout), _p(m3), N, Cin, Cw, HW, BF16, _stream())
+    else:
+        _conv1x1_dgrad(L, conv.weight, g_c1, gx, None, Cin, 1, ws, N, Cin, Cw, HW)
+    return gx, g_w1
+
+
 class _BottleneckNode(Function):
     @staticmethod
     @_one_stream_query
@@ -1000,27 +1217,15 @@ class _BottleneckNode(Function):
             L.cot_blurpool3x3s2_forward(_p(cot_full), _p(cot_out), N * Cw, H, W, BF16, st)
         c3, y = new(Cout, Ho, Wo), new(Cout, Ho, Wo)
         if bp.ds_conv is not None:  # projection shortcut: bn(conv1x1(x)), on every second pixel in a stride-2 block
-            if bp.ds_pool2:  # `avg_down`: 2 x 2 average pooling, then the stride-1 projection
-                xs = torch.empty((N, Cin, H // 2, W // 2), dtype=x.dtype, device=dev)
-                L.cot_avgpool2x2s2_forward(_p(x), _p(xs), N * Cin, H, W, BF16, st)
-            elif bp.ds_stride == 2 and H % 2 == 0 and W % 2 == 0:  # every second pixel: one pass, 16-byte accesses (pool3x3.hip)
-                xs = torch.empty((N, Cin, H // 2, W // 2), dtype=x.dtype, device=dev)
-                L.cot_subsample2_forward(_p(x), _p(xs), N * Cin, H, W, BF16, st)
-            else:
-                xs = x[:, :, ::2, ::2].contiguous() if bp.ds_stride == 2 else x
-            d0, res = new(Cout, Ho, Wo), new(Cout, Ho, Wo)
-            s_d = stat(Cout, nws_o)
-            _conv_bn_fwd(L, xs, None, Cin, bp.ds_conv, d0, res, bp.ds_bn, s_d, 2 * Cout, N, Cin, Cout, HWo, 0)
+            xs, d0, res, s_d = _shortcut_fwd(L, bp, x, N, Cin, Cout, H, W, Ho, Wo, nws_o)
         else:
             xs, d0, res, s_d = None, None, x, None
         s_3 = stat(Cout, nws_o)
         ps = _drop_path_scale(blk, N, dev)  # stochastic depth: per-sample 0 or 1 / keep on the normalised branch
         m3 = _relu_mask(L, N, Cout, HWo, dev)
         _conv_bn_fwd(L, cot_out, None, Cw, bp.conv3, c3, y, bp.bn3, s_3, 2 * Cout, N, Cw, Cout, HWo, 1, residual=res, ps=ps, mask=m3)
-        ctx.blk, ctx.geom, ctx.has_ds, ctx.has_ps, ctx.has_mask = blk, geom, bp.ds_conv is not None, ps is not None, m3 is not None
-        extra = (x, c1, a1, s_1, cot_out, c3, y, s_3) + ((d0, s_d, xs) if bp.ds_conv is not None else ()) + \
-            ((m3,) if m3 is not None else ()) + ((ps,) if ps is not None else ())
-        ctx.save_for_backward(*(saved + extra))
+        ctx.blk, ctx.geom = blk, geom
+        _pack(ctx, dict(saved, x_in=x, c1=c1, a1=a1, s_1=s_1, cot_out=cot_out, c3=c3, y_out=y, s_3=s_3, d0=d0, s_d=s_d, xs=xs, m3=m3, ps=ps))
         return y
 
     @staticmethod
@@ -1029,9 +1234,8 @@ class _BottleneckNode(Function):
         L = _lib.api()
         blk = ctx.blk
         bp = _block_plan(blk)
-        t = ctx.saved_tensors
-        saved, extra = t[:_N_SAVED], t[_N_SAVED:]
-        x, c1, a1, s_1, cot_out, c3, y, s_3 = extra[:8]
+        s = _unpack(ctx)
+        x, c1, a1, cot_out, c3, y, m3 = s.x_in, s.c1, s.a1, s.cot_out, s.c3, s.y_out, s.m3
         N, Cin, H, W = x.shape
         Cw, Cout = bp.conv1.out_channels, bp.conv3.out_channels
         Ho, Wo = y.shape[2], y.shape[3]
@@ -1040,30 +1244,25 @@ class _BottleneckNode(Function):
         ws_a, nws_w, _ = _block_sizes(L, N, Cin, Cw, Cout, HW)
         ws_b, _, nws_o = _block_sizes(L, N, Cin, Cw, Cout, HWo)
         ws = torch.empty(max(ws_a, ws_b), dtype=torch.uint8, device=dev)
-        cN, cC, cH, cW = saved[0].shape
+        cN, cC, cH, cW = s.x.shape
         cpl = _plan(bp.cot)
         side = _Side(dev, max(ws_a, ws_b, _sizes(L, cN, cC, cH, cW, cpl.se0.out_channels, cpl.ke0.groups, cpl.grouped)[0]), ws,
                      bp.params)
         gout = gout.contiguous()
         # bn3 + residual + relu: dx of the normalisation and the residual's gradient in one pass
-        ps = extra[-1] if ctx.has_ps else None
-        m3 = extra[-2 if ctx.has_ps else -1] if ctx.has_mask else None
         # identity shortcut with a sign mask: the residual's gradient is folded into conv1's data gradient below, never written
-        fold = (not ctx.has_ds) and m3 is not None and not bp.avd and _res_fold_ok(L, N, Cin, Cw, HW)
+        fold = s.d0 is None and m3 is not None and not bp.avd and _res_fold_ok(L, N, Cin, Cw, HW)
         g_c3, g_res = torch.empty_like(c3), (None if fold else torch.empty_like(c3))
-        d_bn3_w, d_bn3_b = _bn_bwd(L, gout, c3, y, g_c3, bp.bn3, s_3, N, Cout, HWo, 1, nws_o, dres=g_res, ps=ps, mask=m3)
+        d_bn3_w, d_bn3_b = _bn_bwd(L, gout, c3, y, g_c3, bp.bn3, s.s_3, N, Cout, HWo, 1, nws_o, dres=g_res, ps=s.ps, mask=m3)
         g_cot_out = torch.empty_like(cot_out)
-        L.cot_conv1x1_backward_data(_p(g_c3), _p(bp.conv3.weight), _p(g_cot_out), None, Cw, 0, _p(ws), N, Cw, Cout, HWo,
-                                    BF16, st)
-        g_w3 = grad_sink.out_like(bp.conv3.weight)
-        side.run(lambda st_, a_=(_p(g_c3), _p(cot_out), None, Cw, _p(g_w3), None, _p(side.ws), N, Cw, Cout, HWo, BF16): L.cot_conv1x1_backward_weight(*a_, st_), g_c3, cot_out)
+        g_w3, _ = _conv1x1_bwd(L, side, ws, bp.conv3, g_c3, cot_out, None, Cw, g_cot_out, None, 0, N, Cw, Cout, HWo)
         if bp.avd_post:  # (cot_out at the output resolution was the pooled tensor: its gradient goes back through the blur)
             g_full = torch.empty((N, Cw, H, W), dtype=x.dtype, device=dev)
             L.cot_blurpool3x3s2_backward(_p(g_cot_out), _p(g_full), N * Cw, H, W, BF16, st)
             g_layer_out = g_full
         else:
             g_layer_out = g_cot_out
-        g_p1, g_cot = _cot_backward(L, bp.cot, saved, ctx.geom, g_layer_out, side)
+        g_p1, _, g_cot = _cot_backward(L, bp.cot, s, ctx.geom, g_layer_out, side)
         if bp.avd:
             g_a1 = torch.empty_like(a1)
             L.cot_avgpool3x3s2_backward(_p(g_p1), _p(g_a1), N * Cw, H, W, BF16, st)
@@ -1071,46 +1270,12 @@ class _BottleneckNode(Function):
         else:
             g_a1 = g_p1
             g_c1 = g_layer_out  # (reuse: consumed by the layer's backward)
-        d_bn1_w, d_bn1_b = _bn_bwd(L, g_a1, c1, None, g_c1, bp.bn1, s_1, N, Cw, HW, 1, nws_w)
-        g_ds = ()
-        if ctx.has_ds:
-            d0, s_d, xs = extra[8], extra[9], extra[10]
-            # (g_c3 is still being read by conv3's weight gradient on the side stream: no reuse of its buffer here)
-            g_d0 = torch.empty_like(g_c3) if side.on else g_c3
-            d_ds_w, d_ds_b = _bn_bwd(L, g_res, d0, None, g_d0, bp.ds_bn, s_d, N, Cout, HWo, 0, nws_o)
-            if bp.ds_pool2:  # the projection saw 2 x 2 averages: its data gradient is spread over the four pixels of each window
-                g_xs = torch.empty_like(xs)
-                L.cot_conv1x1_backward_data(_p(g_d0), _p(bp.ds_conv.weight), _p(g_xs), None, Cin, 0, _p(ws), N, Cin,
-                                            Cout, HWo, BF16, st)
-                gx = torch.empty_like(x)
-                L.cot_avgpool2x2s2_backward(_p(g_xs), _p(gx), N * Cin, H, W, BF16, st)
-            elif bp.ds_stride == 2:  # the projection saw every second pixel: its data gradient lands there, zeros elsewhere
-                g_xs = torch.empty_like(xs)
-                L.cot_conv1x1_backward_data(_p(g_d0), _p(bp.ds_conv.weight), _p(g_xs), None, Cin, 0, _p(ws), N, Cin,
-                                            Cout, HWo, BF16, st)
-                if H % 2 == 0 and W % 2 == 0:  # values back in place and the zeros around them in one pass
-                    gx = torch.empty_like(x)
-                    L.cot_subsample2_backward(_p(g_xs), _p(gx), N * Cin, H, W, BF16, st)
-                else:
-                    gx = torch.zeros_like(x)
-                    gx[:, :, ::2, ::2] = g_xs
-            else:
-                gx = torch.empty_like(x)
-                L.cot_conv1x1_backward_data(_p(g_d0), _p(bp.ds_conv.weight), _p(gx), None, Cin, 0, _p(ws), N, Cin,
-                                            Cout, HWo, BF16, st)
-            g_wd = grad_sink.out_like(bp.ds_conv.weight)
-            side.run(lambda st_, a_=(_p(g_d0), _p(xs), None, Cin, _p(g_wd), None, _p(side.ws), N, Cin, Cout, HWo, BF16): L.cot_conv1x1_backward_weight(*a_, st_), g_d0, xs)
-            g_ds = (g_wd, d_ds_w, d_ds_b)
+        d_bn1_w, d_bn1_b = _bn_bwd(L, g_a1, c1, None, g_c1, bp.bn1, s.s_1, N, Cw, HW, 1, nws_w)
+        if s.d0 is not None:
+            gx, g_ds = _shortcut_bwd(L, side, ws, bp, g_res, g_c3, s.d0, s.s_d, s.xs, x, N, Cin, Cout, H, W, HWo, nws_o)
         else:
-            gx = g_res  # identity shortcut: the residual's gradient is the first contribution to dx
-        g_w1 = grad_sink.out_like(bp.conv1.weight)  # (issued before its data gradient: the two overlap)
-        side.run(lambda st_, a_=(_p(g_c1), _p(x), None, Cin, _p(g_w1), None, _p(side.ws), N, Cin, Cw, HW, BF16): L.cot_conv1x1_backward_weight(*a_, st_), g_c1, x)
-        if fold:
-            gx = torch.empty_like(x)
-            L.cot_conv1x1_backward_data_relu_res(_p(g_c1), _p(bp.conv1.weight), _p(gx), _p(gout), _p(m3), N, Cin, Cw, HW, BF16, st)
-        else:
-            L.cot_conv1x1_backward_data(_p(g_c1), _p(bp.conv1.weight), _p(gx), None, Cin, 1, _p(ws), N, Cin, Cw, HW, BF16,
-                                        st)
+            gx, g_ds = g_res, ()  # identity shortcut: the residual's gradient is the first contribution to dx (None: folded)
+        gx, g_w1 = _conv1_bwd(L, side, ws, bp.conv1, g_c1, x, gx, gout, m3, N, Cin, Cw, HW)
         side.join()
         return (None, gx, g_w1, d_bn1_w, d_bn1_b) + g_cot + (g_w3, d_bn3_w, d_bn3_b) + g_ds
 
@@ -1141,9 +1306,9 @@ def block_forward(blk, x):
 # the wrappers, bench.py and the tests have always used.  The channel-major switches are attributes of THIS module (tests rebind them).
 CM_LAYOUT = os.environ.get("COT_CM_LAYOUT", "1") != "0"
 CM_OPENING = os.environ.get("COT_CM_OPENING", "1") != "0"  # the stage's stride-2 opening block on the channel-major node too (A/B switch)
-GX_SLABS = os.environ.get("COT_GX_SLABS", "1") != "0"  # CoXtLayer.embed[0] in channel-major blocks: two-slab kernels per group instead of torch.stack (cot_block_cm.py)
+GX_SLABS = os.environ.get("COT_GX_SLABS", "1") != "0"  # CoXtLayer.embed[0] in channel-major blocks: two-slab kernels per group instead of torch.stack (_cot_forward)
 from .cot_block_sa import (_SABlockPlan, _SA_PLANS, _SASIZES, _sa_plan, _sa_sizes, _SplitAttnBlockNode, sa_block_eligible,  # noqa: E402,F401
                            sa_block_forward)
-from .cot_block_cm import (_CM_OK, _CM_SIZES, _BottleneckCMNode, _bn_bwd_lay, _bn_fwd_lay, _cm_buf, _cm_geometry_ok, _cm_sizes,  # noqa: E402,F401
-                           _cm_static_ok, _cm_view, _is_cm, cm_block_eligible, cm_block_forward, plan_stage_layouts)
+from .cot_block_cm import (_CM_OK, _CM_SIZES, _BottleneckCMNode, _cm_buf, _cm_geometry_ok, _cm_sizes, _cm_static_ok, _cm_view,  # noqa: E402,F401
+                           _is_cm, cm_block_eligible, cm_block_forward, plan_stage_layouts)
 from .cot_block_eval import _bn_inf, eval_block_eligible, eval_block_forward  # noqa: E402,F401
