@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""tests/test_fuzz_gpu.py's loop for many seeds on the device: python scripts/fuzz_gpu.py [--seeds 40] [--count 100] [--first 7000]
+"""tests/test_fuzz_gpu.py's loop for many seeds on the device: python scripts/fuzz_gpu.py [--seeds 40] [--count 100] [--first 7000] [--cases CASES_LR]
 Prints the failing case descriptions (none expected) and the number of cases per kind."""
 import argparse
 import os
@@ -17,6 +17,7 @@ def main():
     ap.add_argument("--first", type=int, default=7000)
     ap.add_argument("--seconds", type=float, default=0, help="stop starting new seeds after this many seconds (0: no limit)")
     ap.add_argument("--scale", type=int, default=1, help="plane sizes of the convolution cases times this (tests.test_fuzz_emulated.SCALE)")
+    ap.add_argument("--cases", default="", help="a case list of tests.test_fuzz_emulated by name (CASES_LR: the local-relation kernels); default: run_cases' pool")
     a = ap.parse_args()
     t0, total, bad, kinds = time.time(), 0, [], {}
     with device_fuzz() as tfe:
@@ -25,7 +26,7 @@ def main():
             if a.seconds and time.time() - t0 > a.seconds:
                 break
             try:
-                failures, k = run_cases(tfe, seed, a.count)
+                failures, k = run_cases(tfe, seed, a.count, cases=getattr(tfe, a.cases) if a.cases else None)
             except Exception as e:  # an assertion inside a case (a non-zero return code): report the seed and go on
                 failures, k = [("EXCEPTION", seed, repr(e)[:300])], {}
             total += a.count

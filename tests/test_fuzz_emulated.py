@@ -647,6 +647,178 @@ def case_optimizer_and_input(rng):
     return ok and torch.equal(y, ref), ("input normalise", shape, str(dtype))
 
 
+# ---- the local-relation kernels (local_relation.hip) against a plain fp64 statement of the operation: rectangular planes, every loader
+# width (W odd / W % 4 == 2 / W % 4 == 0), single-row tiles (W > 128) up to and beyond the LDS boundary, ragged last tiles, both backward routes
+def lr_reference64(q, k, v, pos, gout, terms=False):
+    """fp64, from unfold and einsum (the semantics in the header of local_relation.hip), differentiated by autograd:
+        logit[n,g,t,p] = sum_{j<8} q[n,8g+j,p] (uk[n,8g+j,t,p] + pos[8g+j,t])   uk = 0 outside the image: a padded tap keeps q * pos
+        out[n,c,p]     = sum_t softmax_t(logit)[n, c mod G, t, p] v[n,c,p + off_t]
+    -> (out, gq, gk, gv, gpos[C][9]); with `terms` also, for the bounds on bf16 gk (gL = d loss / d logit, gA = d loss / d a):
+        S[n,c,p'] = sum_t |gL_t q| at p' - off_t                                   the magnitudes of the products gk[n,c,p'] sums
+        R[n,c,p'] = sum_t |q| (2 |gL_t| + a_t sum_u a_u |gA_u|) at p' - off_t      what a relative error of 1 in every a_u moves them by"""
+    N, C, H, W = q.shape
+    G = C // 8
+    q, k, v, pos = (t.detach().double().requires_grad_(True) for t in (q, k, v, pos))
+    uk = F.unfold(k, 3, 1, 1, 1).view(N, G, 8, 9, H, W)
+    logit = torch.einsum("ngjhw,ngjthw->ngthw", q.view(N, G, 8, H, W), uk + pos.view(1, G, 8, 9, 1, 1))
+    logit.retain_grad()
+    a = torch.softmax(logit, 2)
+    a.retain_grad()
+    uv = F.unfold(v, 3, 1, 1, 1).view(N, 8, G, 9, H, W)  # channel c = g + j G takes head g = c mod G
+    out = torch.einsum("ngthw,njgthw->njghw", a, uv).reshape(N, C, H, W)
+    out.backward(gout.double())
+    res = (out.detach(), q.grad, k.grad, v.grad, pos.grad)
+    if terms:
+        gather = lambda x: F.fold(x.reshape(N, C * 9, H * W), (H, W), 3, 1, 1, 1)  # noqa: E731  (the term at p lands on p + off_t)
+        aq = q.detach().abs().view(N, G, 8, 1, H, W)
+        gl, ad = logit.grad.abs(), a.detach()
+        moved = 2 * gl + ad * (ad * a.grad.abs()).sum(2, keepdim=True)
+        res += (gather(gl.view(N, G, 1, 9, H, W) * aq), gather(moved.view(N, G, 1, 9, H, W) * aq))
+    return res
+
+
+def lr_tolerances(dtype):
+    """(name -> factor) on `tol (1 + |want|)` per element, tests/test_lrnet_emulated.py::test_forward_and_all_gradients_match_the_composition"""
+    return (2e-5 if dtype == torch.float32 else 4e-2), {"out": 1, "gv": 1, "gq": 4, "gk": 4}
+
+
+def lr_mismatches(got, want, dtype, skip=()):
+    """names of the outputs (out, gq, gk, gv, gpos) that are not finite or off the fp64 reference; gpos against its own scale"""
+    tol, factor = lr_tolerances(dtype)
+    bad = []
+    for name, g, w in zip(("out", "gq", "gk", "gv"), got, want):
+        if not torch.isfinite(g).all().item():
+            bad.append((name, "not finite"))
+        elif name not in skip:
+            err = (g.double() - w).abs()
+            if not (err <= factor[name] * tol * (1 + w.abs())).all().item():
+                bad.append((name, err.max().item()))
+    g, w = got[4], want[4]
+    err = (g.double() - w).abs().max().item()
+    if not torch.isfinite(g).all().item() or not err <= 4 * tol * max(1.0, w.abs().max().item()):
+        bad.append(("gpos", err))
+    return bad
+
+
+def lr_gk_ratio(gk, want, S):
+    """bf16 gk under a saturated softmax: the error beyond the output rounding 2^-9 |want|, in units of 2^-8 S (S from lr_reference64:
+    the magnitudes of the products the element sums)"""
+    over = ((gk.double() - want).abs() - 2.0 ** -9 * want.abs()).clamp_min(0)
+    return (over / (2.0 ** -8 * S).clamp_min(1e-300)).max().item()
+
+
+def lr_gk_rounding_ratio(gk, want, R):
+    """the same error in units of 2^-8 R + LR_GK_FLOOR.  The forward rounds each probability to bf16 once (a_u (1 + e_u), |e_u| <= 2^-8, the
+    unit roundoff of 8 significant bits) and the backward stores gL_t = a_t (gA_t - sum_u a_u gA_u) in bf16, so to first order gL_t moves
+    by at most 2^-8 (2 |gL_t| + a_t sum_u a_u |gA_u|).  The second term does not shrink with gL_t, which is why a saturated softmax
+    (gL_t -> 0) leaves gk errors far above 2^-8 S.  The floor: a gL_t or a gk below the smallest normal number (1.2e-38) is flushed
+    to zero, a relative error of 1 that no multiple of R covers; 9 such products with |q| of a few tens stay far below 1e-30."""
+    over = ((gk.double() - want).abs() - 2.0 ** -9 * want.abs()).clamp_min(0)
+    return (over / (2.0 ** -8 * R + LR_GK_FLOOR)).max().item()
+
+
+LR_GK_FLOOR = 1e-30
+
+
+def _margins_untouched(view):
+    """`view` came from _nan_margined: everything around it in its allocation is still NaN"""
+    flat, lo = view._base, view.storage_offset()
+    return flat[:lo].isnan().all().item() and flat[lo + view.numel():].isnan().all().item()
+
+
+def lr_geom(N, C, H, W):
+    return tke._lib.AggGeom(N, C, H, W, 1, C // 8, 3, 3, 1, 1, 1, 1, 1, 1)
+
+
+def lr_run(q, k, v, gout, pos, null_probs=False, margin=None):
+    """forward + backward through the C ABI of `E`: q / k / v / gout / probs inside NaN margins, NaN-filled outputs inside NaN margins that
+    must stay NaN (wide enough for a whole tile, at most 256 pixels, written past the end of the last plane: the row guard of a ragged last
+    tile), the workspace at exactly the reported size, 0x7f-filled, with a guard behind it.  Every pointer is 16-byte aligned, which the C ABI
+    requires (tests/test_lrnet_emulated.py::test_misaligned_pointers_are_refused) -> ((out, gq, gk, gv, gpos), probs, first backward kernel)"""
+    N, C, H, W = q.shape
+    g, dt = lr_geom(N, C, H, W), tke._lib.dtype_code(q.dtype)
+    margin = W + 1 if margin is None else margin
+    q, k, v, gout = (_nan_margined(t, margin) for t in (q, k, v, gout))
+    nan = lambda *shape: torch.full(shape, float("nan"), dtype=q.dtype)  # noqa: E731
+    plane = lambda: _nan_margined(nan(N, C, H, W), 256 + W + 1)  # noqa: E731
+    probs, out = _nan_margined(nan(N, 1, C // 8, 9, H, W), 256 + W + 1), plane()
+    assert E.cot_local_relation_forward(P(q), P(k), P(v), P(pos), P(out), P(probs), ctypes.byref(g), dt, None) == 0, E.cot_last_error()
+    if null_probs:  # the branch that stores no probabilities: the same bits in out
+        out2 = plane()
+        assert E.cot_local_relation_forward(P(q), P(k), P(v), P(pos), P(out2), None, ctypes.byref(g), dt, None) == 0, E.cot_last_error()
+        assert torch.isfinite(out).all().item() and torch.equal(out, out2), "probs == NULL changes out"
+        assert _margins_untouched(out2), "write outside out (probs == NULL)"
+    nb = int(E.cot_local_relation_workspace_bytes(ctypes.byref(g), dt))
+    assert nb > 0, nb
+    buf = torch.full((nb + 256,), 0x7f, dtype=torch.uint8)
+    gq, gk, gv, gpos = plane(), plane(), plane(), torch.full((C, 9), float("nan"), dtype=torch.float32)
+    rc = E.cot_local_relation_backward(P(gout), P(q), P(k), P(v), P(pos), P(probs), P(gq), P(gk), P(gv), P(gpos), P(buf[:nb]),
+                                       ctypes.byref(g), dt, None)
+    assert rc == 0, E.cot_last_error()
+    route = E.cot_last_kernel().decode().split("+")[0]
+    assert (buf[nb:] == 0x7f).all().item(), "write past the reported workspace size"
+    for name, t in (("out", out), ("probs", probs), ("gq", gq), ("gk", gk), ("gv", gv)):
+        assert _margins_untouched(t), f"write outside {name}"
+    return (out, gq, gk, gv, gpos), probs, route
+
+
+# 1; odd (the V = 1 loader); W % 4 == 2 (V = 2); W % 4 == 0 (V = 4); the model's 28 / 56; one row per tile (W > 128) up to the widest
+# width that fits LDS (211); two beyond it
+LR_WIDTHS = [1, 3, 5, 7, 9, 13, 21, 2, 6, 10, 14, 30, 4, 8, 12, 16, 20, 28, 56, 100, 129, 130, 132, 171, 200, 211, 214, 260]
+
+
+def case_local_relation(rng):
+    N, C, H, W = rng.randint(1, 3), 8 * rng.choice([1, 2, 3, 5, 8, 16]), rng.randint(1, 28), rng.choice(LR_WIDTHS)
+    if N * C * W > 60000:
+        N = 1
+    H = max(1, min(H, 60000 // (N * C * W)))  # one case stays fast on the emulator
+    dtype = rng.choice([torch.float32, torch.bfloat16])
+    qs, null_probs, margin = rng.choice([0.5, 2]), rng.random() < 0.25, W + 1 + rng.randint(0, 9)
+    g, dt = lr_geom(N, C, H, W), tke._lib.dtype_code(dtype)
+    desc = ("local relation", N, C, H, W, str(dtype), qs, null_probs)
+    if E.cot_local_relation_workspace_bytes(ctypes.byref(g), dt) == -2:
+        fake = ctypes.c_void_p(0x1000)  # never dereferenced: the coverage check comes first
+        ok = E.cot_local_relation_forward(*([fake] * 6), ctypes.byref(g), dt, None) == -2
+        ok = ok and E.cot_local_relation_backward(*([fake] * 11), ctypes.byref(g), dt, None) == -2
+        return ok, ("local relation: refused",) + desc[1:]
+    q, k, v, gout = (torch.randn(N, C, H, W) for _ in range(4))
+    q, k, v, gout = (qs * q).to(dtype), (0.5 * k).to(dtype), v.to(dtype), gout.to(dtype)
+    pos = (torch.randn(C, 3, 1) + torch.randn(C, 1, 3)).reshape(C, 9).contiguous()
+    try:
+        got, _, route = lr_run(q, k, v, gout, pos, null_probs, margin)
+    except AssertionError as e:
+        return False, desc + (str(e)[:200],)
+    bad = lr_mismatches(got, lr_reference64(q, k, v, pos, gout), dtype)
+    return not bad, desc + (route,) + tuple(bad)
+
+
+CASES_LR = [case_local_relation]
+
+
+def lr_check_kinds(descs):
+    """the two conditions that keep the case from hiding a failure: few refusals, both backward routes well represented"""
+    refused = [d for d in descs if d[0].endswith("refused")]
+    accepted = [d for d in descs if not d[0].endswith("refused")]
+    assert len(refused) <= 0.15 * len(descs), (len(refused), len(descs))
+    for route in ("lr_softmax_bwd", "agg_bwd_nchw_k3_lds<softmax>"):
+        n = sum(1 for d in accepted if route in d)
+        assert n >= 0.2 * len(accepted), (route, n, len(accepted))
+
+
+@pytest.mark.parametrize("seed", [71, 72])
+def test_random_shapes_local_relation(seed):
+    rng = random.Random(seed)
+    torch.manual_seed(seed)
+    failures, descs = [], []
+    for _ in range(120):
+        ok, desc = case_local_relation(rng)
+        descs.append(desc)
+        if not ok:
+            failures.append(desc)
+    assert not failures, failures
+    lr_check_kinds(descs)
+
+
 CASES = [case_conv1x1, case_conv1x1, case_conv3x3, case_conv3x3_guarded, case_group_norm, case_pooling, case_subsample]
 CASES_R4 = [case_conv3x3_lds, case_conv3x3_lds, case_bn, case_bn, case_stem, case_pool2, case_conv1x1_stages, case_agg_gn9, case_bn_ps, case_aggregation, case_aggregation, case_conv_general, case_conv_general, case_elementwise, case_optimizer_and_input]
 

@@ -65,7 +65,7 @@ def device_fuzz():
             dev.cot_set_tuning(k, v)
 
 
-def run_cases(tfe, seed, count, cases=None):
+def run_cases(tfe, seed, count, cases=None, descs=None):
     rng = random.Random(seed)
     torch.manual_seed(seed)
     cases = cases or (tfe.CASES + tfe.CASES_R4 + tfe.CASES_R6 + tfe.CASES_R6B)
@@ -75,6 +75,8 @@ def run_cases(tfe, seed, count, cases=None):
         ok, desc = fn(rng)
         torch.cuda.synchronize()
         kinds[fn.__name__] = kinds.get(fn.__name__, 0) + 1
+        if descs is not None:
+            descs.append(desc)
         if not ok:
             failures.append(desc)
     return failures, kinds
@@ -85,3 +87,14 @@ def test_random_shapes_on_the_device(seed):
     with device_fuzz() as tfe:
         failures, _ = run_cases(tfe, seed, 60)
     assert not failures, failures
+
+
+@pytest.mark.parametrize("seed", [701, 702])
+def test_random_local_relation_on_the_device(seed):
+    """case_local_relation (local_relation.hip against the fp64 statement of the operation) through the real LDS tiles and wave
+    butterflies; not part of the default pool, so the draws of the seeds above stay what they are"""
+    descs = []
+    with device_fuzz() as tfe:
+        failures, _ = run_cases(tfe, seed, 200, cases=tfe.CASES_LR, descs=descs)
+        assert not failures, failures
+        tfe.lr_check_kinds(descs)

@@ -224,3 +224,114 @@ def test_graph_capture_of_forward_and_backward_replays_equal_to_eager():
     torch.cuda.synchronize()
     for a, b in zip(captured, eager):
         assert torch.equal(a, b)
+
+
+# ---- the directed edges of tests/test_lrnet_emulated.py on the device (same functions, the device library in the emulator's place), then
+# the Python wrapper off the happy path; checker: lr_reference64 (fp64 from unfold and einsum, no code shared with the product)
+from tests import test_lrnet_emulated as tle  # noqa: E402
+from tests.test_fuzz_gpu import device_fuzz  # noqa: E402
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_lds_boundary_on_the_device(dtype):
+    with device_fuzz():
+        tle.lds_boundary_case(dtype)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("H,W", tle.RAGGED)
+def test_rectangular_and_ragged_tiles_on_the_device(H, W, dtype):
+    with device_fuzz():
+        tle.lr_directed(2, 24, H, W, dtype, seed=H + W)
+
+
+def test_both_backward_routes_by_name_on_the_device():
+    with device_fuzz():
+        tle.backward_routes_case()
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("H,W", [(9, 30), (5, 100), (7, 7), (2, 150)])
+def test_saturated_softmax_on_the_device(H, W, dtype):
+    with device_fuzz():
+        tle.saturated_case(dtype, H, W)
+
+
+def _view(kind, base):
+    """a [2, 24, H, W] view of `base` that the kernels cannot take as it is (differentiable: the gradient flows back to `base`)"""
+    if kind == "channel_slice":  # base [2, 40, 6, 10]
+        return base[:, 8:32]
+    if kind == "transposed":     # base [2, 24, 10, 6]
+        return base.transpose(2, 3)
+    if kind == "offset":         # base [2, 24, 5, 12] (the four-element loader after the wrapper's copy): one element into a storage of its own
+        return torch.cat([base.new_zeros(1), base.reshape(-1)])[1:].view(base.shape)
+    return base                  # rectangular, [2, 24, 5, 100]
+
+
+_BASE = {"channel_slice": (2, 40, 6, 10), "transposed": (2, 24, 10, 6), "offset": (2, 24, 5, 12), "rectangular": (2, 24, 5, 100)}
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("kind", list(_BASE))
+def test_wrapper_views_and_bf16_positions(kind, dtype, fused_calls):
+    from tests import test_fuzz_emulated as tfe
+    g = torch.Generator(device=DEV).manual_seed(17)
+    bases = [(f * torch.randn(_BASE[kind], device=DEV, generator=g)).to(dtype).requires_grad_(True) for f in (0.5, 0.5, 1)]
+    q, k, v = (_view(kind, b) for b in bases)
+    if kind == "offset":
+        assert q.data_ptr() % 16 != 0
+    elif kind != "rectangular":
+        assert not q.is_contiguous()
+    gout = torch.randn(q.shape, device=DEV, generator=g).to(dtype)
+    pos_dt = torch.bfloat16 if dtype == torch.bfloat16 else torch.float32
+    pha, pwa = (torch.randn(s, device=DEV, generator=g).to(pos_dt).requires_grad_(True) for s in ((24, 3, 1), (24, 1, 3)))
+    y = local_relation(q, k, v, pha, pwa, 3)
+    assert _lib.last_kernel() == "lr_fwd"
+    y.backward(gout)
+    torch.cuda.synchronize()
+    assert fused_calls == {"fused": 1, "other": 0}
+    assert pha.grad.dtype == pos_dt and pwa.grad.dtype == pos_dt
+    pos = (pha.detach() + pwa.detach()).float().reshape(24, 9)  # (the sum is formed in the parameters' type, as the wrapper forms it)
+    r_y, r_gq, r_gk, r_gv, r_gpos = tfe.lr_reference64(q, k, v, pos, gout)
+    r_gq, r_gk, r_gv = torch.autograd.grad((q, k, v), bases, (r_gq.to(dtype), r_gk.to(dtype), r_gv.to(dtype)))  # back through the views
+    tol = 2e-5 if dtype == torch.float32 else 4e-2
+    for name, got, want, f in (("y", y, r_y, 1), ("gv", bases[2].grad, r_gv, 1), ("gq", bases[0].grad, r_gq, 4), ("gk", bases[1].grad, r_gk, 4)):
+        assert torch.isfinite(got).all(), name
+        err = (got.detach().double() - want.double()).abs()
+        assert (err <= f * tol * (1 + want.double().abs())).all(), (name, err.max().item())
+    r_gpos = r_gpos.view(24, 3, 3)
+    for name, gr, w in (("pos_h", pha.grad, r_gpos.sum(2, keepdim=True)), ("pos_w", pwa.grad, r_gpos.sum(1, keepdim=True))):
+        assert (gr.double() - w).abs().max().item() <= 4 * tol * max(1.0, w.abs().max().item()), name
+
+
+def test_width_past_the_lds_boundary_takes_the_composition(fused_calls):
+    g = torch.Generator(device=DEV).manual_seed(19)
+    q, k, v = ((f * torch.randn(1, 8, 2, 212, device=DEV, generator=g)).bfloat16().requires_grad_(True) for f in (0.5, 0.5, 1))
+    pos_h, pos_w = torch.randn(8, 3, 1, device=DEV, generator=g), torch.randn(8, 1, 3, device=DEV, generator=g)
+    before = _lib.FALLBACKS.get("local_relation", 0)
+    y = local_relation(q, k, v, pos_h, pos_w, 3)
+    torch.cuda.synchronize()
+    assert fused_calls == {"fused": 0, "other": 1}
+    assert _lib.FALLBACKS.get("local_relation", 0) == before + 1, _lib.FALLBACKS
+    from tests import test_fuzz_emulated as tfe
+    want = tfe.lr_reference64(q, k, v, (pos_h + pos_w).reshape(8, 9), torch.ones_like(y))[0]
+    assert ((y.detach().double() - want).abs() <= 4e-2 * (1 + want.abs())).all()
+
+
+_STRICT_LR = r"""
+import sys, torch
+sys.path.insert(0, sys.argv[1])
+from cotnet_amd import _lib
+from cotnet_amd.local_relation import local_relation
+assert _lib.STRICT_DISPATCH
+q, k, v = (torch.randn(1, 8, 2, 212, device="cuda").bfloat16() for _ in range(3))
+pos_h, pos_w = torch.randn(8, 3, 1, device="cuda"), torch.randn(8, 1, 3, device="cuda")
+local_relation(q, k, v, pos_h, pos_w, 3)
+print("no error raised")
+"""
+
+
+def test_width_past_the_lds_boundary_raises_under_strict_dispatch():
+    env = dict(os.environ, COT_STRICT_DISPATCH="1")
+    r = subprocess.run([sys.executable, "-c", _STRICT_LR, ROOT], env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode != 0 and "no error raised" not in r.stdout and "local_relation" in r.stderr, (r.stdout, r.stderr[-3000:])
