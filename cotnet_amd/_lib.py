@@ -305,6 +305,15 @@ def stream():
     return st if st is not None else _current_stream()
 
 
+def capturing():
+    """True while the current stream records into a HIP graph: the launches issued now do not run until the graph is replayed, so
+    nothing they are meant to fill may be put into a cache that eager calls read (cot_layer_fused, conv3x3g)"""
+    if not DEVICE_ONLY:
+        return False
+    import torch
+    return torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
+
+
 def one_stream_query(fn):
     """torch.cuda.current_stream() costs ~9 us and a node makes ~100 launches: ask once per forward / backward of a node (the
     current stream cannot change inside one; forward and backward run on different threads, hence thread-local).  Measured:

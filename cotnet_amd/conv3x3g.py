@@ -29,7 +29,8 @@ def _masks(H, W, device):
         L = _lib.api()
         m = torch.empty(int(L.cot_conv3x3g_masks_bytes(H, W)), dtype=torch.uint8, device=device)
         L.cot_conv3x3g_masks(_p(m), H, W, _stream())
-        _MASKS[k] = m
+        if not _lib.capturing():  # (a capture records the launch and does not run it: the table serves this call, the cache stays as it was)
+            _MASKS[k] = m
     return m
 
 

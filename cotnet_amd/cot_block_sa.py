@@ -118,7 +118,7 @@ class _SplitAttnBlockNode(Function):
         s_1 = stat(Cw, nws_w)
         _bn_fwd(L, c1, a1, sp.bn1, s_1, 2 * Cw, N, Cw, HW, 1)
         c2, b2 = new(Cw), new(Cw)
-        _conv3x3_fwd(L, sp.conv, a1, c2, masks, ws, N, Cw, G, H, W)
+        wm = _conv3x3_fwd(L, sp.conv, a1, c2, masks, ws, N, Cw, G, H, W)  # (groups of 12 first seen inside a capture: its own merged weight)
         s_0 = stat(Cw, nws_w)
         _bn_fwd(L, c2, b2, sp.bn0, s_0, 2 * Cw, N, Cw, HW, sp.act0)
         # the gate: pooled descriptor [N, Cw] -> fc1 -> BatchNorm over the batch + act -> fc2 -> x * sigmoid(logits)
@@ -152,7 +152,7 @@ class _SplitAttnBlockNode(Function):
         _bn_fwd(L, c3, y, sp.bn3, s_3, 2 * Cout, N, Cout, HWo, 1, residual=res, ps=ps, mask=m3)
         ctx.blk = blk
         _pack(ctx, dict(x=x, c1=c1, a1=a1, s_1=s_1, c2=c2, b2=b2, s_0=s_0, gap=gap, hpre=hpre, h=h, s_s=s_s, logits=logits, out2=out2,
-                        c3=c3, y=y, s_3=s_3, out2p=out2p, d0=d0, s_d=s_d, xs=xs, m3=m3, ps=ps))
+                        c3=c3, y=y, s_3=s_3, out2p=out2p, d0=d0, s_d=s_d, xs=xs, m3=m3, ps=ps, wm=wm))
         return y
 
     @staticmethod
@@ -196,7 +196,7 @@ class _SplitAttnBlockNode(Function):
         g_c2 = g_out2  # (reuse: consumed by the gate's backward)
         d_bn0_w, d_bn0_b = _bn_bwd(L, g_b2, c2, None, g_c2, sp.bn0, s.s_0, N, Cw, HW, sp.act0, nws_w)
         g_a1 = g_b2  # (reuse: consumed by bn0's backward)
-        g_wc = _conv3x3_bwd(L, side, sp.conv, g_c2, a1, g_a1, 0, masks, ws, N, Cw, G, H, W)
+        g_wc = _conv3x3_bwd(L, side, sp.conv, g_c2, a1, g_a1, 0, masks, ws, N, Cw, G, H, W, s.wm)
         g_c1 = torch.empty_like(c1)
         d_bn1_w, d_bn1_b = _bn_bwd(L, g_a1, c1, None, g_c1, sp.bn1, s.s_1, N, Cw, HW, 1, nws_w)
         if sp.ds_conv is not None:  # projection shortcut: BatchNorm, 1x1 convolution [, the 2 x 2 average] backwards -> first contribution to dx

@@ -257,7 +257,10 @@ def _masks(L, H, W, device):
     if m is None:
         m = torch.empty(int(L.cot_conv3x3g_masks_bytes(H, W)), dtype=torch.uint8, device=device)
         L.cot_conv3x3g_masks(_p(m), H, W, _stream())
-        _MASKS[k] = m
+        # a capture records the launch and does not run it: a table first made there serves this call (the replay fills it), and an eager
+        # call afterwards must not find it in the cache with nothing written yet -- _pack_for's policy: cache nothing while capturing
+        if not _capturing():
+            _MASKS[k] = m
     return m
 
 
@@ -279,7 +282,7 @@ _PACK_EVENT = {}                       # device index -> event the compute strea
 
 
 def _capturing():
-    return _lib.DEVICE_ONLY and torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
+    return _lib.capturing()
 
 
 def _pack_for(L, conv, mode, N, C, G, H, W):
@@ -369,11 +372,18 @@ def _merge12(C, G):
     return MERGE12 and G % 2 == 0 and C == 12 * G
 
 
-def _merged_weight(conv, C, G, refresh):
+def _merged_weight(conv, C, G, refresh, own=None):
+    """own: the merged weight the forward of this backward made for itself (_conv3x3_fwd's return value), used as it is"""
+    if own is not None:
+        return own
     w = conv.weight
     ent = _MERGED.get(conv)
     if ent is None or ent[1].device != w.device or ent[1].dtype != w.dtype:
-        ent = _MERGED[conv] = [None, torch.zeros((C, 24, 3, 3), dtype=w.dtype, device=w.device)]
+        ent = [None, torch.zeros((C, 24, 3, 3), dtype=w.dtype, device=w.device)]
+        # (a capture records the zero fill and does not run it: a buffer first made there is this call's own -- the replay fills it --
+        # and never reaches the cache, where an eager call would read its off-diagonal blocks before anything wrote them)
+        if not _capturing():
+            _MERGED[conv] = ent
     key = (w.data_ptr(), w._version, PARAM_EPOCH[0])
     if refresh or ent[0] != key:  # (forward: always -- a replayed graph moves the weights behind every counter; backward: the forward's copy)
         G2 = G // 2
@@ -388,10 +398,13 @@ def _conv3x3_ws_groups(C, G):
 
 
 def _conv3x3_fwd(L, conv, x, y, masks, ws, N, C, G, H, W):
+    """-> None, or the merged weight this call made for itself (groups of 12 first seen inside a capture: not in _MERGED): the
+    backward of this forward is handed it (`own`)"""
     if _merge12(C, G):
         wm = _merged_weight(conv, C, G, True)
         L.cot_conv3x3g_forward(_p(x), _p(wm), _p(y), _p(masks), _p(ws), N, C, C, G // 2, H, W, BF16, _stream())
-        return
+        ent = _MERGED.get(conv)
+        return None if (ent is not None and ent[1] is wm) else wm
     pk = _pack_for(L, conv, 0, N, C, G, H, W)
     if pk is not None:
         L.cot_conv3x3g_forward_packed(_p(x), _p(pk), _p(y), N, C, C, G, H, W, BF16, _stream())
@@ -399,9 +412,9 @@ def _conv3x3_fwd(L, conv, x, y, masks, ws, N, C, G, H, W):
         L.cot_conv3x3g_forward(_p(x), _p(conv.weight), _p(y), _p(masks), _p(ws), N, C, C, G, H, W, BF16, _stream())
 
 
-def _conv3x3_dgrad(L, conv, gy, gx, accumulate, masks, ws, N, C, G, H, W):
+def _conv3x3_dgrad(L, conv, gy, gx, accumulate, masks, ws, N, C, G, H, W, own=None):
     if _merge12(C, G):
-        wm = _merged_weight(conv, C, G, False)
+        wm = _merged_weight(conv, C, G, False, own)
         L.cot_conv3x3g_backward_data(_p(gy), _p(wm), _p(gx), accumulate, _p(masks), _p(ws), N, C, C, G // 2, H, W, BF16, _stream())
         return
     pk = _pack_for(L, conv, 1, N, C, G, H, W)
@@ -643,12 +656,13 @@ def _conv1x1_bwd(L, side, ws, conv, gy, x1, x2, c1, gx1, gx2, accumulate, N, Ci,
     return g
 
 
-def _conv3x3_bwd(L, side, conv, gy, x, gx, accumulate, masks, ws, N, C, G, H, W):
-    """the grouped 3x3: weight gradient queued (x carries margins: _new_guarded), then gx (+)= the data gradient -> gw"""
+def _conv3x3_bwd(L, side, conv, gy, x, gx, accumulate, masks, ws, N, C, G, H, W, own=None):
+    """the grouped 3x3: weight gradient queued (x carries margins: _new_guarded), then gx (+)= the data gradient -> gw.
+    own: _conv3x3_fwd's return value"""
     gw = grad_sink.out_like(conv.weight)
     fn, a = L.cot_conv3x3g_backward_weight_guarded, (_p(gy), _p(x), _p(gw), _p(masks), _p(side.ws), N, C, C, G, H, W, BF16, _guard_elems(x))
     side.run(lambda st_: fn(*a, st_), gy, x, masks)
-    _conv3x3_dgrad(L, conv, gy, gx, accumulate, masks, ws, N, C, G, H, W)
+    _conv3x3_dgrad(L, conv, gy, gx, accumulate, masks, ws, N, C, G, H, W, own)
     return gw
 
 
@@ -754,7 +768,7 @@ def _cot_forward(L, layer, x, cm=None):
 
     # static context k = relu(bn(conv3x3_grouped(x)))                                             (ref :80)
     k_pre, k = new(C), new1(C)
-    _conv3x3_fwd(L, pl.ke0, x, k_pre, masks, ws, N, C, G, H, W)
+    wm = _conv3x3_fwd(L, pl.ke0, x, k_pre, masks, ws, N, C, G, H, W)
     s_k = stat(C, nws_x)
     if cm:
         _bn_fwd_lay(L, k_pre, None, k, None, pl.ke1, s_k, N, C, HW, 1, y_cm=True)
@@ -865,7 +879,7 @@ def _cot_forward(L, layer, x, cm=None):
         L.cot_radix_mix_logits(_p(y), _p(k), _p(logitsT), _p(out), _p(attn), N, C, HW, BF16, st)
     return out, dict(x=x, xc=x1 if cm else None, k_pre=k_pre, k=k, e0=e0, e1=e1, e3=e3, w=w, gn_mean=gn_mean, gn_rstd=gn_rstd,
                      v_pre=v_pre, v=v, a=a, y=y, attn=attn, s_k=s_k, s_e=s_e, s_v=s_v, s_y=s_y, gapT=gapT, hpre=hpre, h=h, s_a=s_a,
-                     qk=qk), geom
+                     qk=qk, wm=wm), geom
 
 
 def _cot_backward(L, layer, s, geom, gout, side=None, cm=None):
@@ -997,7 +1011,7 @@ def _cot_backward(L, layer, s, geom, gout, side=None, cm=None):
     else:
         gk_pre, gx3 = gv, gx1  # (reuse: gv is dead)
         d_ke_w, d_ke_b = _bn_bwd(L, gk, k_pre, None, gk_pre, ke1, s.s_k, N, C, HW, 1, nws_c)
-    g_wk = _conv3x3_bwd(L, side, ke0, gk_pre, x, gx3, 0 if cm else 1, masks, ws, N, C, G, H, W)
+    g_wk = _conv3x3_bwd(L, side, ke0, gk_pre, x, gx3, 0 if cm else 1, masks, ws, N, C, G, H, W, s.wm)
     if own_side:
         side.join()
     # order = _Plan.params

@@ -57,6 +57,7 @@ class FlatSGD:
         are averaged with one multi-tensor lerp.  `ema_state_dict()` returns it under the model's state_dict keys."""
         self.lr, self.momentum, self.weight_decay, self.nesterov = float(lr), float(momentum), float(weight_decay), nesterov
         self.ema_decay = None if ema_decay is None else float(ema_decay)
+        self._captured_lr = None  # the rate a HIP-graph capture of step() baked into its cot_sgd_step launches (set_lr)
         self.model = model
         # masters must be taken from the fp32 values BEFORE rounding when the caller converts later; here parameters
         # are already in their storage dtype, so the master starts as the (exact) up-cast of the working copy.
@@ -87,6 +88,8 @@ class FlatSGD:
             self.reducer.finish()
         L = _lib.api()
         stream = _lib.stream()
+        if _lib.capturing():  # cot_sgd_step takes the rate by value: every replay of this capture steps with it (set_lr)
+            self._captured_lr = self.lr
         for b, st in zip(self.reducer.buckets, self.state):
             key = b.key
             wd = self.weight_decay if key == "decay" else 0.0
@@ -128,7 +131,18 @@ class FlatSGD:
         return out
 
     def set_lr(self, lr):
-        self.lr = float(lr)
+        """the rate of the steps issued from here on.  cot_sgd_step takes it by value, so a HIP graph that captured step() keeps the
+        rate it was captured with: a different rate after such a capture raises, and changes nothing, instead of leaving the replays
+        silently at the old one (a schedule over a replayed step would otherwise train at a constant rate).  The captured rate itself
+        is always accepted.  To move on, capture the step again and call set_lr INSIDE that capture, before step(): while capturing,
+        any rate is accepted, and the step() that follows records it.  (A device-resident rate that replays could follow needs another
+        cot_sgd_step signature -- an ABI change, not made here.)"""
+        lr = float(lr)
+        if self._captured_lr is not None and lr != self._captured_lr and not _lib.capturing():
+            raise RuntimeError(f"FlatSGD.set_lr({lr:g}): step() was captured into a HIP graph at lr = {self._captured_lr:g}, and replays "
+                               "keep the captured rate -- capture the step again and set the new rate inside that capture (its "
+                               "step() records it); the rate is left as it was")
+        self.lr = lr
 
     def master_parameters(self):
         """fp32 view of every parameter (master copy for bf16 parameters), in module.parameters() order of the buckets"""
