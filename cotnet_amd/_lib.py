@@ -104,6 +104,7 @@ SYMBOLS = {
     "cot_stem3x3s2_backward_weight": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "cot_sgd_step": (_I, [_P, _P, _P, _P, ctypes.c_int64, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
                           _I, _I, _I, _P]),
+    "cot_sgd_step_lr": (_I, [_P, _P, _P, _P, ctypes.c_int64, _P, ctypes.c_float, ctypes.c_float, ctypes.c_float, _I, _I, _I, _P]),
     "cot_conv1x1_workspace": (ctypes.c_int64, [_I, _I, _I, _I, _I]),
     "cot_conv1x1_forward": (_I, [_P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "cot_conv1x1_backward_data": (_I, [_P, _P, _P, _P, _I, _I, _P, _I, _I, _I, _I, _I, _P]),

@@ -119,6 +119,7 @@ int aggmix_backward_weight(const T*, const T*, T*, T*, const cot_agg_geom&, int,
 const char* last_kernel_mix();
 extern int g_mix_tune[3];  // agg_mix.hip: [0] = 1 generic kernels only, [1] = lanes a tiled workgroup aims for, [2] = pixels per lane
 int sgd_flat(void*, void*, void*, const void*, int64_t, float, float, float, float, int, int, int, hipStream_t);
+int sgd_flat_lr(void*, void*, void*, const void*, int64_t, const float*, float, float, float, int, int, int, hipStream_t);
 int ema_flat(void*, const void*, int64_t, float, int, hipStream_t);
 int bn_workspace_floats(int N, int C);
 int bn_act_lay_covers(int N, int C, int HW);
@@ -559,6 +560,19 @@ int cot_sgd_step(void* param, void* master, void* momentum_buf, const void* grad
     if (rc) return rc;
     return sgd_flat(param, master, momentum_buf, grad, n, lr, momentum, weight_decay, grad_scale, nesterov, param_dtype,
                     grad_dtype, (hipStream_t)stream);
+}
+
+int cot_sgd_step_lr(void* param, void* master, void* momentum_buf, const void* grad, int64_t n, const void* lr_dev,
+                    float momentum, float weight_decay, float grad_scale, int nesterov, int param_dtype, int grad_dtype,
+                    void* stream) {
+    if (!param || !momentum_buf || !grad) return set_error(COT_ERR_INVALID_ARG, "NULL device pointer");
+    if (!lr_dev) return set_error(COT_ERR_INVALID_ARG, "NULL lr_dev (the device float the rate is read from)");
+    if (n <= 0) return set_error(COT_ERR_INVALID_ARG, "non-positive element count %lld", (long long)n);
+    int rc = check_align16({param, master, momentum_buf, grad});
+    if (rc) return rc;
+    if ((uintptr_t)lr_dev % 4 != 0) return set_error(COT_ERR_INVALID_ARG, "lr_dev %p is not 4-byte aligned", lr_dev);
+    return sgd_flat_lr(param, master, momentum_buf, grad, n, (const float*)lr_dev, momentum, weight_decay, grad_scale,
+                       nesterov, param_dtype, grad_dtype, (hipStream_t)stream);
 }
 
 int cot_ema_step(void* ema, const void* src, int64_t n, float decay, int src_dtype, void* stream) {

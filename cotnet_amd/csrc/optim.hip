@@ -8,15 +8,25 @@
 // Low-precision training keeps an fp32 master copy: the kernel reads the bf16 gradient bucket, updates master and
 // momentum in fp32 and writes the bf16 working copy the convolutions read -- 2+4+4 B read, 4+4+2 B written per
 // parameter, HBM-bound, 16-byte accesses per lane.  Same arithmetic (in fp32) as torch.optim.SGD with dampening 0.
+#include <type_traits>
+
 #include "cot_common.h"
 
 namespace cot {
 
-template <typename PT, typename GT, bool HAS_MASTER, int V>
+// Where the rate comes from is the kernel's last template argument.  LR = float: by value, fixed when the launch is enqueued
+// (or recorded into a HIP graph).  LR = const float*: one float in device memory, read when the kernel RUNS -- every lane loads
+// it once in front of the loop, the tail uses the same value -- so a graph that recorded the launch steps with whatever the
+// float holds at each replay.  The kernel only reads it; the caller writes it, ordered on the stream.
+__device__ __forceinline__ float sgd_rate(float lr) { return lr; }
+__device__ __forceinline__ float sgd_rate(const float* __restrict__ lr_dev) { return *lr_dev; }
+
+template <typename PT, typename GT, bool HAS_MASTER, int V, typename LR>
 __global__ __launch_bounds__(256) void sgd_flat_kernel(PT* __restrict__ param, float* __restrict__ master,
                                                       float* __restrict__ mom, const GT* __restrict__ grad,
-                                                      int64_t n, float lr, float momentum, float wd, float gscale,
+                                                      int64_t n, LR lr_arg, float momentum, float wd, float gscale,
                                                       int nesterov) {
+    const float lr = sgd_rate(lr_arg);
     const int64_t nvec = n / V;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nvec; i += (int64_t)gridDim.x * blockDim.x) {
         const Vec<GT, V> gv = ldv<GT, V>(grad + i * V);
@@ -91,19 +101,20 @@ int ema_flat(void* ema, const void* src, int64_t n, float decay, int src_dtype, 
     return check_launch("ema_flat_kernel");
 }
 
-template <typename PT, typename GT, bool HAS_MASTER>
-static int launch_sgd(void* param, void* master, void* mom, const void* grad, int64_t n, float lr, float momentum,
+template <typename PT, typename GT, bool HAS_MASTER, typename LR>
+static int launch_sgd(void* param, void* master, void* mom, const void* grad, int64_t n, LR lr, float momentum,
                       float wd, float gscale, int nesterov, hipStream_t s) {
     constexpr int V = 4;  // 16 B of fp32 state per lane
     int64_t blocks = ceil_div64(n / V > 0 ? n / V : 1, 256);
     if (blocks > 2048) blocks = 2048;  // grid-stride: 8 blocks per CU
-    COT_LAUNCH((sgd_flat_kernel<PT, GT, HAS_MASTER, V>), dim3((unsigned)blocks), dim3(256), 0, s, (PT*)param,
+    COT_LAUNCH((sgd_flat_kernel<PT, GT, HAS_MASTER, V, LR>), dim3((unsigned)blocks), dim3(256), 0, s, (PT*)param,
                (float*)master, (float*)mom, (const GT*)grad, n, lr, momentum, wd, gscale, nesterov);
-    return check_launch("sgd_flat_kernel");
+    return check_launch(std::is_pointer<LR>::value ? "sgd_flat_kernel<lr_dev>" : "sgd_flat_kernel");
 }
 
-int sgd_flat(void* param, void* master, void* mom, const void* grad, int64_t n, float lr, float momentum, float wd,
-             float gscale, int nesterov, int param_dtype, int grad_dtype, hipStream_t s) {
+template <typename LR>  // float (cot_sgd_step) or const float* (cot_sgd_step_lr)
+static int sgd_dispatch(void* param, void* master, void* mom, const void* grad, int64_t n, LR lr, float momentum, float wd,
+                        float gscale, int nesterov, int param_dtype, int grad_dtype, hipStream_t s) {
     if (param_dtype == COT_BF16 && grad_dtype == COT_BF16 && master)
         return launch_sgd<bf16_t, bf16_t, true>(param, master, mom, grad, n, lr, momentum, wd, gscale, nesterov, s);
     if (param_dtype == COT_BF16 && grad_dtype == COT_F32 && master)
@@ -114,6 +125,17 @@ int sgd_flat(void* param, void* master, void* mom, const void* grad, int64_t n, 
         return launch_sgd<float, bf16_t, false>(param, master, mom, grad, n, lr, momentum, wd, gscale, nesterov, s);
     return set_error(COT_ERR_UNSUPPORTED, "sgd: param dtype %d / grad dtype %d / master %s not supported", param_dtype,
                      grad_dtype, master ? "given" : "NULL");
+}
+
+int sgd_flat(void* param, void* master, void* mom, const void* grad, int64_t n, float lr, float momentum, float wd,
+             float gscale, int nesterov, int param_dtype, int grad_dtype, hipStream_t s) {
+    return sgd_dispatch<float>(param, master, mom, grad, n, lr, momentum, wd, gscale, nesterov, param_dtype, grad_dtype, s);
+}
+
+int sgd_flat_lr(void* param, void* master, void* mom, const void* grad, int64_t n, const float* lr_dev, float momentum,
+                float wd, float gscale, int nesterov, int param_dtype, int grad_dtype, hipStream_t s) {
+    return sgd_dispatch<const float*>(param, master, mom, grad, n, lr_dev, momentum, wd, gscale, nesterov, param_dtype,
+                                      grad_dtype, s);
 }
 
 }  // namespace cot

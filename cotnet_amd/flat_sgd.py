@@ -9,7 +9,8 @@ On MI355X the step is bound by HBM passes and launch count, so this module
   * lays parameters, gradients, masters and momentum out in a few flat buckets per (dtype, weight-decay) group
     (cotnet_amd.data_parallel.GradBucketReducer with flatten_params=True, grad_mode="copy": autograd's gradients are
     moved into the bucket with one multi-tensor copy, then all-reduced over RCCL on the side stream);
-  * updates each bucket with ONE hand-written HIP kernel (`cot_sgd_step`, csrc/optim.hip).
+  * updates each bucket with ONE hand-written HIP kernel (`cot_sgd_step`, csrc/optim.hip; `cot_sgd_step_lr` with
+    device_lr=True: the rate read from device memory, so that a step replayed from a HIP graph follows a schedule).
 
 Arithmetic = torch.optim.SGD (dampening 0) evaluated in fp32 on the master weights; checked against it in
 tests/test_flat_sgd_gpu.py.
@@ -38,7 +39,7 @@ def _decay_group(name, p):
 
 class FlatSGD:
     def __init__(self, model, lr, momentum=0.9, weight_decay=0.0, nesterov=True, bucket_mb=10.0, process_group=None,
-                 broadcast_params=True, ema_decay=None, force_collectives=False, grad_dtype=None):
+                 broadcast_params=True, ema_decay=None, force_collectives=False, grad_dtype=None, device_lr=False):
         """bucket_mb: size of the flat gradient buckets.  10 MiB cuts CoTNet-50's 44 MB of bf16 weight gradients into five
         buckets in the order backward produces them (classifier and stage 4 first, the stem last), so four all-reduces are
         already on the communication stream when backward ends and only the last, small one is exposed; round 2's 48 MiB
@@ -54,7 +55,12 @@ class FlatSGD:
         ema_decay: also keep an exponential moving average of the weights (the reference's ModelEmaV2,
         utils/model_ema.py, `model_ema: True` / decay 0.9999 in its recipes): one flat kernel per bucket after the SGD
         kernel instead of one elementwise op per state_dict tensor; floating-point buffers (BatchNorm running statistics)
-        are averaged with one multi-tensor lerp.  `ema_state_dict()` returns it under the model's state_dict keys."""
+        are averaged with one multi-tensor lerp.  `ema_state_dict()` returns it under the model's state_dict keys.
+        device_lr: False (default): `cot_sgd_step` takes the rate by value, so a HIP graph that captured step() keeps the rate it
+        was captured with (set_lr).  True: the rate lives in `self.lr_dev`, one fp32 element on the parameters' device, allocated
+        here once (its address never changes); step() issues `cot_sgd_step_lr`, whose kernel reads that element when it runs, so a
+        capture bakes no rate and set_lr between replays moves the replayed step (lr_schedule.CosineSchedule.apply).  Same
+        arithmetic on the same fp32 rate: the two forms are bit-equal (tests/test_sgd_device_lr_gpu.py)."""
         self.lr, self.momentum, self.weight_decay, self.nesterov = float(lr), float(momentum), float(weight_decay), nesterov
         self.ema_decay = None if ema_decay is None else float(ema_decay)
         self._captured_lr = None  # the rate a HIP-graph capture of step() baked into its cot_sgd_step launches (set_lr)
@@ -71,6 +77,10 @@ class FlatSGD:
             if self.ema_decay is not None:
                 st["ema"] = (master if master is not None else b.pflat).float().clone()
             self.state.append(st)
+        self.lr_dev = None
+        if device_lr:
+            dev = self.reducer.buckets[0].pflat.device if self.reducer.buckets else next(model.parameters()).device
+            self.lr_dev = torch.full((1,), self.lr, dtype=torch.float32, device=dev)
         if self.ema_decay is not None:
             self._buf_src = [bf for bf in model.buffers() if bf.is_floating_point()]
             self._buf_ema = [bf.detach().float().clone() for bf in self._buf_src]
@@ -88,16 +98,20 @@ class FlatSGD:
             self.reducer.finish()
         L = _lib.api()
         stream = _lib.stream()
-        if _lib.capturing():  # cot_sgd_step takes the rate by value: every replay of this capture steps with it (set_lr)
-            self._captured_lr = self.lr
+        if self.lr_dev is not None:  # the kernel reads the rate when it runs: a capture bakes none
+            sgd, rate = L.cot_sgd_step_lr, self.lr_dev.data_ptr()
+        else:
+            sgd, rate = L.cot_sgd_step, self.lr
+            if _lib.capturing():  # cot_sgd_step takes the rate by value: every replay of this capture steps with it (set_lr)
+                self._captured_lr = self.lr
         for b, st in zip(self.reducer.buckets, self.state):
             key = b.key
             wd = self.weight_decay if key == "decay" else 0.0
-            L.cot_sgd_step(b.pflat.data_ptr(),
-                           st["master"].data_ptr() if st["master"] is not None else None,
-                           st["mom"].data_ptr(), self.reducer.reduced(b).data_ptr(),
-                           b.pflat.numel(), self.lr, self.momentum, wd, 1.0, 1 if self.nesterov else 0,
-                           _lib.dtype_code(b.pflat.dtype), _lib.dtype_code(self.reducer.reduced(b).dtype), stream)
+            sgd(b.pflat.data_ptr(),
+                st["master"].data_ptr() if st["master"] is not None else None,
+                st["mom"].data_ptr(), self.reducer.reduced(b).data_ptr(),
+                b.pflat.numel(), rate, self.momentum, wd, 1.0, 1 if self.nesterov else 0,
+                _lib.dtype_code(b.pflat.dtype), _lib.dtype_code(self.reducer.reduced(b).dtype), stream)
             if self.ema_decay is not None:
                 src = st["master"] if st["master"] is not None else b.pflat
                 L.cot_ema_step(st["ema"].data_ptr(), src.data_ptr(), src.numel(),
@@ -131,13 +145,29 @@ class FlatSGD:
         return out
 
     def set_lr(self, lr):
-        """the rate of the steps issued from here on.  cot_sgd_step takes it by value, so a HIP graph that captured step() keeps the
-        rate it was captured with: a different rate after such a capture raises, and changes nothing, instead of leaving the replays
-        silently at the old one (a schedule over a replayed step would otherwise train at a constant rate).  The captured rate itself
-        is always accepted.  To move on, capture the step again and call set_lr INSIDE that capture, before step(): while capturing,
-        any rate is accepted, and the step() that follows records it.  (A device-resident rate that replays could follow needs another
-        cot_sgd_step signature -- an ABI change, not made here.)"""
+        """the rate of the steps issued from here on.
+
+        device_lr=False: cot_sgd_step takes it by value, so a HIP graph that captured step() keeps the rate it was captured with:
+        a different rate after such a capture raises, and changes nothing, instead of leaving the replays silently at the old one
+        (a schedule over a replayed step would otherwise train at a constant rate).  The captured rate itself is always accepted.
+        To move on, capture the step again and call set_lr INSIDE that capture, before step(): while capturing, any rate is
+        accepted, and the step() that follows records it.
+
+        device_lr=True: never raises outside a capture.  The rate is written into `self.lr_dev` with one fill on the CURRENT stream
+        (the value travels as that fill's kernel argument, rounded to fp32 as the by-value argument is: no host staging buffer that
+        a second set_lr could overwrite before the first write ran).  Eager steps and replays issued afterwards read it -- the
+        write is ordered on the current stream, so issue the step or the replay on that stream or on one that waits for it.
+        WHILE capturing it raises and changes nothing: a recorded fill would put the captured rate back at every replay, the
+        silent constant-rate training again -- set the rate outside the capture."""
         lr = float(lr)
+        if self.lr_dev is not None:
+            if _lib.capturing():
+                raise RuntimeError(f"FlatSGD.set_lr({lr:g}) inside a HIP-graph capture: the fill of the device-resident rate would be "
+                                   "recorded and reset the rate at every replay -- set the rate outside the capture (replays read "
+                                   "lr_dev when they run); the rate is left as it was")
+            self.lr = lr
+            self.lr_dev.fill_(self.lr)
+            return
         if self._captured_lr is not None and lr != self._captured_lr and not _lib.capturing():
             raise RuntimeError(f"FlatSGD.set_lr({lr:g}): step() was captured into a HIP graph at lr = {self._captured_lr:g}, and replays "
                                "keep the captured rate -- capture the step again and set the new rate inside that capture (its "

@@ -465,6 +465,16 @@ int cot_sgd_step(void* param, void* master, void* momentum_buf, const void* grad
                  float momentum, float weight_decay, float grad_scale, int nesterov, int param_dtype, int grad_dtype,
                  void* stream);
 
+/* The same step with the rate in device memory: `lr_dev` points to ONE float on the device (4-byte aligned; the 16-byte rule
+ * of the other pointers does not apply to it; NULL is COT_ERR_INVALID_ARG).  The kernel reads it when it EXECUTES, not when this
+ * call enqueues it, and only reads it: a HIP graph that recorded this launch steps with whatever the float holds at each replay,
+ * which is how a replayed training step follows a learning-rate schedule without being captured again.  The caller orders its
+ * writes to that float on the stream: written on `stream` (or on a stream `stream` waits for) before the launch or the replay.
+ * With the same fp32 rate the result is bit-identical to cot_sgd_step's; every other argument is validated as there. */
+int cot_sgd_step_lr(void* param, void* master, void* momentum_buf, const void* grad, int64_t n, const void* lr_dev,
+                    float momentum, float weight_decay, float grad_scale, int nesterov, int param_dtype, int grad_dtype,
+                    void* stream);
+
 /* ---- exponential moving average of the weights over a flat buffer (replaces the per-tensor
  * `ema = decay*ema + (1-decay)*model` of ModelEmaV2._update, utils/model_ema.py:45-53):  ema fp32 [n], src the fp32
  * master copy / fp32 parameters (COT_F32) or bf16 parameters (COT_BF16). */
