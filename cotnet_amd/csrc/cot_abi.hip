@@ -281,6 +281,9 @@ int bn_rowstats(const float*, int, int, int, int, float, float, float*, float*, 
 template <typename T>
 int bn_batch_stats(const void*, float*, float*, float*, float*, long long*, float*, int, int, int, float, float, hipStream_t);
 int input_normalize(const void*, void*, const float*, const float*, int64_t, int, int, int, hipStream_t);  // input_norm.hip
+int mix_normalize(const void*, void*, const float*, const float*, const void*, int, int, int, int, int, hipStream_t);  // mix_loss.hip
+int soft_ce_forward(const void*, const void*, const void*, double, float*, float*, float*, int, int, int, hipStream_t);
+int soft_ce_backward(const void*, const void*, const void*, double, const float*, const float*, void*, int, int, int, hipStream_t);
 const char* last_kernel_nchw();
 const char* last_kernel_nhwc();
 int set_tuning_nchw(int key, int value);
@@ -1654,6 +1657,68 @@ int cot_input_normalize(const void* x_u8, void* y, const float* mean, const floa
     int rc = check_align16({x_u8, y});
     if (rc) return rc;
     return input_normalize(x_u8, y, mean, stdv, planes, C, HW, dtype, (hipStream_t)stream);
+}
+
+static size_t norm_out_bytes(int dtype) { return dtype == COT_F32 ? 4 : 2; }
+
+int cot_mix_normalize(const void* x_u8, void* y, const float* mean, const float* stdv, const void* params, int N, int C, int H, int W,
+                      int dtype, void* stream) {
+    if (!x_u8 || !y || !mean || !stdv) return set_error(COT_ERR_INVALID_ARG, "NULL device pointer");
+    if (!params) return set_error(COT_ERR_INVALID_ARG, "NULL params (the device block mode / lambda / box are read from)");
+    if ((uintptr_t)params % 4 != 0) return set_error(COT_ERR_INVALID_ARG, "params %p is not 4-byte aligned", params);
+    if (N <= 0 || C <= 0 || H <= 0 || W <= 0 || (int64_t)H * W > INT32_MAX)
+        return set_error(COT_ERR_INVALID_ARG, "bad N=%d / C=%d / H=%d / W=%d", N, C, H, W);
+    if (N % 2 != 0) return set_error(COT_ERR_INVALID_ARG, "batch size %d is odd: sample i is mixed with sample N-1-i", N);
+    if (dtype != COT_F32 && dtype != COT_BF16 && dtype != COT_F16)
+        return set_error(COT_ERR_UNSUPPORTED, "cot_mix_normalize: output dtype %d (float32 / bfloat16 / float16)", dtype);
+    if ((H * W) % 16 == 0) {  // 16 pixels per lane: 16-byte loads and stores
+        int rc = check_align16({x_u8, y});
+        if (rc) return rc;
+    } else if ((uintptr_t)y % norm_out_bytes(dtype) != 0) {  // element path
+        return set_error(COT_ERR_INVALID_ARG, "y %p is not aligned to its element size", y);
+    }
+    const size_t n = (size_t)N * C * H * W;
+    const uintptr_t x0 = (uintptr_t)x_u8, y0 = (uintptr_t)y;
+    if (x0 < y0 + n * norm_out_bytes(dtype) && y0 < x0 + n)
+        return set_error(COT_ERR_INVALID_ARG, "y overlaps x: the partner sample is read from the unmodified input");
+    return mix_normalize(x_u8, y, mean, stdv, params, N, C, H, W, dtype, (hipStream_t)stream);
+}
+
+static int soft_ce_validate(const char* who, const void* logits, const void* labels, const void* params, double smoothing, int N, int K,
+                            int dtype) {
+    if (!logits || !labels) return set_error(COT_ERR_INVALID_ARG, "NULL device pointer");
+    if (!params) return set_error(COT_ERR_INVALID_ARG, "NULL params (the device block lambda is read from)");
+    if ((uintptr_t)params % 4 != 0) return set_error(COT_ERR_INVALID_ARG, "params %p is not 4-byte aligned", params);
+    if ((uintptr_t)labels % 8 != 0) return set_error(COT_ERR_INVALID_ARG, "labels %p is not 8-byte aligned (int64)", labels);
+    if (N <= 0 || K < 1) return set_error(COT_ERR_INVALID_ARG, "bad N=%d / K=%d", N, K);
+    if (!(smoothing >= 0.0 && smoothing < 1.0)) return set_error(COT_ERR_INVALID_ARG, "smoothing %g outside [0, 1)", smoothing);
+    if (dtype != COT_F32 && dtype != COT_BF16)
+        return set_error(COT_ERR_UNSUPPORTED, "%s: logits dtype %d (float32 / bfloat16)", who, dtype);
+    if ((uintptr_t)logits % (dtype == COT_F32 ? 4 : 2) != 0) return set_error(COT_ERR_INVALID_ARG, "logits %p is not element-aligned", logits);
+    return COT_OK;
+}
+
+int cot_soft_target_ce_forward(const void* logits, const void* labels, const void* params, double smoothing, void* row_loss,
+                               void* row_lse, void* mean_loss, int N, int K, int dtype, void* stream) {
+    int rc = soft_ce_validate("cot_soft_target_ce_forward", logits, labels, params, smoothing, N, K, dtype);
+    if (rc) return rc;
+    if (!row_loss || !row_lse || !mean_loss) return set_error(COT_ERR_INVALID_ARG, "NULL output pointer");
+    if ((uintptr_t)row_loss % 4 || (uintptr_t)row_lse % 4 || (uintptr_t)mean_loss % 4)
+        return set_error(COT_ERR_INVALID_ARG, "fp32 outputs must be 4-byte aligned");
+    return soft_ce_forward(logits, labels, params, smoothing, (float*)row_loss, (float*)row_lse, (float*)mean_loss, N, K, dtype,
+                           (hipStream_t)stream);
+}
+
+int cot_soft_target_ce_backward(const void* logits, const void* labels, const void* params, double smoothing, const void* row_lse,
+                                const void* grad_out, void* dlogits, int N, int K, int dtype, void* stream) {
+    int rc = soft_ce_validate("cot_soft_target_ce_backward", logits, labels, params, smoothing, N, K, dtype);
+    if (rc) return rc;
+    if (!row_lse || !dlogits) return set_error(COT_ERR_INVALID_ARG, "NULL device pointer");
+    if (!grad_out) return set_error(COT_ERR_INVALID_ARG, "NULL grad_out (the device float the upstream gradient is read from)");
+    if ((uintptr_t)row_lse % 4 || (uintptr_t)grad_out % 4 || (uintptr_t)dlogits % (dtype == COT_F32 ? 4 : 2))
+        return set_error(COT_ERR_INVALID_ARG, "row_lse / grad_out / dlogits must be element-aligned");
+    return soft_ce_backward(logits, labels, params, smoothing, (const float*)row_lse, (const float*)grad_out, dlogits, N, K, dtype,
+                            (hipStream_t)stream);
 }
 
 int cot_bn_act_workspace(int N, int C) { return (N > 0 && C > 0) ? bn_workspace_floats(N, C) : 0; }

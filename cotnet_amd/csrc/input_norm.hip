@@ -3,24 +3,10 @@
 // elementwise kernels on the prefetch stream: .float() / .half(), .sub_(mean), .div_(std)).
 //   1 B read + sizeof(T) B written per element, HBM-bound: a lane takes 16 consecutive pixels (one 16-byte load) and
 //   writes them with 16-byte stores.
-// Arithmetic = the reference's, operation by operation: fp32: IEEE subtract, then IEEE divide (no reciprocal, no FMA
-// contraction) -> bit-identical to torch; fp16 (reference `fp16=True`): every intermediate rounded to half as torch's
-// half kernels do (fp32 holds a half product / quotient exactly enough that the double rounding is innocuous);
-// bf16 (extension for the bf16 model): computed in fp32, rounded once.
-#include "cot_common.h"
+// The per-pixel arithmetic (norm_one<T>) is in input_norm.h: cot_mix_normalize (mix_loss.hip) shares it.
+#include "input_norm.h"
 
 namespace cot {
-
-template <typename T> __device__ __forceinline__ T norm_one(uint8_t u, float m, float s) {
-#pragma clang fp contract(off)
-    const float d = (float)u - m;
-    return (T)(d / s);
-}
-template <> __device__ __forceinline__ f16_t norm_one<f16_t>(uint8_t u, float m, float s) {
-#pragma clang fp contract(off)
-    const f16_t d = (f16_t)((float)u - m);  // m, s are already half-representable (the host rounds them as the reference does)
-    return (f16_t)((float)d / s);
-}
 
 template <typename T>
 __global__ __launch_bounds__(256) void input_normalize_kernel(const uint8_t* __restrict__ x, T* __restrict__ y,

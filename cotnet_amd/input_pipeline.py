@@ -8,6 +8,10 @@ of the consumer.  Here the three kernels are ONE hand-written pass (`cot_input_n
 bf16 model); the side stream, the non-blocking copy and the one-batch look-ahead are kept.  fp32 results are
 bit-identical to the reference's (IEEE subtract, then IEEE divide).  Random erasing (`re_prob`) is data augmentation and
 out of scope: a non-zero `re_prob` raises.
+
+`PrefetchLoader(..., mixup=DeviceMixup(...))` moves the recipe's batch-mode mixup / CutMix from the host collate onto the side stream
+too: the host loader yields plain uint8 batches and integer labels, the side stream draws the batch's parameters and runs
+`cot_mix_normalize` in place of `cot_input_normalize`, and the loss (cotnet_amd.loss) reads the same parameters from `mixup.params`.
 """
 import torch
 
@@ -38,7 +42,7 @@ class PrefetchLoader:
     (default: fp16 if `fp16` else fp32, as the reference; torch.bfloat16 feeds the bf16 model without a cast kernel)."""
 
     def __init__(self, loader, mean=IMAGENET_DEFAULT_MEAN, std=IMAGENET_DEFAULT_STD, fp16=False, re_prob=0.0,
-                 re_mode="const", re_count=1, re_num_splits=0, dtype=None, device="cuda"):
+                 re_mode="const", re_count=1, re_num_splits=0, dtype=None, device="cuda", mixup=None):
         if re_prob > 0.0:
             raise NotImplementedError("RandomErasing is data augmentation: out of scope (SURVEY.md 2)")
         self.loader = loader
@@ -49,8 +53,57 @@ class PrefetchLoader:
         if self.dtype == torch.float16:  # the reference rounds the constants to half first (loader.py:69-71)
             mean, std = mean.half().float(), std.half().float()
         self.mean, self.std = mean.to(self.device), std.to(self.device)
+        self.mixup = mixup  # a cotnet_amd.mixup.DeviceMixup, or None: the batches pass unmixed, as before
+
+    @property
+    def mixup_enabled(self):
+        return self.mixup is not None and self.mixup.mixup_enabled
+
+    @mixup_enabled.setter
+    def mixup_enabled(self, x):  # the training loop's switch for the last epochs (reference loader.py:116-123, train.py:243-245)
+        if self.mixup is None:
+            assert not x, "PrefetchLoader was built without a mixup"
+        else:
+            self.mixup.mixup_enabled = x
 
     def __iter__(self):
+        if self.mixup is not None:
+            return self._iter_mixed()
+        return self._iter_plain()
+
+    def _iter_mixed(self):
+        """The batch is prepared one step AHEAD of the loss that needs its parameters, and the loss of the batch in flight still reads
+        `mixup.params`.  So the side stream draws into a block of its own, `cot_mix_normalize` reads that one, and the block is copied
+        into `mixup.params` on the consumer's stream when the batch is handed over -- behind the previous step in stream order, in
+        front of this batch's loss.  The side stream's next draw waits (on the device) for that copy."""
+        mix = self.mixup
+        stream = torch.cuda.Stream(device=self.device)
+        ahead = mix.new_block()
+        handed = torch.cuda.Event()
+        first = True
+        inp = tgt = None
+        for next_input, next_target in self.loader:
+            with torch.cuda.stream(stream):
+                stream.wait_event(handed)
+                next_input = next_input.to(self.device, non_blocking=True).contiguous()
+                next_target = next_target.to(self.device, non_blocking=True)
+                mix.draw(next_input.shape, block=ahead)
+                next_input = mix.mix_normalize(next_input, self.mean, self.std, self.dtype, block=ahead)
+            if not first:
+                yield inp, tgt
+            else:
+                first = False
+            cur = torch.cuda.current_stream(self.device)
+            cur.wait_stream(stream)
+            mix.params.copy_(ahead, non_blocking=True)
+            handed.record(cur)
+            next_input.record_stream(cur)
+            next_target.record_stream(cur)
+            inp, tgt = next_input, next_target
+        if inp is not None:
+            yield inp, tgt
+
+    def _iter_plain(self):
         stream = torch.cuda.Stream(device=self.device)
         first = True
         inp = tgt = None

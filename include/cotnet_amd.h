@@ -493,6 +493,50 @@ int cot_conv1x1_lds_covers(int K, int k1, int two_slabs, int HW);
 int cot_input_normalize(const void* x_u8, void* y, const float* mean, const float* std, int64_t planes, int C, int HW,
                         int dtype, void* stream);
 
+/* ---- the recipe's mixup / CutMix and soft-target loss on the device (reference: datasets/mixup.py FastCollateMixup(mode='batch'),
+ * :282-299; mixup_target, :22-27; loss/cross_entropy.py SoftTargetCrossEntropy, :29-36).
+ * What changes per batch lives in ONE parameter block of 8 x 32-bit words in device memory (4-byte aligned).  The kernels read it when
+ * they EXECUTE and only read it, so a HIP graph that recorded them follows whatever the block holds at each replay; the caller orders
+ * its writes to the block on the stream, as for cot_sgd_step_lr's rate.
+ *   lam = float32(lambda), one_minus_lam = float32(1.0 - lambda) with the subtraction in double -- the reference forms both from the
+ *   double (mixup.py:27, :296); 1 - lam in fp32 would not match.  The box [yl, yh) x [xl, xh) is only ever compared with pixel
+ *   coordinates, never used as an address. */
+typedef struct cot_mix_params {
+    int32_t mode; /* 0 none, 1 mixup, 2 CutMix (any other value: as 0) */
+    float lam, one_minus_lam;
+    int32_t yl, yh, xl, xh, reserved;
+} cot_mix_params;
+
+/* cot_input_normalize with the batch-mode collate mixing folded into the same pass: x uint8 [N, C, H, W], partner of sample i is
+ * j = N-1-i, read from the unmodified input (y must not overlap x):
+ *     mode 1: u = rint(float(x_i)*lam + float(x_j)*one_minus_lam)   two fp32 products rounded separately, then added; half to even
+ *     mode 2: u = x_j inside the box, x_i outside;   mode 0: u = x_i
+ *     y = (u - mean[c]) / std[c]  exactly as cot_input_normalize (COT_F32 / COT_F16 / COT_BF16)
+ * N must be even (the reference asserts, mixup.py:303): odd N is COT_ERR_INVALID_ARG before any launch.  x and y are 16-byte aligned
+ * when H*W is a multiple of 16 (16 pixels per lane); otherwise the kernel works element by element and y only needs its element's
+ * alignment. */
+int cot_mix_normalize(const void* x_u8, void* y, const float* mean, const float* std, const void* params, int N, int C, int H, int W,
+                      int dtype, void* stream);
+
+/* Soft-target cross entropy against targets that are never materialised: logits [N, K] row-major (COT_F32 or COT_BF16), labels
+ * int64 [N], `params` the block above (only lam / one_minus_lam are read):
+ *     t[n,j] = lam*oh(j, y_n) + one_minus_lam*oh(j, y_{N-1-n}),  oh(j, y) = on if j == y else off,
+ *     off = smoothing/K, on = 1 - smoothing + off (formed in double, rounded to fp32 once); everything else in fp32.
+ * Labels are only compared with the column index: an out-of-range label matches no column and reads nothing.
+ * forward:  row_loss[n] = -sum_j t[n,j]*(logit[n,j] - lse_n), fp32 [N];  row_lse = a workspace of 4N floats that carries the rows'
+ *           log-sum-exp from forward to backward of the SAME call pair and is OPAQUE: its layout is not part of this interface and may
+ *           change (today: the row maximum, log(sum_j exp(logit - maximum)) summed in fp64 as a high and a low part, and the low part
+ *           of the fp64 row loss);  mean_loss = one fp32 element, the fp64 row losses added in a fixed order and rounded once (no
+ *           atomics: the same bits on every run).
+ * backward: dlogits[n,j] = g*(exp(logit[n,j] - lse_n)*sum_j t[n,j] - t[n,j])/N in the logits' dtype, formed in fp64 and rounded once
+ *           (the difference cancels wherever a probability meets its target; sum_j t is 1 up to the entries' fp32 rounding);
+ *           g = ONE fp32 element in device memory, read when the kernel runs.
+ * A block {0, 1.0f, 0.0f} gives LabelSmoothingCrossEntropy(smoothing); with smoothing = 0 plain cross entropy.  0 <= smoothing < 1. */
+int cot_soft_target_ce_forward(const void* logits, const void* labels, const void* params, double smoothing, void* row_loss,
+                               void* row_lse, void* mean_loss, int N, int K, int dtype, void* stream);
+int cot_soft_target_ce_backward(const void* logits, const void* labels, const void* params, double smoothing, const void* row_lse,
+                                const void* grad_out, void* dlogits, int N, int K, int dtype, void* stream);
+
 /* ---- training-mode BatchNorm2d fused with activation and residual add, NCHW.
  * Replaces nn.BatchNorm2d + in-place ReLU/SiLU (+ `x += residual`) sequences of the reference's blocks
  * (models/cotnet.py:231-235, :248-262, :89-90):
