@@ -29,6 +29,7 @@
 // Exactness: integer-valued data is bit-exact (exact products, exact fp32 sums); padded taps of gW are cleared by
 // SELECTION once per item (exact zeros whatever gO holds there, as the reference writes 0 without multiplying).
 #include "conv_lds_common.h"
+#include "cot_host.h"
 
 namespace cot {
 

@@ -18,6 +18,7 @@
 #include <initializer_list>
 
 #include "conv_lds_common.h"
+#include "cot_host.h"
 
 namespace cot {
 

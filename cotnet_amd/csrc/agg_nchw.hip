@@ -16,6 +16,7 @@
 //    The fused backward produces gX and gW from one pass over gO / x / w (5.25 elements of HBM traffic
 //    per output element instead of 6.25 for the reference's two kernels).
 #include "cot_common.h"
+#include "cot_host.h"
 
 namespace cot {
 
@@ -1124,8 +1125,6 @@ static int launch_bwd_k3(const T* gout, const T* x, const T* w, T* gx, T* gw, co
 }
 
 // packed-bf16 dot-product form of the fused backward (agg_dot2.hip): -1 = geometry not covered
-int agg_backward_nchw_dot2(const bf16_t* gout, const bf16_t* x, const bf16_t* w, bf16_t* gx, bf16_t* gw, const cot_agg_geom& g,
-                           hipStream_t s);
 template <typename T> static inline int try_dot2(const T*, const T*, const T*, T*, T*, const cot_agg_geom&, hipStream_t) { return -1; }
 template <> inline int try_dot2<bf16_t>(const bf16_t* gout, const bf16_t* x, const bf16_t* w, bf16_t* gx, bf16_t* gw,
                                         const cot_agg_geom& g, hipStream_t s) {

@@ -10,6 +10,7 @@
 // the contiguous block w[pixel][wc0*taps .. (wc0+V)*taps).  Threads with the same wc0 (the C/wC channels
 // sharing a weight) sit in the same wave for C <= 512 and their weight loads coalesce to one request.
 #include "cot_common.h"
+#include "cot_host.h"
 
 namespace cot {
 

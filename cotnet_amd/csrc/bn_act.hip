@@ -14,6 +14,7 @@
 // All kernels are HBM-bound.  Algorithmic traffic per element (e = storage bytes): forward 3e (+e with residual)
 // [stats read, apply read, write], backward 5e (+e) [reduce reads dy,x(,y); apply reads dy,x(,y), writes dx(,dres)].
 #include "cot_common.h"
+#include "cot_host.h"
 
 namespace cot {
 
@@ -493,8 +494,6 @@ __global__ __launch_bounds__(256) void bn_apply_bwd_fold(const T* __restrict__ d
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// the sign mask of the current call (set by cot_bn_act_{forward,backward}_mask around the call; NULL otherwise)
-thread_local uint8_t* t_bn_mask = nullptr;
 int g_bn_fold = 1;          // cot_set_tuning key 12 (default on since round 3: 202 fewer launches per CoTNet-50 step, profiles/r02_bn_fold_ab.txt)
 int g_bn_grid_cap = 4096;  // cot_set_tuning key 13: most workgroups of a flat (grid-stride) BatchNorm apply kernel
 static inline int pick_vec(size_t esize, int HW) {
@@ -523,7 +522,6 @@ static inline unsigned flat_grid(int64_t nvec) {
 // bytes of the ReLU sign mask for this tensor, 0 = not supported (the backward then reads the saved output): 8 elements per access
 // on every kernel family that can serve the tensor, i.e. 2-byte elements, planes that are multiples of 8, and not the one-wave fp64
 // path of tiny batches
-extern int g_bn_small_m;
 int64_t bn_relu_mask_bytes(int N, int C, int HW, int esize) {
     if (esize != 2 || HW % 8 != 0 || (int64_t)N * HW <= g_bn_small_m) return 0;
     return (int64_t)N * C * HW / 8;
@@ -538,10 +536,10 @@ int bn_workspace_floats(int N, int C) {
 template <typename T, int V, int ACT>
 static int bn_fwd_launch_act(const T* x, const T* res, T* y, const float* gamma, const float* beta, float* mean,
                              float* rstd, float* rmean, float* rvar, long long* nbt, float* ws, int N, int C, int HW,
-                             float eps, float mom, const float* ps, hipStream_t s) {
+                             float eps, float mom, const float* ps, uint8_t* mask, hipStream_t s) {
     int split, nper;
     pick_split(N, C, &split, &nper);
-    uint8_t* const mk = V == 8 ? t_bn_mask : nullptr;  // (read HERE: a launch macro may evaluate its arguments on another thread)
+    uint8_t* const mk = V == 8 ? mask : nullptr;
     COT_LAUNCH((bn_stats_partial<T, V>), dim3(C, split), dim3(256), 48 * sizeof(float), s, x, ws, N, C, HW, nper);
     if (g_bn_fold || ps) {  // (the per-sample scale lives in the kernels that walk a channel image by image)
         COT_LAUNCH((bn_apply_fwd_fold<T, V, ACT>), dim3(C, split), dim3(256), 0, s, x, res, y, (const float*)ws, gamma,
@@ -559,8 +557,8 @@ static int bn_fwd_launch_act(const T* x, const T* res, T* y, const float* gamma,
 template <typename T, int V>
 static int bn_fwd_launch(const T* x, const T* res, T* y, const float* gamma, const float* beta, float* mean,
                          float* rstd, float* rmean, float* rvar, long long* nbt, float* ws, int N, int C, int HW,
-                         float eps, float mom, int act, const float* ps, hipStream_t s) {
-#define BN_FA(A_) return bn_fwd_launch_act<T, V, A_>(x, res, y, gamma, beta, mean, rstd, rmean, rvar, nbt, ws, N, C, HW, eps, mom, ps, s)
+                         float eps, float mom, int act, const float* ps, uint8_t* mask, hipStream_t s) {
+#define BN_FA(A_) return bn_fwd_launch_act<T, V, A_>(x, res, y, gamma, beta, mean, rstd, rmean, rvar, nbt, ws, N, C, HW, eps, mom, ps, mask, s)
     if (act == ACT_RELU) BN_FA(ACT_RELU);
     if (act == ACT_SILU) BN_FA(ACT_SILU);
     BN_FA(ACT_NONE);
@@ -570,10 +568,10 @@ static int bn_fwd_launch(const T* x, const T* res, T* y, const float* gamma, con
 template <typename T, int V, int ACT>
 static int bn_bwd_launch_act(const T* dy, const T* x, const T* y, T* dx, T* dres, const float* gamma, const float* beta,
                              const float* mean, const float* rstd, float* dgamma, float* dbeta, float* ws, int N, int C,
-                             int HW, const float* ps, hipStream_t s) {
+                             int HW, const float* ps, const uint8_t* mask, hipStream_t s) {
     int split, nper;
     pick_split(N, C, &split, &nper);
-    const uint8_t* const mk = V == 8 ? t_bn_mask : nullptr;  // (read here, see bn_fwd_launch_act)
+    const uint8_t* const mk = V == 8 ? mask : nullptr;
     COT_LAUNCH((bn_bwd_reduce<T, V, ACT>), dim3(C, split), dim3(256), 48 * sizeof(float), s, dy, x, y, mean, rstd, gamma,
                beta, ws, N, C, HW, nper, ps, mk);
     if (g_bn_fold || ps) {
@@ -591,8 +589,8 @@ static int bn_bwd_launch_act(const T* dy, const T* x, const T* y, T* dx, T* dres
 template <typename T, int V>
 static int bn_bwd_launch(const T* dy, const T* x, const T* y, T* dx, T* dres, const float* gamma, const float* beta,
                          const float* mean, const float* rstd, float* dgamma, float* dbeta, float* ws, int N, int C,
-                         int HW, int act, const float* ps, hipStream_t s) {
-#define BN_BA(A_) return bn_bwd_launch_act<T, V, A_>(dy, x, y, dx, dres, gamma, beta, mean, rstd, dgamma, dbeta, ws, N, C, HW, ps, s)
+                         int HW, int act, const float* ps, const uint8_t* mask, hipStream_t s) {
+#define BN_BA(A_) return bn_bwd_launch_act<T, V, A_>(dy, x, y, dx, dres, gamma, beta, mean, rstd, dgamma, dbeta, ws, N, C, HW, ps, mask, s)
     if (act == ACT_RELU && y) BN_BA(ACT_RELU_Y);  // sign of the saved output (required when there was a residual)
     if (act == ACT_RELU) BN_BA(ACT_RELU);
     if (act == ACT_SILU) BN_BA(ACT_SILU);
@@ -961,13 +959,13 @@ static inline int bn_chan_rr(int64_t MV, int threads, int full) {
 template <typename T>
 int bn_act_forward(const void* x, const void* res, void* y, const float* gamma, const float* beta, float* mean,
                    float* rstd, float* rmean, float* rvar, long long* nbt, float* ws, int N, int C, int HW, float eps,
-                   float mom, int act, const float* ps, hipStream_t s) {
-#define BN_F(VV) return bn_fwd_launch<T, VV>((const T*)x, (const T*)res, (T*)y, gamma, beta, mean, rstd, rmean, rvar, nbt, ws, N, C, HW, eps, mom, act, ps, s)
+                   float mom, int act, const float* ps, uint8_t* mask, hipStream_t s) {
+#define BN_F(VV) return bn_fwd_launch<T, VV>((const T*)x, (const T*)res, (T*)y, gamma, beta, mean, rstd, rmean, rvar, nbt, ws, N, C, HW, eps, mom, act, ps, mask, s)
     // a sign mask is one byte per EIGHT elements: only the 8-element instances write / read it.  bn_relu_mask_bytes() hands out a
-    // mask size exactly for the geometries that take them; a call that reaches another instance with a mask set must not run
+    // mask size exactly for the geometries that take them; a call that reaches another instance with a mask given must not run
     // (forward: the backward would read a mask nobody wrote; backward: the mask pointer stands in for y and a kernel that reads y
     // would walk 16 times the mask's size -- ADVICE r4)
-    if (t_bn_mask && (sizeof(T) != 2 || pick_vec(sizeof(T), HW) != 8 || (int64_t)N * HW <= g_bn_small_m)) return -3;
+    if (mask && (sizeof(T) != 2 || pick_vec(sizeof(T), HW) != 8 || (int64_t)N * HW <= g_bn_small_m)) return -3;
     if ((int64_t)N * HW <= g_bn_small_m && !ps) {
         const dim3 grid(C), block(64);  // one wave per channel
 #define BN_SF(A_) COT_LAUNCH((bn_small_fwd<T, A_>), grid, block, 0, s, (const T*)x, (const T*)res, (T*)y, gamma, beta, mean, rstd, rmean, rvar, nbt, N, C, HW, eps, mom)
@@ -979,7 +977,7 @@ int bn_act_forward(const void* x, const void* res, void* y, const float* gamma, 
     }
     if (const int cv = bn_chan_vec<T, false>(N, C, HW)) {
         const dim3 grid(C), block(bn_chan_threads(N, C, HW, cv, bn_chan_rounds<T, false>(cv)));
-        uint8_t* const mk = cv == 8 ? t_bn_mask : nullptr;
+        uint8_t* const mk = cv == 8 ? mask : nullptr;
         const int rr = bn_chan_rr((int64_t)N * HW / cv, (int)block.x, bn_chan_rounds<T, false>(cv));
 #define BN_CFR(V_, A_, R_) COT_LAUNCH((bn_chan_fwd<T, V_, A_, R_>), grid, block, 0, s, (const T*)x, (const T*)res, (T*)y, gamma, beta, mean, rstd, rmean, rvar, nbt, N, C, HW, eps, mom, ps, (V_) == 8 ? mk : nullptr)
 #define BN_CF(V_, A_)                      \
@@ -1014,9 +1012,9 @@ int bn_act_forward(const void* x, const void* res, void* y, const float* gamma, 
 template <typename T>
 int bn_act_backward(const void* dy, const void* x, const void* y, void* dx, void* dres, const float* gamma,
                     const float* beta, const float* mean, const float* rstd, float* dgamma, float* dbeta, float* ws,
-                    int N, int C, int HW, int act, const float* ps, hipStream_t s) {
-#define BN_B(VV) return bn_bwd_launch<T, VV>((const T*)dy, (const T*)x, (const T*)y, (T*)dx, (T*)dres, gamma, beta, mean, rstd, dgamma, dbeta, ws, N, C, HW, act, ps, s)
-    if (t_bn_mask && (sizeof(T) != 2 || pick_vec(sizeof(T), HW) != 8 || (int64_t)N * HW <= g_bn_small_m)) return -3;  // (see bn_act_forward)
+                    int N, int C, int HW, int act, const float* ps, const uint8_t* mask, hipStream_t s) {
+#define BN_B(VV) return bn_bwd_launch<T, VV>((const T*)dy, (const T*)x, (const T*)y, (T*)dx, (T*)dres, gamma, beta, mean, rstd, dgamma, dbeta, ws, N, C, HW, act, ps, mask, s)
+    if (mask && (sizeof(T) != 2 || pick_vec(sizeof(T), HW) != 8 || (int64_t)N * HW <= g_bn_small_m)) return -3;  // (see bn_act_forward)
     if ((int64_t)N * HW <= g_bn_small_m && !ps) {
         const dim3 grid(C), block(64);  // one wave per channel
 #define BN_SB(A_) COT_LAUNCH((bn_small_bwd<T, A_>), grid, block, 0, s, (const T*)dy, (const T*)x, (const T*)y, (T*)dx, (T*)dres, gamma, beta, rstd, dgamma, dbeta, N, C, HW)
@@ -1029,7 +1027,7 @@ int bn_act_backward(const void* dy, const void* x, const void* y, void* dx, void
     }
     if (const int cv = bn_chan_vec<T, true>(N, C, HW)) {
         const dim3 grid(C), block(bn_chan_threads(N, C, HW, cv, bn_chan_rounds<T, true>(cv)));
-        const uint8_t* const mk = cv == 8 ? t_bn_mask : nullptr;
+        const uint8_t* const mk = cv == 8 ? mask : nullptr;
         const int rr = bn_chan_rr((int64_t)N * HW / cv, (int)block.x, bn_chan_rounds<T, true>(cv));
 #define BN_CBR(V_, A_, R_) COT_LAUNCH((bn_chan_bwd<T, V_, A_, R_>), grid, block, 0, s, (const T*)dy, (const T*)x, (const T*)y, (T*)dx, (T*)dres, gamma, beta, mean, rstd, dgamma, dbeta, N, C, HW, ps, (V_) == 8 ? mk : nullptr)
 #define BN_CB(V_, A_)                      \
@@ -1196,12 +1194,11 @@ int bn_rowstats(const float* rows, int N, int C, int H, int W, float eps, float 
 }
 // y = act(gamma * (x - mean_c) * rstd_c + beta [+ residual]) from GIVEN batch statistics (bf16; the flat apply kernel)
 int bn_apply_forward(const void* x, const void* res, void* y, const float* gamma, const float* beta, const float* mean, const float* rstd,
-                     int N, int C, int HW, int act, hipStream_t s) {
+                     int N, int C, int HW, int act, uint8_t* mask, hipStream_t s) {
     typedef bf16_t T;
     if (HW % 8 != 0) return -2;
     const int64_t nvec = (int64_t)N * C * HW / 8;
-    uint8_t* const mk = t_bn_mask;
-#define BN_AF(A_) COT_LAUNCH((bn_apply_fwd<T, 8, A_>), dim3(flat_grid(nvec)), dim3(256), 0, s, (const T*)x, (const T*)res, (T*)y, mean, rstd, gamma, beta, C, HW, nvec, mk)
+#define BN_AF(A_) COT_LAUNCH((bn_apply_fwd<T, 8, A_>), dim3(flat_grid(nvec)), dim3(256), 0, s, (const T*)x, (const T*)res, (T*)y, mean, rstd, gamma, beta, C, HW, nvec, mask)
     if (act == ACT_RELU) BN_AF(ACT_RELU);
     else if (act == ACT_SILU) BN_AF(ACT_SILU);
     else BN_AF(ACT_NONE);
@@ -1431,14 +1428,14 @@ int bn_act_backward_lay(const void* dy, const void* dy2, const void* x, const vo
 }
 
 template int bn_act_forward<float>(const void*, const void*, void*, const float*, const float*, float*, float*, float*,
-                                   float*, long long*, float*, int, int, int, float, float, int, const float*, hipStream_t);
+                                   float*, long long*, float*, int, int, int, float, float, int, const float*, uint8_t*, hipStream_t);
 template int bn_act_forward<bf16_t>(const void*, const void*, void*, const float*, const float*, float*, float*, float*,
-                                    float*, long long*, float*, int, int, int, float, float, int, const float*, hipStream_t);
+                                    float*, long long*, float*, int, int, int, float, float, int, const float*, uint8_t*, hipStream_t);
 template int bn_act_backward<float>(const void*, const void*, const void*, void*, void*, const float*, const float*,
-                                    const float*, const float*, float*, float*, float*, int, int, int, int, const float*,
+                                    const float*, const float*, float*, float*, float*, int, int, int, int, const float*, const uint8_t*,
                                     hipStream_t);
 template int bn_act_backward<bf16_t>(const void*, const void*, const void*, void*, void*, const float*, const float*,
-                                     const float*, const float*, float*, float*, float*, int, int, int, int, const float*,
+                                     const float*, const float*, float*, float*, float*, int, int, int, int, const float*, const uint8_t*,
                                      hipStream_t);
 
 }  // namespace cot

@@ -26,6 +26,7 @@
 // kernel (no atomics: bit-reproducible, and capturable in a HIP graph without a zero-fill node).
 #include "cot_common.h"
 #include "mfma_common.h"
+#include "cot_host.h"
 
 namespace cot {
 
@@ -389,7 +390,7 @@ int conv1x1_wgrad_reduce_launch(const float* part, int S, int M, int J, int has_
 
 // ------------------------------------------------------------------------------------------------------------------
 // host side
-extern int g_conv1x1_tune[4];  // [0] xcd remap (default 1), [1] MT override (0 = auto), [2] wgrad target waves, [3] launches of at least this many waves use ring depth 1 (0 = 8192)
+// g_conv1x1_tune: [0] xcd remap (default 1), [1] MT override (0 = auto), [2] wgrad target waves, [3] launches of at least this many waves use ring depth 1 (0 = 8192)
 int g_conv1x1_tune[4] = {1, 0, 2048, 0};
 int g_wgrad_cap_pct = 0;  // cot_set_tuning key 19: partial-sum bytes of a weight gradient as a percentage of its input bytes (0 = the kernels' defaults)
 

@@ -17,13 +17,9 @@
 // conv1x1.hip.  Output columns are in the weight tensor's own [ci][3][3] order, so no re-ordering on the way out.
 #include "cot_common.h"
 #include "mfma_common.h"
+#include "cot_host.h"
 
 namespace cot {
-
-int conv1x1_wgrad_reduce_launch(const float* part, int S, int M, int J, int has_bias, void* gw, void* gb,
-                                hipStream_t stream);  // conv1x1.hip
-extern int g_conv1x1_tune[4];
-extern int g_wgrad_cap_pct;
 
 __host__ __device__ inline int masks_padded(int HW) { return (HW + 127) / 128 * 128 + 128; }
 

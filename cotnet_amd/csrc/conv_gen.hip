@@ -30,6 +30,7 @@
 #include <algorithm>
 
 #include "mfma_common.h"
+#include "cot_host.h"
 
 namespace cot {
 

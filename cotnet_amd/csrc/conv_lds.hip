@@ -20,14 +20,9 @@
 #include "cot_common.h"
 #include "mfma_common.h"
 #include "conv_lds_common.h"
+#include "cot_host.h"
 
 namespace cot {
-extern int g_conv_ablate;  // (conv_lds2.hip; cot_set_tuning key 24)
-
-extern int g_conv_lds_tune[3];
-extern int g_conv_lds2_tune;
-extern int g_conv_k_tail;  // (conv_lds2.hip; cot_set_tuning key 54)
-int conv1x1_lds_gemm2(const C1LdsArgs& a0, hipStream_t stream);  // conv_lds2.hip
 
 // dst[c][r] = src[r][c]   (R x C row-major -> C x R row-major), 32x32 tiles through LDS.
 // pack = 1: the K-step-major form the LDS kernels read for the data gradient: dst[((r/32)*C + c)*32 + r%32] = src[r][c],
@@ -260,9 +255,8 @@ __global__ __launch_bounds__(64 * WAVES, 2) void conv1x1_lds_fwd(const C1LdsArgs
 
 // cot_conv3x3g_pack / cot_conv3x3g_*_packed (round 5): the weights of a layer change once per optimizer step, its two packings (forward,
 // data gradient) are each used once per step -- packing ahead of time saves no work but takes 32 small launches off the compute
-// stream's critical path (the host side packs on a side stream right after the optimizer step).  0 = pack and run (the ordinary entry
-// points), 1 = pack only, 2 = run on a packing made by an identical call in mode 1.
-thread_local int t_c3_pack = 0;
+// stream's critical path (the host side packs on a side stream right after the optimizer step).  `pack` of conv3x3g_lds_gemm: 0 = pack
+// and run (the ordinary entry points), 1 = pack only, 2 = run on a packing made by an identical call with pack = 1.
 
 // ====================================================================================================================
 // Grouped 3x3 convolution (stride 1, padding 1) -- CotLayer.key_embed[0] (models/cotnet.py:43-47; groups 4; CoXtLayer 8) --
@@ -828,7 +822,7 @@ static int c3res_rows(int KX, int Mreal) {
 }
 // -> -1: not covered (the caller takes the per-step ring); `ws`: the repacked weights' workspace as for conv3x3g_lds_gemm
 static int conv3x3g_res_gemm(const void* x, const void* w, void* y, void* ws, int N, int Cin, int Cout, int G, int H, int W, int mode,
-                             int accumulate, hipStream_t stream) {
+                             int accumulate, int pack, hipStream_t stream) {
     const int KX = (mode == 0 ? Cin : Cout) / G, Mreal = (mode == 0 ? Cout : Cin) / G, HW = H * W;
     if (!g_conv3x3_res || !conv3x3g_lds_covers(KX, Mreal, H, W)) return -1;
     const int MM = c3res_rows(KX, Mreal);
@@ -950,12 +944,12 @@ static int conv3x3g_res_gemm(const void* x, const void* w, void* y, void* ws, in
         };
         if (g_conv3x3_perm == 2 || overlap(slc) < overlap(8 * slc)) a.perm = 1;
     }
-    if (t_c3_pack != 2) {   // repack the weights: [G][NTAP][MM][KK]  (2 = `ws` already holds this call's packing: cot_conv3x3g_*_packed)
+    if (pack != 2) {   // repack the weights: [G][NTAP][MM][KK]  (2 = `ws` already holds this call's packing: cot_conv3x3g_*_packed)
         const int64_t total = (int64_t)G * NTAP * MM * KK;
         COT_LAUNCH(conv3x3g_repack_kernel, dim3((unsigned)ceil_div64(total, 256)), dim3(256), 0, stream, (const bf16_t*)w,
                    (bf16_t*)ws, G, MM, KX, KK, NTAP, mode, MBLK, a.perm);
         int rc = check_launch("conv3x3g_repack_kernel");
-        if (rc || t_c3_pack == 1) return rc;  // (1 = pack only: cot_conv3x3g_pack)
+        if (rc || pack == 1) return rc;  // (1 = pack only: cot_conv3x3g_pack)
     }
     if (flat) {
         if (K16) return launch_c3res<2, 1, 1, 1, 1>(a, blocks, stream);
@@ -986,11 +980,11 @@ bool conv3x3g_lds_covers(int KK, int MM, int H, int W) {
 // mode 0: y = conv(x, w);  mode 1: data gradient (x := dY, y := dX, weights transposed and flipped).  `ws`: the call's
 // workspace (>= G*10*MM*KK bf16).  Returns COT_OK, an error, or -1 when the geometry is not covered.
 int conv3x3g_lds_gemm(const void* x, const void* w, void* y, void* ws, int N, int Cin, int Cout, int G, int H, int W,
-                      int mode, int accumulate, hipStream_t stream) {
+                      int mode, int accumulate, int pack, hipStream_t stream) {
     const int KX = (mode == 0 ? Cin : Cout) / G, Mreal = (mode == 0 ? Cout : Cin) / G, HW = H * W;
     if (!conv3x3g_lds_covers(KX, Mreal, H, W)) return -1;
     {
-        const int rc = conv3x3g_res_gemm(x, w, y, ws, N, Cin, Cout, G, H, W, mode, accumulate, stream);
+        const int rc = conv3x3g_res_gemm(x, w, y, ws, N, Cin, Cout, G, H, W, mode, accumulate, pack, stream);
         if (rc != -1) return rc;
     }
     const int MBLK = Mreal > 128 ? Mreal / 128 : 1, MM = Mreal / MBLK;
@@ -1036,12 +1030,12 @@ int conv3x3g_lds_gemm(const void* x, const void* w, void* y, void* ws, int N, in
         a.tiles = ceil_div(H, TR);
         blocks = (int64_t)N * a.tiles * G;
     }
-    if (t_c3_pack != 2) {   // repack the weights: [G][NTAP][MM][KK]
+    if (pack != 2) {   // repack the weights: [G][NTAP][MM][KK]
         const int64_t total = (int64_t)G * NTAP * MM * KK;
         COT_LAUNCH(conv3x3g_repack_kernel, dim3((unsigned)ceil_div64(total, 256)), dim3(256), 0, stream, (const bf16_t*)w,
                    (bf16_t*)ws, G, MM, KX, KK, NTAP, mode, MBLK, 0);
         int rc = check_launch("conv3x3g_repack_kernel");
-        if (rc || t_c3_pack == 1) return rc;
+        if (rc || pack == 1) return rc;
     }
     if (flat) {
         if (K16) return launch_c3<2, 1, 1, 1, 1>(a, blocks, stream);
@@ -1268,8 +1262,6 @@ int conv1x1_wgrad_lds_splits(int N, int M, int J, int HW, int has_bias) {
     if (S < 1) S = 1;
     return (int)S;
 }
-
-int conv1x1_wgrad_reduce_launch(const float* part, int S, int M, int J, int has_bias, void* gw, void* gb, hipStream_t stream);
 
 int conv1x1_wgrad_lds_run(const void* gy, const void* x1, const void* x2, int k1, void* gw, void* gb, float* workspace, int N,
                           int J, int M, int HW, hipStream_t stream) {

@@ -22,10 +22,10 @@
 #include <algorithm>
 
 #include "conv_lds_common.h"
+#include "cot_host.h"
 
 namespace cot {
 
-extern int g_conv_lds_tune[3];
 // cot_set_tuning key 23: bit 0 = second-generation forward kernel (conv_lds.hip) instead of this one; bit 1 = fragment prefetch
 // off in the FLAT kernels (default on); bit 2 = fragment prefetch on in the BIG kernels (default off: it costs registers, i.e.
 // workgroups per CU, where the layers are bandwidth-bound)

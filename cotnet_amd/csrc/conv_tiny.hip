@@ -12,6 +12,7 @@
 // MFMA maps as in mfma_common.h (A: lane l holds row l&15, k = 8*(l>>4)..+7; B: column l&15; D: rows 4*(l>>4)+r, column l&15).
 // The data is a few hundred KB and L2-resident; the 2-byte gathers cost issue slots, not bandwidth.
 #include "mfma_common.h"
+#include "cot_host.h"
 
 namespace cot {
 

@@ -33,6 +33,7 @@
 #include "cot_common.h"
 #include "mfma_common.h"
 #include "conv_lds_common.h"
+#include "cot_host.h"
 
 namespace cot {
 
@@ -43,8 +44,6 @@ namespace cot {
 // of the input bytes (0 = 100); bits 16..23 = target workgroups per CU x 4 (0 = 4, i.e. one); bits 24..30 = forced slice
 // count (tests)
 int g_wgrad2_tune = 0;
-extern int g_conv_ablate;
-extern unsigned long long* g_debug_stamps;
 
 struct Wg2Args {
     const bf16_t* gy;
@@ -580,8 +579,6 @@ int conv1x1_wgrad2_splits(int N, int M, int J, int HW, int has_bias) {
     if (S < 1) S = 1;
     return (int)S;
 }
-
-int conv1x1_wgrad_reduce_launch(const float* part, int S, int M, int J, int has_bias, void* gw, void* gb, hipStream_t stream);
 
 // Sum of a FEW slices of a LARGE matrix (the deep layers: 0.26 .. 1 M outputs, 2 .. 16 slices).  The reduce kernel of
 // conv1x1.hip gives a workgroup 32 outputs and spreads the slices over its 8 lane groups -- right for the small matrices of

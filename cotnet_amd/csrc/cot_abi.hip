@@ -13,6 +13,7 @@
 #include <string>
 
 #include "cot_common.h"
+#include "cot_host.h"
 
 namespace cot {
 
@@ -93,202 +94,31 @@ static void annotate(const cot_agg_geom& g, int dtype, int layout, int kind, int
 // non-aggregation ops (kh == 0 marks them): kind 10/11/12 = 1x1 convolution forward / data gradient / weight gradient,
 // 13/14/15 = grouped 3x3, 20/21 = BatchNorm(+act) forward / backward; geom.N = N, .C = input channels, .W = output channels,
 // .H = pixels per image, .heads = groups, flags = op-specific (BatchNorm: bit 0 residual, bit 1 saved output read)
-static void annotate_op(int kind, int N, int Ci, int Co, int HW, int groups, int dtype, int flags) {
+static cot_agg_geom op_geom(int N, int Ci, int Co, int HW, int groups) {
     cot_agg_geom g;
     memset(&g, 0, sizeof(g));
     g.N = N; g.C = Ci; g.W = Co; g.H = HW; g.heads = groups;
-    annotate(g, dtype, 0, kind, flags);
+    return g;
 }
+// One per ABI call that launches: marks where the call's records begin (when the recorder is on) and stamps them on every exit
+struct Scope {
+    const bool on = enabled();
+    const cot_agg_geom g;
+    const int dtype, layout, kind, flags;
+    Scope(const cot_agg_geom& g_, int dtype_, int layout_, int kind_, int flags_) : g(g_), dtype(dtype_), layout(layout_), kind(kind_), flags(flags_) {
+        if (on) mark();
+    }
+    Scope(int kind_, int N, int Ci, int Co, int HW, int groups, int dtype_, int flags_) : Scope(op_geom(N, Ci, Co, HW, groups), dtype_, 0, kind_, flags_) {}
+    ~Scope() {
+        if (on) annotate(g, dtype, layout, kind, flags);
+    }
+};
 }  // namespace prof
 
-// implemented in agg_nchw.hip / agg_nhwc.hip / agg_mix.hip
-template <typename T>
-int agg_forward_nchw(const T*, const T*, T*, const cot_agg_geom&, int, int, hipStream_t, const char*);
-template <typename T>
-int agg_backward_nchw(const T*, const T*, const T*, T*, T*, const cot_agg_geom&, int, int, hipStream_t);
-template <typename T> int agg_forward_nhwc(const T*, const T*, T*, const cot_agg_geom&, int, int, int, hipStream_t);
-template <typename T>
-int agg_backward_nhwc(const T*, const T*, const T*, T*, T*, const cot_agg_geom&, int, int, int, hipStream_t);
-template <typename T>
-int aggmix_forward(const T*, const T*, const T*, T*, const cot_agg_geom&, int, int, int, int, hipStream_t);
-template <typename T>
-int aggmix_backward_input(const T*, const T*, const T*, T*, const cot_agg_geom&, int, int, int, int, int,
-                          hipStream_t);
-template <typename T>
-int aggmix_backward_weight(const T*, const T*, T*, T*, const cot_agg_geom&, int, int, int, int, hipStream_t);
-const char* last_kernel_mix();
-extern int g_mix_tune[3];  // agg_mix.hip: [0] = 1 generic kernels only, [1] = lanes a tiled workgroup aims for, [2] = pixels per lane
-int sgd_flat(void*, void*, void*, const void*, int64_t, float, float, float, float, int, int, int, hipStream_t);
-int sgd_flat_lr(void*, void*, void*, const void*, int64_t, const float*, float, float, float, int, int, int, hipStream_t);
-int ema_flat(void*, const void*, int64_t, float, int, hipStream_t);
-int bn_workspace_floats(int N, int C);
-int bn_act_lay_covers(int N, int C, int HW);
-int bn_tile_stats(const float*, int, int, int, float, float, float*, float*, float*, float*, long long*, hipStream_t);
-int bn_apply_forward(const void*, const void*, void*, const float*, const float*, const float*, const float*, int, int, int, int, hipStream_t);
-int bn_act_forward_lay(const void*, const void*, void*, void*, const float*, const float*, float*, float*, float*, float*, long long*, int,
-                       int, int, float, float, int, const float*, int, hipStream_t);
-int bn_act_backward_lay(const void*, const void*, const void*, const void*, void*, void*, const float*, const float*, const float*,
-                        const float*, float*, float*, int, int, int, int, const float*, int, hipStream_t);
-int64_t bn_relu_mask_bytes(int N, int C, int HW, int esize);
-extern thread_local uint8_t* t_bn_mask;
-extern thread_local int t_c3_pack;
-extern int g_bn_fold, g_bn_grid_cap, g_bn_small_m, g_bn_split_target;
-template <typename T>
-int bn_act_forward(const void*, const void*, void*, const float*, const float*, float*, float*, float*, float*, long long*,
-                   float*, int, int, int, float, float, int, const float*, hipStream_t);
-template <typename T>
-int bn_act_inference(const void*, const void*, void*, const float*, const float*, const float*, const float*, int, int, int,
-                     float, int, hipStream_t);
-template <typename T>
-int bn_act_backward(const void*, const void*, const void*, void*, void*, const float*, const float*, const float*,
-                    const float*, float*, float*, float*, int, int, int, int, const float*, hipStream_t);
-template <typename T>
-int agg_softmax_forward_nchw(const T*, const T*, T*, T*, const cot_agg_geom&, hipStream_t);
-template <typename T>
-int agg_softmax_backward_nchw(const T*, const T*, const T*, T*, T*, const cot_agg_geom&, hipStream_t);
-bool lr_covers(const cot_agg_geom&);
-int64_t lr_workspace_bytes(const cot_agg_geom&, size_t);
-const char* last_kernel_lr();
-template <typename T>
-int lr_forward(const T*, const T*, const T*, const float*, T*, T*, const cot_agg_geom&, hipStream_t);
-template <typename T>
-int lr_backward(const T*, const T*, const T*, const T*, const float*, const T*, T*, T*, T*, float*, void*, const cot_agg_geom&,
-                hipStream_t);
-template <typename T> int radix_gap(const void*, const void*, void*, int64_t, int, hipStream_t);
-template <typename T> int radix_mix(const void*, const void*, const void*, void*, int64_t, int, hipStream_t);
-template <typename T>
-int radix_mix_bwd(const void*, const void*, const void*, const void*, void*, void*, void*, int64_t, int, hipStream_t);
-// implemented in conv1x1.hip
-int conv1x1_gemm(const void*, const void*, int, const void*, const void*, void*, void*, int, int, int, int, int, int, int,
-                 hipStream_t);
-int conv1x1_wgrad_splits(int N, int M, int J, int HW, int has_bias);
-int conv1x1_wgrad(const void*, const void*, const void*, int, void*, void*, float*, int, int, int, int, hipStream_t);
-extern int g_conv1x1_tune[4];
-extern int g_wgrad_cap_pct;
-extern int g_wgrad_lds_cap_pct;
-extern int g_bn_chan;
-extern int g_bn_chan7;
-extern int g_stem_lds;
-// implemented in conv_lds.hip
-extern int g_conv_lds_tune[3];
-extern int g_conv3x3_ring;
-extern int g_conv3x3_res;
-extern int g_conv3x3_wsingle;
-extern int g_conv3x3_cols;
-extern int g_conv3x3_perm;
-extern int g_conv_flat_ns3;
-extern int g_conv_big_fill;
-extern int g_bn_chan_rr;
-extern int g_conv_big_xswz;
-extern int g_gn9_pack;
-extern int g_radix_pack7;
-extern int g_conv_lds2_tune;
-extern int g_conv_k_tail;
-extern int g_conv_ablate;
 unsigned long long* g_debug_stamps = nullptr;  // DIAGNOSTIC: see cot_debug_stamps
 static int g_grouped_tuned = 1;  // tuning key 36: grouped 1x1 convolutions group by group on the tuned kernels
 static int g_conv3x3_merge = 1;  // tuning key 37: merged-groups 3x3 weight gradient for group widths off the 8-channel grid
 static inline bool g_conv_lds_tune_wgrad_off() { return (g_conv_lds_tune[2] >> 2) & 1; }  // tuning key 17 bit 2 (A/B)
-bool conv1x1_lds_covers(int K, int k1, bool two_slabs, int HW);
-int conv1x1_lds_gemm(const void*, const void*, int, const void*, int, const void*, void*, void*, int, int, int, int, int, int,
-                     hipStream_t, int64_t xs = 0, int64_t ys = 0, float* stats = nullptr, const void* acc_src = nullptr,
-                     const void* acc_mask = nullptr);
-int gn9_stats_finalize(const float*, float*, float*, int, int, int, float, hipStream_t);
-int agg_gn9_forward_nchw(const bf16_t*, const bf16_t*, const float*, const float*, const bf16_t*, const bf16_t*, int, bf16_t*,
-                         const cot_agg_geom&, hipStream_t);
-int agg_gn9_backward_nchw_dot2(const bf16_t*, const bf16_t*, const bf16_t*, const float*, const float*, const bf16_t*, const bf16_t*, int,
-                               bf16_t*, bf16_t*, const cot_agg_geom&, hipStream_t);
-int transpose_bf16(const void* src, void* dst, int R, int C, int pack, hipStream_t stream);
-bool conv1x1_wgrad_lds_covers(int N, int HW, int M, int J);
-int conv1x1_wgrad_lds_splits(int N, int M, int J, int HW, int has_bias);
-int conv1x1_wgrad_lds_run(const void*, const void*, const void*, int, void*, void*, float*, int, int, int, int, hipStream_t);
-extern int g_wgrad2_tune;  // conv_wgrad2.hip (third-generation weight gradient)
-extern int g_pool_tile;    // pool3x3.hip (row-block pooling kernels)
-template <typename T> int subsample2(int bwd, const void* a, void* out, int64_t planes, int H, int W, hipStream_t stream);
-template <typename T> int avgpool2x2s2(int bwd, const void* a, void* out, int64_t planes, int H, int W, hipStream_t stream);
-bool conv1x1_wgrad2_covers(int N, int HW, int M, int J, int k1, bool two_slabs);
-int conv1x1_wgrad2_splits(int N, int M, int J, int HW, int has_bias);
-int conv1x1_wgrad2_run(const void*, const void*, const void*, int, void*, void*, float*, int, int, int, int, hipStream_t, int sy = 0,
-                       int sx = 0);
-bool conv3x3g_wgrad2_covers(int N, int Cin, int Cout, int G, int H, int W, int x_guard);
-int conv3x3g_wgrad2_splits(int N, int Cin, int Cout, int G, int HW);
-int conv3x3g_wgrad2_run(const void*, const void*, void*, const void*, float*, int, int, int, int, int, int, int, hipStream_t);
-int conv3x3g_lds_gemm(const void*, const void*, void*, void*, int, int, int, int, int, int, int, int, hipStream_t);
-// implemented in stem7x7.hip
-int stem7x7_splits(int N, int H, int W);
-int stem7x7_forward(const void*, const void*, void*, int, int, int, hipStream_t);
-int stem7x7_wgrad(const void*, const void*, void*, float*, int, int, int, hipStream_t);
-int stem3x3s2_splits(int N, int H, int W, int Co);
-int stem3x3s2_forward(const void*, const void*, void*, int, int, int, int, hipStream_t);
-int stem3x3s2_wgrad(const void*, const void*, void*, float*, int, int, int, int, hipStream_t);
-// implemented in pool3x3.hip
-template <typename T> int pool3x3s2(int, const void*, const void*, void*, int64_t, int, int, hipStream_t);
-// implemented in group_norm9.hip
-int gn9_forward(const void*, const void*, const void*, void*, float*, float*, int, int, int, float, int, hipStream_t);
-int gn9_backward(const void*, const void*, const float*, const float*, const void*, void*, void*, void*, float*, int, int,
-                 int, int, hipStream_t);
-int gn9_backward_params(const float* workspace, void* dgamma, void* dbeta, int N, int C, hipStream_t stream);
-int gn9f_forward(const void*, const void*, const void*, void*, float*, float*, int, int, int, float, hipStream_t);
-int gn9f_backward(const void*, const void*, const float*, const float*, const void*, void*, void*, void*, float*, int, int,
-                  int, hipStream_t);
-// implemented in conv_tiny.hip (one image of <= 256 pixels: the se branch's convolutions over the batch axis)
-extern int g_conv_tiny;
-int stem7x7_f32_forward(const void*, const void*, void*, int, int, int, hipStream_t);                       // stem7x7_f32.hip
-int stem7x7_f32_backward_weight(const void*, const void*, void*, float*, int, int, int, int, hipStream_t);
-bool conv_tiny_covers(int N, int Ci, int Co, int HW);
-int conv_tiny_forward(const void*, const void*, const void*, void*, int, int, int, hipStream_t);
-int conv_tiny_backward_data(const void*, const void*, void*, int, int, int, int, hipStream_t);
-int conv_tiny_backward_weight(const void*, const void*, void*, void*, int, int, int, hipStream_t);
-// implemented in conv_gen.hip (general grouped 1x1 / 3x3 convolutions, fp32 or bf16, any channel counts)
-int convg_forward(const void*, const void*, const void*, void*, int, int, int, int, int, int, int, int, int, hipStream_t);
-int convg_backward_data(const void*, const void*, void*, int, int, int, int, int, int, int, int, int, hipStream_t);
-int64_t convg_workspace(int, int, int, int, int, int, int);
-int convg_backward_weight(const void*, const void*, void*, void*, float*, int, int, int, int, int, int, int, int,
-                          hipStream_t);
-// implemented in conv3x3g.hip
-int64_t conv3x3g_masks_bytes(int H, int W);
-int conv3x3g_masks(void*, int, int, hipStream_t);
-int conv3x3g_gemm(const void*, const void*, void*, const void*, int, int, int, int, int, int, int, int, hipStream_t);
-int conv3x3g_wgrad_splits(int N, int Cin, int Cout, int G, int HW);
-int conv3x3g_wgrad(const void*, const void*, void*, const void*, float*, int, int, int, int, int, int, hipStream_t);
-template <typename T> int radix_gap_t(const void*, const void*, void*, int, int, int, int, hipStream_t);
-template <typename T> int se_gap(const void*, void*, int64_t, int, hipStream_t);
-template <typename T> int se_gate(const void*, const void*, void*, int64_t, int, hipStream_t);
-template <typename T> int se_gate_bwd(const void*, const void*, const void*, void*, void*, int64_t, int, hipStream_t);
-template <typename T>
-int radix_mix_logits(const void*, const void*, const void*, void*, void*, int, int, int, int, hipStream_t);
-template <typename T>
-int radix_mix_bwd_reduce(const void*, const void*, const void*, const void*, void*, int, int, int, int, hipStream_t);
-template <typename T>
-int radix_mix_bwd_apply(const void*, const void*, const void*, void*, void*, int, int, int, int, hipStream_t);
-template <typename T>
-int radix_gap_t_bn(const void*, const void*, void*, const float*, const float*, float*, float*, float*, float*, long long*, const float*,
-                   int, float, float, int, int, int, int, hipStream_t);
-int bn_stats_split(int N, int C);
-template <typename T> int bn_stats_sums_launch(const void*, float*, int, int, int, hipStream_t);
-template <typename T>
-int radix_mix_logits_bn(const void*, const void*, const void*, void*, void*, const float*, const float*, const float*, const float*, int,
-                        int, int, int, hipStream_t);
-template <typename T>
-int radix_mix_bwd_reduce_bn(const void*, const void*, const void*, const void*, void*, float*, const float*, const float*, const float*,
-                            const float*, int, int, int, int, hipStream_t);
-template <typename T>
-int radix_mix_bwd_apply_bn(const void*, const void*, const void*, const void*, const float*, void*, void*, const float*, const float*,
-                           const float*, const float*, float*, float*, int, int, int, int, hipStream_t);
-int agg_forward_rowstats_nchw(const bf16_t*, const bf16_t*, bf16_t*, float*, const float*, const float*, const bf16_t*, const bf16_t*, int,
-                              const cot_agg_geom&, hipStream_t);
-int bn_rowstats(const float*, int, int, int, int, float, float, float*, float*, float*, float*, long long*, hipStream_t);
-template <typename T>
-int bn_batch_stats(const void*, float*, float*, float*, float*, long long*, float*, int, int, int, float, float, hipStream_t);
-int input_normalize(const void*, void*, const float*, const float*, int64_t, int, int, int, hipStream_t);  // input_norm.hip
-int mix_normalize(const void*, void*, const float*, const float*, const void*, int, int, int, int, int, hipStream_t);  // mix_loss.hip
-int soft_ce_forward(const void*, const void*, const void*, double, float*, float*, float*, int, int, int, hipStream_t);
-int soft_ce_backward(const void*, const void*, const void*, double, const float*, const float*, void*, int, int, int, hipStream_t);
-const char* last_kernel_nchw();
-const char* last_kernel_nhwc();
-int set_tuning_nchw(int key, int value);
-int set_tuning_dot2(int key, int value);
-int xchg_mode();
 
 static int out_size(int in, int k, int s, int p, int d) {
     // python: int((in + 2p - (d(k-1)+1)) / s + 1) -- float division, truncation toward zero
@@ -367,6 +197,20 @@ using namespace cot;
         default: return set_error(COT_ERR_UNSUPPORTED, "unknown dtype %d", dtype);    \
     }
 
+// the families with fp32 and bf16 instantiations only
+#define DISPATCH_F32_BF16(dtype, WHO, CALL)                                                                        \
+    switch (dtype) {                                                                                               \
+        case COT_F32: { typedef float T; return CALL; }                                                            \
+        case COT_BF16: { typedef bf16_t T; return CALL; }                                                          \
+        default: return set_error(COT_ERR_UNSUPPORTED, WHO ": dtype %d (float32 / bfloat16 only)", dtype);         \
+    }
+
+static int check_running_pair(const float* running_mean, const float* running_var) {
+    if ((running_mean == NULL) != (running_var == NULL))
+        return set_error(COT_ERR_INVALID_ARG, "running_mean and running_var must be given together");
+    return COT_OK;
+}
+
 static int check_align16(std::initializer_list<const void*> ptrs) {
     for (const void* p : ptrs)
         if (p && ((uintptr_t)p % 16) != 0)
@@ -391,147 +235,66 @@ const char* cot_status_string(int status) {
 
 int cot_agg_out_size(int in, int k, int s, int p, int d) { return out_size(in, k, s, p, d); }
 
+// cot_set_tuning: one row per key -- where the value goes, how it is normalised, and what it is in a line (the full account is at the
+// global's definition).  Keys 0-8 go to set_tuning_nchw, 29-34 to set_tuning_dot2; 35 is unused.
+static int tn_raw(int v) { return v; }
+static int tn_bool(int v) { return v ? 1 : 0; }
+static int tn_012(int v) { return v == 2 ? 2 : (v ? 1 : 0); }
+static int tn_nonneg(int v) { return v > 0 ? v : 0; }
+struct TuneRow {
+    int key;
+    int* target;
+    int (*norm)(int);
+    const char* what;
+};
+static const TuneRow kTuning[] = {
+    {9, &g_conv1x1_tune[0], tn_raw, "first-generation 1x1: XCD remap"},
+    {10, &g_conv1x1_tune[1], tn_raw, "first-generation 1x1: MT override (0 = auto)"},
+    {11, &g_conv1x1_tune[2], tn_raw, "first-generation 1x1 weight gradient: target waves"},
+    {12, &g_bn_fold, tn_bool, "BatchNorm: statistics merged in the apply kernel's prologue"},
+    {13, &g_bn_grid_cap, [](int v) { return v > 0 ? v : 4096; }, "BatchNorm: most workgroups of a flat apply kernel"},
+    {14, &g_conv1x1_tune[3], tn_raw, "first-generation 1x1: waves from which the ring depth is 1"},
+    {15, &g_conv_lds_tune[0], tn_raw, "LDS kernels on / off"},
+    {16, &g_conv_lds_tune[1], tn_raw, "LDS kernels: images per FLAT tile (0 = by plane size)"},
+    {17, &g_conv_lds_tune[2], tn_raw, "LDS kernels: A/B bits (bit 2 weight gradient off, bit 5 transposed weight copy)"},
+    {18, &g_bn_small_m, tn_nonneg, "BatchNorm: samples per channel up to which the fp64 path is taken"},
+    {19, &g_wgrad_cap_pct, tn_nonneg, "weight gradient: partial-sum cap in percent of the input bytes"},
+    {20, &g_wgrad_lds_cap_pct, tn_nonneg, "LDS weight gradient: the same cap"},
+    {21, &g_bn_chan, tn_nonneg, "channel-resident BatchNorm: 0 off, 1 on, 256 / 512 / 1024 on with that workgroup size"},
+    {22, &g_conv_tiny, tn_bool, "one-image 1x1 kernels"},
+    {23, &g_conv_lds2_tune, tn_raw, "third-generation 1x1: A/B bits"},
+    {24, &g_conv_ablate, tn_raw, "DIAGNOSTIC: timing ablations of the third-generation 1x1 kernel (results become wrong)"},
+    {25, &g_wgrad2_tune, tn_raw, "third-generation weight gradient: A/B bits"},
+    {26, &g_dry_run, tn_bool, "dry run: record launches instead of issuing them (see cot_launch_log)"},
+    {27, &g_pool_tile, tn_bool, "row-block pooling kernels"},
+    {28, &g_bn_split_target, [](int v) { return v > 0 ? v : 1024; }, "streaming BatchNorm: workgroups aimed for"},
+    {36, &g_grouped_tuned, tn_bool, "grouped 1x1 convolutions group by group on the tuned kernels"},
+    {37, &g_conv3x3_merge, tn_bool, "merged-groups 3x3 weight gradient"},
+    {38, &g_conv3x3_ring, [](int v) { return v >= 5 ? 5 : 3; }, "3x3 per-step ring depth"},
+    {39, &g_conv3x3_res, tn_012, "chunk-resident 3x3: 0 off, 1 groups of >= 24 channels, 2 also 16-channel groups"},
+    {40, &g_bn_chan7, tn_bool, "channel-resident BatchNorm: 7-element accesses"},
+    {41, &g_stem_lds, tn_bool, "7x7 stem: input rows staged in LDS"},
+    {42, &g_conv3x3_wsingle, tn_012, "chunk-resident 3x3: one weight buffer"},
+    {43, &g_conv_flat_ns3, tn_012, "third-generation 1x1: three-stage FLAT tiles"},
+    {44, &g_conv3x3_cols, tn_012, "chunk-resident 3x3: 512- or 256-column tiles"},
+    {45, &g_conv3x3_perm, tn_012, "chunk-resident 3x3: K order inside a chunk"},
+    {46, &g_conv_big_fill, tn_nonneg, "third-generation 1x1: workgroups below which BIG tiles take narrower channel blocks"},
+    {47, &g_bn_chan_rr, tn_bool, "channel-resident BatchNorm: short-round instances"},
+    {48, &g_conv_big_xswz, [](int v) { return v & 7; }, "third-generation 1x1: LDS permutation bits"},
+    {49, &g_gn9_pack, tn_bool, "GroupNorm-9: several (image, group) pairs per wave on small planes"},
+    {50, &g_radix_pack7, tn_bool, "radix tail: 8 planes of 7 x 7 per wave"},
+    {51, &g_mix_tune[0], tn_bool, "mixed aggregation: generic kernels only"},
+    {52, &g_mix_tune[1], [](int v) { return v >= 64 ? v : 256; }, "mixed aggregation: lanes a workgroup aims for"},
+    {53, &g_mix_tune[2], [](int v) { return v == 1 || v == 2 || v == 4 ? v : 0; }, "mixed aggregation: pixels per lane"},
+    {54, &g_conv_k_tail, tn_bool, "third-generation 1x1: reduction depths off the 32-channel grid"},
+};
+
 int cot_set_tuning(int key, int value) {
-    if (key >= 9 && key <= 11) {
-        g_conv1x1_tune[key - 9] = value;
-        return COT_OK;
-    }
-    if (key == 12) {
-        g_bn_fold = value ? 1 : 0;
-        return COT_OK;
-    }
-    if (key == 14) {
-        g_conv1x1_tune[3] = value;
-        return COT_OK;
-    }
-    if (key >= 15 && key <= 17) {
-        g_conv_lds_tune[key - 15] = value;
-        return COT_OK;
-    }
-    if (key == 38) {
-        g_conv3x3_ring = value >= 5 ? 5 : 3;
-        return COT_OK;
-    }
-    if (key == 39) {
-        g_conv3x3_res = value == 2 ? 2 : (value ? 1 : 0);
-        return COT_OK;
-    }
-    if (key == 18) {
-        g_bn_small_m = value > 0 ? value : 0;
-        return COT_OK;
-    }
-    if (key == 13) {
-        g_bn_grid_cap = value > 0 ? value : 4096;
-        return COT_OK;
-    }
-    if (key == 22) {
-        g_conv_tiny = value ? 1 : 0;
-        return COT_OK;
-    }
-    if (key == 23) {
-        g_conv_lds2_tune = value;
-        return COT_OK;
-    }
-    if (key == 26) {  // dry run: record launches instead of issuing them (see cot_launch_log)
-        g_dry_run = value ? 1 : 0;
-        return COT_OK;
-    }
-    if (key == 25) {
-        g_wgrad2_tune = value;
-        return COT_OK;
-    }
-    if (key == 27) {
-        g_pool_tile = value ? 1 : 0;
-        return COT_OK;
-    }
-    if (key == 28) {
-        g_bn_split_target = value > 0 ? value : 1024;
-        return COT_OK;
-    }
-    if (key == 24) {  // DIAGNOSTIC: timing ablations of the third-generation 1x1 kernel (results become wrong)
-        g_conv_ablate = value;
-        return COT_OK;
-    }
-    if (key == 45) {
-        g_conv3x3_perm = value == 2 ? 2 : (value ? 1 : 0);
-        return COT_OK;
-    }
-    if (key == 44) {
-        g_conv3x3_cols = value == 2 ? 2 : (value ? 1 : 0);
-        return COT_OK;
-    }
-    if (key == 43) {
-        g_conv_flat_ns3 = value == 2 ? 2 : (value ? 1 : 0);
-        return COT_OK;
-    }
-    if (key == 46) {
-        g_conv_big_fill = value > 0 ? value : 0;
-        return COT_OK;
-    }
-    if (key == 47) {
-        g_bn_chan_rr = value ? 1 : 0;
-        return COT_OK;
-    }
-    if (key == 48) {
-        g_conv_big_xswz = value & 7;
-        return COT_OK;
-    }
-    if (key == 49) {
-        g_gn9_pack = value ? 1 : 0;
-        return COT_OK;
-    }
-    if (key == 50) {
-        g_radix_pack7 = value ? 1 : 0;
-        return COT_OK;
-    }
-    if (key == 51) {
-        g_mix_tune[0] = value ? 1 : 0;
-        return COT_OK;
-    }
-    if (key == 52) {
-        g_mix_tune[1] = value >= 64 ? value : 256;
-        return COT_OK;
-    }
-    if (key == 53) {
-        g_mix_tune[2] = value == 1 || value == 2 || value == 4 ? value : 0;
-        return COT_OK;
-    }
-    if (key == 42) {
-        g_conv3x3_wsingle = value == 2 ? 2 : (value ? 1 : 0);
-        return COT_OK;
-    }
-    if (key == 41) {
-        g_stem_lds = value ? 1 : 0;
-        return COT_OK;
-    }
-    if (key == 40) {
-        g_bn_chan7 = value ? 1 : 0;
-        return COT_OK;
-    }
-    if (key == 21) {
-        g_bn_chan = value > 0 ? value : 0;  // 0 off, 1 on, 256 / 512 / 1024: on with that workgroup size (A/B)
-        return COT_OK;
-    }
-    if (key == 20) {
-        g_wgrad_lds_cap_pct = value > 0 ? value : 0;
-        return COT_OK;
-    }
-    if (key == 19) {
-        g_wgrad_cap_pct = value > 0 ? value : 0;
-        return COT_OK;
-    }
-    if (key == 37) {
-        g_conv3x3_merge = value ? 1 : 0;
-        return COT_OK;
-    }
-    if (key == 36) {
-        g_grouped_tuned = value ? 1 : 0;
-        return COT_OK;
-    }
-    if (key == 54) {
-        g_conv_k_tail = value ? 1 : 0;
-        return COT_OK;
-    }
+    for (const TuneRow& r : kTuning)
+        if (r.key == key) {
+            *r.target = r.norm(value);
+            return COT_OK;
+        }
     if (key >= 29 && key <= 34) {
         set_tuning_dot2(key - 29, value);
         return COT_OK;
@@ -615,8 +378,9 @@ int64_t cot_conv1x1_workspace(int N, int Ci, int Co, int HW, int has_bias) {
     return ((wt > part ? wt : part) + 255) / 256 * 256;
 }
 
-static int cot_conv1x1_forward_impl(const void* x1, const void* x2, int c1, const void* weight, const void* bias, void* y, int N,
+int cot_conv1x1_forward(const void* x1, const void* x2, int c1, const void* weight, const void* bias, void* y, int N,
                         int Ci, int Co, int HW, int dtype, void* stream) {
+    prof::Scope scope(10, N, Ci, Co, HW, 1, dtype, 0);
     int rc = conv1x1_validate(N, Ci, Co, HW, c1, x2 != nullptr, dtype, Ci);
     if (rc) return rc;
     if (!x1 || !weight || !y) return set_error(COT_ERR_INVALID_ARG, "NULL device pointer");
@@ -628,14 +392,6 @@ static int cot_conv1x1_forward_impl(const void* x1, const void* x2, int c1, cons
         if (rc != -1) return rc;
     }
     return conv1x1_gemm(x1, x2, c1, weight, bias, y, nullptr, Co, N, Ci, Co, HW, 0, 0, (hipStream_t)stream);
-}
-int cot_conv1x1_forward(const void* x1, const void* x2, int c1, const void* weight, const void* bias, void* y, int N,
-                        int Ci, int Co, int HW, int dtype, void* stream) {
-    const bool p = prof::enabled();
-    if (p) prof::mark();
-    const int rc = cot_conv1x1_forward_impl(x1, x2, c1, weight, bias, y, N, Ci, Co, HW, dtype, stream);
-    if (p) prof::annotate_op(10, N, Ci, Co, HW, 1, dtype, 0);
-    return rc;
 }
 
 /* ---- GroupNorm-9 fused into its neighbours (SURVEY 7.6 / VERDICT r3 J1): statistics out of the producing convolution's
@@ -657,10 +413,8 @@ int cot_conv1x1_forward_stats(const void* x1, const void* x2, int c1, const void
     if (dtype != COT_BF16) return set_error(COT_ERR_UNSUPPORTED, "cot_conv1x1_forward_stats: COT_BF16 only");
     if (!cot_conv1x1_stats_covers(Ci, c1, x2 != nullptr, HW))
         return set_error(COT_ERR_UNSUPPORTED, "cot_conv1x1_forward_stats: geometry not covered (cot_conv1x1_stats_covers)");
-    const bool p = prof::enabled();
-    if (p) prof::mark();
+    prof::Scope scope(10, N, Ci, Co, HW, 1, dtype, 0);
     rc = conv1x1_lds_gemm(x1, x2, c1, weight, 0, bias, y, nullptr, Co, N, Ci, Co, HW, 0, (hipStream_t)stream, 0, 0, stats);
-    if (p) prof::annotate_op(10, N, Ci, Co, HW, 1, dtype, 0);
     if (rc == -1) return set_error(COT_ERR_UNSUPPORTED, "cot_conv1x1_forward_stats: geometry not covered (cot_conv1x1_stats_covers)");
     return rc;
 }
@@ -676,8 +430,7 @@ int cot_bn_tile_stats_finalize(const float* stats, float* save_mean, float* save
                                int64_t* num_batches_tracked, int N, int C, int HW, float eps, float momentum, void* stream) {
     if (N <= 0 || C <= 0 || HW <= 0) return set_error(COT_ERR_INVALID_ARG, "bad geometry N=%d C=%d HW=%d", N, C, HW);
     if (!stats || !save_mean || !save_rstd) return set_error(COT_ERR_INVALID_ARG, "NULL device pointer");
-    if ((running_mean == NULL) != (running_var == NULL))
-        return set_error(COT_ERR_INVALID_ARG, "running_mean and running_var must be given together");
+    if (check_running_pair(running_mean, running_var)) return COT_ERR_INVALID_ARG;
     return bn_tile_stats(stats, N, C, HW, eps, momentum, save_mean, save_rstd, running_mean, running_var, (long long*)num_batches_tracked,
                          (hipStream_t)stream);
 }
@@ -693,13 +446,11 @@ int cot_agg_gn9_forward(const void* x, const void* logits, const float* mean, co
     if (!x || !logits || !mean || !rstd || !gamma || !beta || !out) return set_error(COT_ERR_INVALID_ARG, "NULL device pointer");
     if ((rc = check_align16({x, logits, out}))) return rc;
     if (dtype != COT_BF16 || groups_per_image <= 0) return set_error(COT_ERR_UNSUPPORTED, "cot_agg_gn9_*: COT_BF16 only");
-    const bool p = prof::enabled();
-    if (p) prof::mark();
+    prof::Scope scope(*g, dtype, COT_NCHW, 0, 0);  // (same algorithmic bytes as the plain aggregation: x, logits read, out written)
     rc = agg_gn9_forward_nchw((const bf16_t*)x, (const bf16_t*)logits, mean, rstd, (const bf16_t*)gamma, (const bf16_t*)beta,
                               groups_per_image, (bf16_t*)out, *g, (hipStream_t)stream);
     if (rc == COT_ERR_UNSUPPORTED) set_error(rc, "cot_agg_gn9_forward: geometry not covered (3x3, stride 1, pad 1, one head)");
     else g_kernel = last_kernel_nchw();
-    if (p) prof::annotate(*g, dtype, COT_NCHW, 0, 0);  // (same algorithmic bytes as the plain aggregation: x, logits read, out written)
     return rc;
 }
 // ---- aggregation forward that also emits the following BatchNorm's row statistics (agg_fwd_nchw_k3_lds<ST = 1>), and their finalize
@@ -714,22 +465,19 @@ int cot_agg_forward_rowstats(const void* x, const void* w, void* out, float* row
         return set_error(COT_ERR_INVALID_ARG, "GroupNorm prologue: rstd / gamma / beta / groups_per_image missing");
     if ((rc = check_align16({x, w, out, rowstats}))) return rc;
     if (dtype != COT_BF16) return set_error(COT_ERR_UNSUPPORTED, "cot_agg_forward_rowstats: COT_BF16 only");
-    const bool p = prof::enabled();
-    if (p) prof::mark();
+    prof::Scope scope(*g, dtype, COT_NCHW, 0, 0);
     rc = agg_forward_rowstats_nchw((const bf16_t*)x, (const bf16_t*)w, (bf16_t*)out, rowstats, gn_mean, gn_rstd, (const bf16_t*)gn_gamma,
                                    (const bf16_t*)gn_beta, groups_per_image, *g, (hipStream_t)stream);
     if (rc == COT_ERR_UNSUPPORTED)
         return set_error(rc, "cot_agg_forward_rowstats: geometry not covered (3x3, stride 1, pad 1, one head, C / wC <= 8, the LDS kernel's planes)");
     g_kernel = last_kernel_nchw();
-    if (p) prof::annotate(*g, dtype, COT_NCHW, 0, 0);
     return rc;
 }
 int cot_bn_rowstats_finalize(const float* rowstats, float* save_mean, float* save_rstd, float* running_mean, float* running_var,
                              int64_t* num_batches_tracked, int N, int C, int H, int W, float eps, float momentum, void* stream) {
     if (!rowstats || !save_mean || !save_rstd) return set_error(COT_ERR_INVALID_ARG, "NULL device pointer");
     if (N <= 0 || C <= 0 || H <= 0 || W <= 0) return set_error(COT_ERR_INVALID_ARG, "bad N/C/H/W");
-    if ((running_mean == NULL) != (running_var == NULL))
-        return set_error(COT_ERR_INVALID_ARG, "running_mean and running_var must be given together");
+    if (check_running_pair(running_mean, running_var)) return COT_ERR_INVALID_ARG;
     return bn_rowstats(rowstats, N, C, H, W, eps, momentum, save_mean, save_rstd, running_mean, running_var, (long long*)num_batches_tracked,
                        (hipStream_t)stream);
 }
@@ -741,19 +489,18 @@ int cot_agg_gn9_backward(const void* gout, const void* x, const void* logits, co
     if ((rc = check_align16({gout, x, logits, gx, gw}))) return rc;
     if (dtype != COT_BF16 || groups_per_image <= 0) return set_error(COT_ERR_UNSUPPORTED, "cot_agg_gn9_*: COT_BF16 only");
     const bool k3 = g->kh == 3 && g->kw == 3 && g->sh == 1 && g->sw == 1 && g->ph == 1 && g->pw == 1 && g->dh == 1 && g->dw == 1;
-    const bool p = prof::enabled();
-    if (p) prof::mark();
+    prof::Scope scope(*g, dtype, COT_NCHW, 1, 3);
     rc = k3 ? agg_gn9_backward_nchw_dot2((const bf16_t*)gout, (const bf16_t*)x, (const bf16_t*)logits, mean, rstd, (const bf16_t*)gamma,
                                          (const bf16_t*)beta, groups_per_image, (bf16_t*)gx, (bf16_t*)gw, *g, (hipStream_t)stream)
             : -1;
     if (rc == -1) return set_error(COT_ERR_UNSUPPORTED, "cot_agg_gn9_backward: geometry not covered (cot_gn9_fused_covers)");
     g_kernel = "agg_bwd_nchw_k3_dot2<gx,gw,gn9>";
-    if (p) prof::annotate(*g, dtype, COT_NCHW, 1, 3);
     return rc;
 }
 
-static int cot_conv1x1_backward_data_impl(const void* gy, const void* weight, void* gx1, void* gx2, int c1, int accumulate,
+int cot_conv1x1_backward_data(const void* gy, const void* weight, void* gx1, void* gx2, int c1, int accumulate,
                               void* workspace, int N, int Ci, int Co, int HW, int dtype, void* stream) {
+    prof::Scope scope(11, N, Ci, Co, HW, 1, dtype, 0);
     int rc = conv1x1_validate(N, Ci, Co, HW, c1, gx2 != nullptr, dtype, Co);
     if (rc) return rc;
     if (!gy || !weight || !gx1 || !workspace) return set_error(COT_ERR_INVALID_ARG, "NULL device pointer");
@@ -799,26 +546,16 @@ int cot_conv1x1_backward_data_relu_res(const void* gy, const void* weight, void*
         return set_error(COT_ERR_UNSUPPORTED, "cot_conv1x1_backward_data_relu_res: N=%d %d->%d HW=%d is off the LDS kernels (_covers)", N, Ci, Co, HW);
     int rc = check_align16({gy, weight, gx, gout});
     if (rc) return rc;
-    const bool p = prof::enabled();
-    if (p) prof::mark();
+    prof::Scope scope(11, N, Ci, Co, HW, 1, dtype, 0);
     rc = conv1x1_lds_gemm(gy, nullptr, Co, weight, 2, nullptr, gx, nullptr, Ci, N, Co, Ci, HW, 0, (hipStream_t)stream, 0, 0, nullptr, gout,
                           relu_mask);
     if (rc == -1) return set_error(COT_ERR_UNSUPPORTED, "cot_conv1x1_backward_data_relu_res: the kernel refused N=%d %d->%d HW=%d", N, Ci, Co, HW);
-    if (p) prof::annotate_op(11, N, Ci, Co, HW, 1, dtype, 0);
     return rc;
 }
 
-int cot_conv1x1_backward_data(const void* gy, const void* weight, void* gx1, void* gx2, int c1, int accumulate,
-                              void* workspace, int N, int Ci, int Co, int HW, int dtype, void* stream) {
-    const bool p = prof::enabled();
-    if (p) prof::mark();
-    const int rc = cot_conv1x1_backward_data_impl(gy, weight, gx1, gx2, c1, accumulate, workspace, N, Ci, Co, HW, dtype, stream);
-    if (p) prof::annotate_op(11, N, Ci, Co, HW, 1, dtype, 0);
-    return rc;
-}
-
-static int cot_conv1x1_backward_weight_impl(const void* gy, const void* x1, const void* x2, int c1, void* gweight, void* gbias,
+int cot_conv1x1_backward_weight(const void* gy, const void* x1, const void* x2, int c1, void* gweight, void* gbias,
                                 void* workspace, int N, int Ci, int Co, int HW, int dtype, void* stream) {
+    prof::Scope scope(12, N, Ci, Co, HW, 1, dtype, 0);
     int rc = conv1x1_validate(N, Ci, Co, HW, c1, x2 != nullptr, dtype, 8);
     if (rc) return rc;
     if (!gy || !x1 || !gweight || !workspace) return set_error(COT_ERR_INVALID_ARG, "NULL device pointer");
@@ -835,14 +572,6 @@ static int cot_conv1x1_backward_weight_impl(const void* gy, const void* x1, cons
     if (conv1x1_wgrad_lds_covers(N, HW, Co, Ci) && !g_conv_lds_tune_wgrad_off())
         return conv1x1_wgrad_lds_run(gy, x1, x2, c1, gweight, gbias, (float*)workspace, N, Ci, Co, HW, (hipStream_t)stream);
     return conv1x1_wgrad(gy, x1, x2, c1, gweight, gbias, (float*)workspace, N, Ci, Co, HW, (hipStream_t)stream);
-}
-int cot_conv1x1_backward_weight(const void* gy, const void* x1, const void* x2, int c1, void* gweight, void* gbias,
-                                void* workspace, int N, int Ci, int Co, int HW, int dtype, void* stream) {
-    const bool p = prof::enabled();
-    if (p) prof::mark();
-    const int rc = cot_conv1x1_backward_weight_impl(gy, x1, x2, c1, gweight, gbias, workspace, N, Ci, Co, HW, dtype, stream);
-    if (p) prof::annotate_op(12, N, Ci, Co, HW, 1, dtype, 0);
-    return rc;
 }
 
 static int conv3x3g_validate(int N, int Cin, int Cout, int G, int H, int W, int dtype, int kdim_per_group) {
@@ -909,32 +638,26 @@ int64_t cot_conv3x3g_workspace(int N, int Cin, int Cout, int groups, int H, int 
     return ws;
 }
 
-static int cot_conv3x3g_forward_impl(const void* x, const void* weight, void* y, const void* masks, void* workspace, int N, int Cin,
+int cot_conv3x3g_forward(const void* x, const void* weight, void* y, const void* masks, void* workspace, int N, int Cin,
                          int Cout, int groups, int H, int W, int dtype, void* stream) {
     int rc = conv3x3g_validate(N, Cin, Cout, groups, H, W, dtype, Cin / (groups > 0 ? groups : 1));
     if (rc) return rc;
+    prof::Scope scope(13, N, Cin, Cout, H * W, groups, dtype, 0);
     if (!x || !weight || !y || !masks || !workspace) return set_error(COT_ERR_INVALID_ARG, "NULL device pointer");
     if ((rc = check_align16({x, weight, y, masks, workspace}))) return rc;
     if (conv3x3g_general(Cin, Cout, groups, dtype))
         return convg_forward(x, weight, nullptr, y, N, Cin, Cout, groups, H, W, 3, 0, dtype, (hipStream_t)stream);
-    rc = conv3x3g_lds_gemm(x, weight, y, workspace, N, Cin, Cout, groups, H, W, 0, 0, (hipStream_t)stream);
+    rc = conv3x3g_lds_gemm(x, weight, y, workspace, N, Cin, Cout, groups, H, W, 0, 0, /*pack=*/0, (hipStream_t)stream);
     if (rc != -1) return rc;
     return conv3x3g_gemm(x, weight, y, masks, N, Cin, Cout, groups, H, W, 0, 0, (hipStream_t)stream);
 }
-int cot_conv3x3g_forward(const void* x, const void* weight, void* y, const void* masks, void* workspace, int N, int Cin,
-                         int Cout, int groups, int H, int W, int dtype, void* stream) {
-    const bool p = prof::enabled();
-    if (p) prof::mark();
-    const int rc = cot_conv3x3g_forward_impl(x, weight, y, masks, workspace, N, Cin, Cout, groups, H, W, dtype, stream);
-    if (p) prof::annotate_op(13, N, Cin, Cout, H * W, groups, dtype, 0);
-    return rc;
-}
 
-static int cot_conv3x3g_backward_data_impl(const void* gy, const void* weight, void* gx, int accumulate, const void* masks,
+int cot_conv3x3g_backward_data(const void* gy, const void* weight, void* gx, int accumulate, const void* masks,
                                void* workspace, int N, int Cin, int Cout, int groups, int H, int W, int dtype,
                                void* stream) {
     int rc = conv3x3g_validate(N, Cin, Cout, groups, H, W, dtype, Cout / (groups > 0 ? groups : 1));
     if (rc) return rc;
+    prof::Scope scope(14, N, Cin, Cout, H * W, groups, dtype, 0);
     if (!gy || !weight || !gx || !masks || !workspace) return set_error(COT_ERR_INVALID_ARG, "NULL device pointer");
     if ((rc = check_align16({gy, weight, gx, masks, workspace}))) return rc;
     if (conv3x3g_general(Cin, Cout, groups, dtype))
@@ -946,27 +669,14 @@ static int cot_conv3x3g_backward_data_impl(const void* gy, const void* weight, v
     // at B = 64 (the forward does not: 1012 vs 1140, 1237 vs 2058 us; profiles/r06_deep_stem_kernel_choice.log)
     const bool wide_dense = groups == 1 && W > 128;
     if (!wide_dense) {
-        rc = conv3x3g_lds_gemm(gy, weight, gx, workspace, N, Cin, Cout, groups, H, W, 1, accumulate ? 1 : 0, (hipStream_t)stream);
+        rc = conv3x3g_lds_gemm(gy, weight, gx, workspace, N, Cin, Cout, groups, H, W, 1, accumulate ? 1 : 0, /*pack=*/0, (hipStream_t)stream);
         if (rc != -1) return rc;
     }
     return conv3x3g_gemm(gy, weight, gx, masks, N, Cin, Cout, groups, H, W, 1, accumulate ? 1 : 0, (hipStream_t)stream);
 }
-int cot_conv3x3g_backward_data(const void* gy, const void* weight, void* gx, int accumulate, const void* masks,
-                               void* workspace, int N, int Cin, int Cout, int groups, int H, int W, int dtype,
-                               void* stream) {
-    const bool p = prof::enabled();
-    if (p) prof::mark();
-    const int rc = cot_conv3x3g_backward_data_impl(gy, weight, gx, accumulate, masks, workspace, N, Cin, Cout, groups, H, W, dtype, stream);
-    if (p) prof::annotate_op(14, N, Cin, Cout, H * W, groups, dtype, 0);
-    return rc;
-}
 
 // ---- packings made ahead of time (round 5): cot_conv3x3g_pack fills `packed` with exactly what the forward (mode 0) / data-gradient
 // (mode 1) call of the same geometry would pack into its workspace, the _packed entry points run on it without packing.
-struct C3PackScope {
-    explicit C3PackScope(int m) { t_c3_pack = m; }
-    ~C3PackScope() { t_c3_pack = 0; }
-};
 int64_t cot_conv3x3g_packed_bytes(int Cin, int Cout, int groups) {
     if (Cin <= 0 || Cout <= 0 || groups <= 0 || Cin % groups || Cout % groups) return 0;
     const int64_t kpf = ((Cin / groups) + 31) / 32 * 32, kpd = ((Cout / groups) + 31) / 32 * 32;
@@ -980,9 +690,8 @@ int cot_conv3x3g_pack(const void* weight, void* packed, int mode, int N, int Cin
     if ((rc = check_align16({weight, packed}))) return rc;
     if (dtype != COT_BF16 || conv3x3g_general(Cin, Cout, groups, dtype))
         return set_error(COT_ERR_UNSUPPORTED, "cot_conv3x3g_pack: this convolution does not run on packed weights (general kernels)");
-    C3PackScope scope(1);
     // (x / y are not touched in pack-only mode: the planner needs the geometry alone)
-    rc = conv3x3g_lds_gemm(packed, weight, packed, packed, N, Cin, Cout, groups, H, W, mode, 0, (hipStream_t)stream);
+    rc = conv3x3g_lds_gemm(packed, weight, packed, packed, N, Cin, Cout, groups, H, W, mode, 0, /*pack=*/1, (hipStream_t)stream);
     if (rc == -1) return set_error(COT_ERR_UNSUPPORTED, "cot_conv3x3g_pack: geometry off the LDS kernels (they gather the weights in place)");
     return rc;
 }
@@ -993,13 +702,8 @@ int cot_conv3x3g_forward_packed(const void* x, const void* packed, void* y, int 
     if (!x || !packed || !y) return set_error(COT_ERR_INVALID_ARG, "NULL device pointer");
     if ((rc = check_align16({x, packed, y}))) return rc;
     if (dtype != COT_BF16 || conv3x3g_general(Cin, Cout, groups, dtype)) return set_error(COT_ERR_UNSUPPORTED, "cot_conv3x3g_forward_packed: general kernels");
-    const bool p = prof::enabled();
-    if (p) prof::mark();
-    {
-        C3PackScope scope(2);
-        rc = conv3x3g_lds_gemm(x, packed, y, const_cast<void*>(packed), N, Cin, Cout, groups, H, W, 0, 0, (hipStream_t)stream);
-    }
-    if (p) prof::annotate_op(13, N, Cin, Cout, H * W, groups, dtype, 0);
+    prof::Scope scope(13, N, Cin, Cout, H * W, groups, dtype, 0);
+    rc = conv3x3g_lds_gemm(x, packed, y, const_cast<void*>(packed), N, Cin, Cout, groups, H, W, 0, 0, /*pack=*/2, (hipStream_t)stream);
     if (rc == -1) return set_error(COT_ERR_UNSUPPORTED, "cot_conv3x3g_forward_packed: geometry off the LDS kernels");
     return rc;
 }
@@ -1010,21 +714,19 @@ int cot_conv3x3g_backward_data_packed(const void* gy, const void* packed, void* 
     if (!gy || !packed || !gx) return set_error(COT_ERR_INVALID_ARG, "NULL device pointer");
     if ((rc = check_align16({gy, packed, gx}))) return rc;
     if (dtype != COT_BF16 || conv3x3g_general(Cin, Cout, groups, dtype)) return set_error(COT_ERR_UNSUPPORTED, "cot_conv3x3g_backward_data_packed: general kernels");
-    const bool p = prof::enabled();
-    if (p) prof::mark();
-    {
-        C3PackScope scope(2);
-        rc = conv3x3g_lds_gemm(gy, packed, gx, const_cast<void*>(packed), N, Cin, Cout, groups, H, W, 1, accumulate ? 1 : 0, (hipStream_t)stream);
-    }
-    if (p) prof::annotate_op(14, N, Cin, Cout, H * W, groups, dtype, 0);
+    prof::Scope scope(14, N, Cin, Cout, H * W, groups, dtype, 0);
+    rc = conv3x3g_lds_gemm(gy, packed, gx, const_cast<void*>(packed), N, Cin, Cout, groups, H, W, 1, accumulate ? 1 : 0, /*pack=*/2,
+                           (hipStream_t)stream);
     if (rc == -1) return set_error(COT_ERR_UNSUPPORTED, "cot_conv3x3g_backward_data_packed: geometry off the LDS kernels");
     return rc;
 }
 
-static int cot_conv3x3g_backward_weight_impl(const void* gy, const void* x, void* gweight, const void* masks, void* workspace, int N,
-                                 int Cin, int Cout, int groups, int H, int W, int dtype, int x_guard, void* stream) {
+int cot_conv3x3g_backward_weight_guarded(const void* gy, const void* x, void* gweight, const void* masks, void* workspace, int N,
+                                         int Cin, int Cout, int groups, int H, int W, int dtype, int x_guard_elems, void* stream) {
+    const int x_guard = x_guard_elems < 0 ? 0 : x_guard_elems;
     int rc = conv3x3g_validate(N, Cin, Cout, groups, H, W, dtype, 8);
     if (rc) return rc;
+    prof::Scope scope(15, N, Cin, Cout, H * W, groups, dtype, 0);
     if (!gy || !x || !gweight || !masks || !workspace) return set_error(COT_ERR_INVALID_ARG, "NULL device pointer");
     if ((rc = check_align16({gy, x, gweight, masks, workspace}))) return rc;
     if (conv3x3g_general(Cin, Cout, groups, dtype)) {
@@ -1049,15 +751,6 @@ static int cot_conv3x3g_backward_weight_impl(const void* gy, const void* x, void
     rc = conv3x3g_wgrad2_run(gy, x, gweight, masks, (float*)workspace, N, Cin, Cout, groups, H, W, x_guard, (hipStream_t)stream);
     if (rc >= 0) return rc;
     return conv3x3g_wgrad(gy, x, gweight, masks, (float*)workspace, N, Cin, Cout, groups, H, W, (hipStream_t)stream);
-}
-int cot_conv3x3g_backward_weight_guarded(const void* gy, const void* x, void* gweight, const void* masks, void* workspace, int N,
-                                         int Cin, int Cout, int groups, int H, int W, int dtype, int x_guard_elems, void* stream) {
-    const bool p = prof::enabled();
-    if (p) prof::mark();
-    const int rc = cot_conv3x3g_backward_weight_impl(gy, x, gweight, masks, workspace, N, Cin, Cout, groups, H, W, dtype,
-                                                     x_guard_elems < 0 ? 0 : x_guard_elems, stream);
-    if (p) prof::annotate_op(15, N, Cin, Cout, H * W, groups, dtype, 0);
-    return rc;
 }
 int cot_conv3x3g_backward_weight(const void* gy, const void* x, void* gweight, const void* masks, void* workspace, int N,
                                  int Cin, int Cout, int groups, int H, int W, int dtype, void* stream) {
@@ -1151,6 +844,8 @@ int cot_local_relation_backward(const void* gout, const void* q, const void* k, 
     return rc;
 }
 
+// (rejects every dtype but fp32 / bf16 with DISPATCH_F32_BF16's own text: after it, and after tail_bn_check, that macro's default
+// branch is unreachable)
 static int tail_check(int64_t planes, int HW, int dtype) {
     if (planes <= 0 || HW <= 0) return set_error(COT_ERR_INVALID_ARG, "non-positive planes/HW");
     if (dtype != COT_F32 && dtype != COT_BF16)
@@ -1163,8 +858,7 @@ int cot_radix_gap(const void* y, const void* k, void* gap, int64_t planes, int H
     if (rc) return rc;
     if (!y || !k || !gap) return set_error(COT_ERR_INVALID_ARG, "NULL device pointer");
     if ((rc = check_align16({y, k}))) return rc;
-    return dtype == COT_F32 ? radix_gap<float>(y, k, gap, planes, HW, (hipStream_t)stream)
-                            : radix_gap<bf16_t>(y, k, gap, planes, HW, (hipStream_t)stream);
+    DISPATCH_F32_BF16(dtype, "radix tail", radix_gap<T>(y, k, gap, planes, HW, (hipStream_t)stream));
 }
 
 int cot_se_gap(const void* x, void* gap, int64_t planes, int HW, int dtype, void* stream) {
@@ -1172,16 +866,14 @@ int cot_se_gap(const void* x, void* gap, int64_t planes, int HW, int dtype, void
     if (rc) return rc;
     if (!x || !gap) return set_error(COT_ERR_INVALID_ARG, "NULL device pointer");
     if ((rc = check_align16({x}))) return rc;
-    return dtype == COT_F32 ? se_gap<float>(x, gap, planes, HW, (hipStream_t)stream)
-                            : se_gap<bf16_t>(x, gap, planes, HW, (hipStream_t)stream);
+    DISPATCH_F32_BF16(dtype, "radix tail", se_gap<T>(x, gap, planes, HW, (hipStream_t)stream));
 }
 int cot_se_gate(const void* x, const void* logit, void* out, int64_t planes, int HW, int dtype, void* stream) {
     int rc = tail_check(planes, HW, dtype);
     if (rc) return rc;
     if (!x || !logit || !out) return set_error(COT_ERR_INVALID_ARG, "NULL device pointer");
     if ((rc = check_align16({x, out}))) return rc;
-    return dtype == COT_F32 ? se_gate<float>(x, logit, out, planes, HW, (hipStream_t)stream)
-                            : se_gate<bf16_t>(x, logit, out, planes, HW, (hipStream_t)stream);
+    DISPATCH_F32_BF16(dtype, "radix tail", se_gate<T>(x, logit, out, planes, HW, (hipStream_t)stream));
 }
 int cot_se_gate_backward(const void* g, const void* x, const void* logit, void* gx, void* glogit, int64_t planes, int HW,
                          int dtype, void* stream) {
@@ -1189,8 +881,7 @@ int cot_se_gate_backward(const void* g, const void* x, const void* logit, void* 
     if (rc) return rc;
     if (!g || !x || !logit || !gx || !glogit) return set_error(COT_ERR_INVALID_ARG, "NULL device pointer");
     if ((rc = check_align16({g, x, gx}))) return rc;
-    return dtype == COT_F32 ? se_gate_bwd<float>(g, x, logit, gx, glogit, planes, HW, (hipStream_t)stream)
-                            : se_gate_bwd<bf16_t>(g, x, logit, gx, glogit, planes, HW, (hipStream_t)stream);
+    DISPATCH_F32_BF16(dtype, "radix tail", se_gate_bwd<T>(g, x, logit, gx, glogit, planes, HW, (hipStream_t)stream));
 }
 
 int cot_radix_mix(const void* y, const void* k, const void* attn, void* out, int64_t planes, int HW, int dtype,
@@ -1199,8 +890,7 @@ int cot_radix_mix(const void* y, const void* k, const void* attn, void* out, int
     if (rc) return rc;
     if (!y || !k || !attn || !out) return set_error(COT_ERR_INVALID_ARG, "NULL device pointer");
     if ((rc = check_align16({y, k, out}))) return rc;
-    return dtype == COT_F32 ? radix_mix<float>(y, k, attn, out, planes, HW, (hipStream_t)stream)
-                            : radix_mix<bf16_t>(y, k, attn, out, planes, HW, (hipStream_t)stream);
+    DISPATCH_F32_BF16(dtype, "radix tail", radix_mix<T>(y, k, attn, out, planes, HW, (hipStream_t)stream));
 }
 
 int cot_radix_mix_backward(const void* gout, const void* y, const void* k, const void* attn, void* gy, void* gk,
@@ -1209,8 +899,7 @@ int cot_radix_mix_backward(const void* gout, const void* y, const void* k, const
     if (rc) return rc;
     if (!gout || !y || !k || !attn || !gy || !gk || !gattn) return set_error(COT_ERR_INVALID_ARG, "NULL device pointer");
     if ((rc = check_align16({gout, y, k, gy, gk}))) return rc;
-    return dtype == COT_F32 ? radix_mix_bwd<float>(gout, y, k, attn, gy, gk, gattn, planes, HW, (hipStream_t)stream)
-                            : radix_mix_bwd<bf16_t>(gout, y, k, attn, gy, gk, gattn, planes, HW, (hipStream_t)stream);
+    DISPATCH_F32_BF16(dtype, "radix tail", radix_mix_bwd<T>(gout, y, k, attn, gy, gk, gattn, planes, HW, (hipStream_t)stream));
 }
 
 int cot_radix_gap_t(const void* y, const void* k, void* gapT, int N, int C, int HW, int dtype, void* stream) {
@@ -1222,8 +911,7 @@ int cot_radix_gap_t_lay(const void* y, const void* k, void* gapT, int N, int C, 
     if (N <= 0 || C <= 0) return set_error(COT_ERR_INVALID_ARG, "non-positive N=%d C=%d", N, C);
     if (!y || !gapT) return set_error(COT_ERR_INVALID_ARG, "NULL device pointer");  // k == NULL: pool y alone
     if ((rc = check_align16({y, k}))) return rc;
-    return dtype == COT_F32 ? radix_gap_t<float>(y, k, gapT, N, C, HW, lay, (hipStream_t)stream)
-                            : radix_gap_t<bf16_t>(y, k, gapT, N, C, HW, lay, (hipStream_t)stream);
+    DISPATCH_F32_BF16(dtype, "radix tail", radix_gap_t<T>(y, k, gapT, N, C, HW, lay, (hipStream_t)stream));
 }
 
 int cot_radix_mix_logits(const void* y, const void* k, const void* logitsT, void* out, void* attn, int N, int C, int HW,
@@ -1237,8 +925,7 @@ int cot_radix_mix_logits_lay(const void* y, const void* k, const void* logitsT, 
     if (N <= 0 || C <= 0) return set_error(COT_ERR_INVALID_ARG, "non-positive N=%d C=%d", N, C);
     if (!y || !k || !logitsT || !out || !attn) return set_error(COT_ERR_INVALID_ARG, "NULL device pointer");
     if ((rc = check_align16({y, k, out}))) return rc;
-    return dtype == COT_F32 ? radix_mix_logits<float>(y, k, logitsT, out, attn, N, C, HW, lay, (hipStream_t)stream)
-                            : radix_mix_logits<bf16_t>(y, k, logitsT, out, attn, N, C, HW, lay, (hipStream_t)stream);
+    DISPATCH_F32_BF16(dtype, "radix tail", radix_mix_logits<T>(y, k, logitsT, out, attn, N, C, HW, lay, (hipStream_t)stream));
 }
 
 int cot_radix_mix_backward_reduce(const void* gout, const void* y, const void* k, const void* attn, void* glogitsT, int N,
@@ -1252,8 +939,7 @@ int cot_radix_mix_backward_reduce_lay(const void* gout, const void* y, const voi
     if (N <= 0 || C <= 0) return set_error(COT_ERR_INVALID_ARG, "non-positive N=%d C=%d", N, C);
     if (!gout || !y || !k || !attn || !glogitsT) return set_error(COT_ERR_INVALID_ARG, "NULL device pointer");
     if ((rc = check_align16({gout, y, k}))) return rc;
-    return dtype == COT_F32 ? radix_mix_bwd_reduce<float>(gout, y, k, attn, glogitsT, N, C, HW, lay, (hipStream_t)stream)
-                            : radix_mix_bwd_reduce<bf16_t>(gout, y, k, attn, glogitsT, N, C, HW, lay, (hipStream_t)stream);
+    DISPATCH_F32_BF16(dtype, "radix tail", radix_mix_bwd_reduce<T>(gout, y, k, attn, glogitsT, N, C, HW, lay, (hipStream_t)stream));
 }
 
 int cot_radix_mix_backward_apply(const void* gout, const void* attn, const void* ggapT, void* gy, void* gk, int N, int C,
@@ -1267,8 +953,7 @@ int cot_radix_mix_backward_apply_lay(const void* gout, const void* attn, const v
     if (N <= 0 || C <= 0) return set_error(COT_ERR_INVALID_ARG, "non-positive N=%d C=%d", N, C);
     if (!gout || !attn || !ggapT || !gy || !gk) return set_error(COT_ERR_INVALID_ARG, "NULL device pointer");
     if ((rc = check_align16({gout, gy, gk}))) return rc;
-    return dtype == COT_F32 ? radix_mix_bwd_apply<float>(gout, attn, ggapT, gy, gk, N, C, HW, lay, (hipStream_t)stream)
-                            : radix_mix_bwd_apply<bf16_t>(gout, attn, ggapT, gy, gk, N, C, HW, lay, (hipStream_t)stream);
+    DISPATCH_F32_BF16(dtype, "radix tail", radix_mix_bwd_apply<T>(gout, attn, ggapT, gy, gk, N, C, HW, lay, (hipStream_t)stream));
 }
 
 // ---- BatchNorm + SiLU of the aggregation's output folded into the radix tail (radix_tail.hip; models/cotnet.py:88-104)
@@ -1277,17 +962,11 @@ int cot_bn_batch_stats(const void* x, float* save_mean, float* save_rstd, float*
                        void* stream) {
     if (!x || !save_mean || !save_rstd || !workspace) return set_error(COT_ERR_INVALID_ARG, "NULL device pointer");
     if (N <= 0 || C <= 0 || HW <= 0) return set_error(COT_ERR_INVALID_ARG, "bad N/C/HW");
-    if ((running_mean == NULL) != (running_var == NULL))
-        return set_error(COT_ERR_INVALID_ARG, "running_mean and running_var must be given together");
+    if (check_running_pair(running_mean, running_var)) return COT_ERR_INVALID_ARG;
     int rc = check_align16({x});
     if (rc) return rc;
-    if (dtype == COT_F32)
-        return bn_batch_stats<float>(x, save_mean, save_rstd, running_mean, running_var, (long long*)num_batches_tracked, workspace,
-                                     N, C, HW, eps, momentum, (hipStream_t)stream);
-    if (dtype == COT_BF16)
-        return bn_batch_stats<bf16_t>(x, save_mean, save_rstd, running_mean, running_var, (long long*)num_batches_tracked, workspace,
-                                      N, C, HW, eps, momentum, (hipStream_t)stream);
-    return set_error(COT_ERR_UNSUPPORTED, "cot_bn_batch_stats: dtype %d (float32 / bfloat16 only)", dtype);
+    DISPATCH_F32_BF16(dtype, "cot_bn_batch_stats", bn_batch_stats<T>(x, save_mean, save_rstd, running_mean, running_var, (long long*)num_batches_tracked,
+                                                                    workspace, N, C, HW, eps, momentum, (hipStream_t)stream));
 }
 static int tail_bn_check(int N, int C, int HW, int dtype, const char* what) {
     int rc = tail_check((int64_t)N * C, HW, dtype);
@@ -1300,9 +979,7 @@ int cot_bn_stats_sums(const void* x, float* workspace, int N, int C, int HW, int
     if (N <= 0 || C <= 0 || HW <= 0) return set_error(COT_ERR_INVALID_ARG, "bad N/C/HW");
     int rc = check_align16({x, workspace});
     if (rc) return rc;
-    if (dtype == COT_F32) return bn_stats_sums_launch<float>(x, workspace, N, C, HW, (hipStream_t)stream);
-    if (dtype == COT_BF16) return bn_stats_sums_launch<bf16_t>(x, workspace, N, C, HW, (hipStream_t)stream);
-    return set_error(COT_ERR_UNSUPPORTED, "cot_bn_stats_sums: dtype %d (float32 / bfloat16 only)", dtype);
+    DISPATCH_F32_BF16(dtype, "cot_bn_stats_sums", bn_stats_sums_launch<T>(x, workspace, N, C, HW, (hipStream_t)stream));
 }
 int cot_radix_gap_t_bn(const void* a, const void* k, void* gapT, const float* gamma, const float* beta, float* save_mean,
                        float* save_rstd, float* running_mean, float* running_var, int64_t* num_batches_tracked, const float* workspace,
@@ -1310,16 +987,12 @@ int cot_radix_gap_t_bn(const void* a, const void* k, void* gapT, const float* ga
     int rc = tail_bn_check(N, C, HW, dtype, "cot_radix_gap_t_bn");
     if (rc) return rc;
     if (!a || !k || !gapT || !gamma || !beta || !save_mean || !save_rstd) return set_error(COT_ERR_INVALID_ARG, "NULL device pointer");
-    if ((running_mean == NULL) != (running_var == NULL))
-        return set_error(COT_ERR_INVALID_ARG, "running_mean and running_var must be given together");
+    if (check_running_pair(running_mean, running_var)) return COT_ERR_INVALID_ARG;
     if ((rc = check_align16({a, k, workspace}))) return rc;
     const int split = workspace ? bn_stats_split(N, C) : 0;
-    return dtype == COT_F32 ? radix_gap_t_bn<float>(a, k, gapT, gamma, beta, save_mean, save_rstd, running_mean, running_var,
-                                                    (long long*)num_batches_tracked, workspace, split, eps, momentum, N, C, HW, lay,
-                                                    (hipStream_t)stream)
-                            : radix_gap_t_bn<bf16_t>(a, k, gapT, gamma, beta, save_mean, save_rstd, running_mean, running_var,
-                                                     (long long*)num_batches_tracked, workspace, split, eps, momentum, N, C, HW, lay,
-                                                     (hipStream_t)stream);
+    DISPATCH_F32_BF16(dtype, "radix tail", radix_gap_t_bn<T>(a, k, gapT, gamma, beta, save_mean, save_rstd, running_mean, running_var,
+                                                             (long long*)num_batches_tracked, workspace, split, eps, momentum, N, C, HW, lay,
+                                                             (hipStream_t)stream));
 }
 int cot_radix_mix_logits_bn(const void* a, const void* k, const void* logitsT, void* out, void* attn, const float* gamma,
                             const float* beta, const float* save_mean, const float* save_rstd, int N, int C, int HW, int lay, int dtype,
@@ -1329,10 +1002,8 @@ int cot_radix_mix_logits_bn(const void* a, const void* k, const void* logitsT, v
     if (!a || !k || !logitsT || !out || !attn || !gamma || !beta || !save_mean || !save_rstd)
         return set_error(COT_ERR_INVALID_ARG, "NULL device pointer");
     if ((rc = check_align16({a, k, out}))) return rc;
-    return dtype == COT_F32 ? radix_mix_logits_bn<float>(a, k, logitsT, out, attn, gamma, beta, save_mean, save_rstd, N, C, HW, lay,
-                                                         (hipStream_t)stream)
-                            : radix_mix_logits_bn<bf16_t>(a, k, logitsT, out, attn, gamma, beta, save_mean, save_rstd, N, C, HW, lay,
-                                                          (hipStream_t)stream);
+    DISPATCH_F32_BF16(dtype, "radix tail", radix_mix_logits_bn<T>(a, k, logitsT, out, attn, gamma, beta, save_mean, save_rstd, N, C, HW, lay,
+                                                                  (hipStream_t)stream));
 }
 int cot_radix_mix_backward_reduce_bn(const void* gout, const void* a, const void* k, const void* attn, void* glogitsT, float* tsum,
                                      const float* gamma, const float* beta, const float* save_mean, const float* save_rstd, int N, int C,
@@ -1342,10 +1013,8 @@ int cot_radix_mix_backward_reduce_bn(const void* gout, const void* a, const void
     if (!gout || !a || !k || !attn || !glogitsT || !tsum || !gamma || !beta || !save_mean || !save_rstd)
         return set_error(COT_ERR_INVALID_ARG, "NULL device pointer");
     if ((rc = check_align16({gout, a, k}))) return rc;
-    return dtype == COT_F32 ? radix_mix_bwd_reduce_bn<float>(gout, a, k, attn, glogitsT, tsum, gamma, beta, save_mean, save_rstd, N, C,
-                                                             HW, lay, (hipStream_t)stream)
-                            : radix_mix_bwd_reduce_bn<bf16_t>(gout, a, k, attn, glogitsT, tsum, gamma, beta, save_mean, save_rstd, N, C,
-                                                              HW, lay, (hipStream_t)stream);
+    DISPATCH_F32_BF16(dtype, "radix tail", radix_mix_bwd_reduce_bn<T>(gout, a, k, attn, glogitsT, tsum, gamma, beta, save_mean, save_rstd, N, C, HW,
+                                                                      lay, (hipStream_t)stream));
 }
 int cot_radix_mix_backward_apply_bn(const void* gout, const void* a, const void* attn, const void* ggapT, const float* tsum, void* ga,
                                     void* gk, const float* gamma, const float* beta, const float* save_mean, const float* save_rstd,
@@ -1355,10 +1024,8 @@ int cot_radix_mix_backward_apply_bn(const void* gout, const void* a, const void*
     if (!gout || !a || !attn || !ggapT || !tsum || !ga || !gk || !gamma || !beta || !save_mean || !save_rstd || !dgamma || !dbeta)
         return set_error(COT_ERR_INVALID_ARG, "NULL device pointer");
     if ((rc = check_align16({gout, a, ga, gk}))) return rc;
-    return dtype == COT_F32 ? radix_mix_bwd_apply_bn<float>(gout, a, attn, ggapT, tsum, ga, gk, gamma, beta, save_mean, save_rstd, dgamma,
-                                                            dbeta, N, C, HW, lay, (hipStream_t)stream)
-                            : radix_mix_bwd_apply_bn<bf16_t>(gout, a, attn, ggapT, tsum, ga, gk, gamma, beta, save_mean, save_rstd,
-                                                             dgamma, dbeta, N, C, HW, lay, (hipStream_t)stream);
+    DISPATCH_F32_BF16(dtype, "radix tail", radix_mix_bwd_apply_bn<T>(gout, a, attn, ggapT, tsum, ga, gk, gamma, beta, save_mean, save_rstd, dgamma,
+                                                                     dbeta, N, C, HW, lay, (hipStream_t)stream));
 }
 
 int64_t cot_stem7x7s2_workspace(int N, int H, int W) {
@@ -1435,9 +1102,7 @@ static int pool_call(int op, const void* a, const void* b, void* out, int64_t pl
     if (planes <= 0 || H <= 0 || W <= 0) return set_error(COT_ERR_INVALID_ARG, "non-positive planes/H/W");
     if (!a || !out || (op >= 3 && op <= 5 && !b)) return set_error(COT_ERR_INVALID_ARG, "NULL device pointer");
     if (op >= 6 && (H < 2 || W < 2)) return set_error(COT_ERR_UNSUPPORTED, "blur pooling reflects by one pixel: H, W >= 2");
-    if (dtype == COT_F32) return pool3x3s2<float>(op, a, b, out, planes, H, W, (hipStream_t)stream);
-    if (dtype == COT_BF16) return pool3x3s2<bf16_t>(op, a, b, out, planes, H, W, (hipStream_t)stream);
-    return set_error(COT_ERR_UNSUPPORTED, "cot_*pool3x3s2_*: dtype %d (float32 / bfloat16 only)", dtype);
+    DISPATCH_F32_BF16(dtype, "cot_*pool3x3s2_*", pool3x3s2<T>(op, a, b, out, planes, H, W, (hipStream_t)stream));
 }
 static int subsample_call(int bwd, const void* a, void* out, int64_t planes, int H, int W, int dtype, void* stream) {
     if (planes <= 0 || H <= 0 || W <= 0) return set_error(COT_ERR_INVALID_ARG, "non-positive planes/H/W");
@@ -1723,35 +1388,29 @@ int cot_soft_target_ce_backward(const void* logits, const void* labels, const vo
 
 int cot_bn_act_workspace(int N, int C) { return (N > 0 && C > 0) ? bn_workspace_floats(N, C) : 0; }
 
-static int cot_bn_act_forward_ps_impl(const void* x, const void* residual, void* y, const float* gamma, const float* beta,
-                          float* save_mean, float* save_rstd, float* running_mean, float* running_var,
-                          int64_t* num_batches_tracked, float* workspace, const float* sample_scale, int N, int C, int HW,
-                          float eps, float momentum, int act, int dtype, void* stream) {
+// the bodies of the BatchNorm entry points without / with a ReLU sign mask (`mask`, NULL = none; -3 = the kernel serving the geometry
+// takes none)
+static int bn_act_forward_body(const void* x, const void* residual, void* y, uint8_t* mask, const float* gamma, const float* beta,
+                               float* save_mean, float* save_rstd, float* running_mean, float* running_var,
+                               int64_t* num_batches_tracked, float* workspace, const float* sample_scale, int N, int C, int HW,
+                               float eps, float momentum, int act, int dtype, void* stream) {
+    prof::Scope scope(20, N, C, C, HW, 1, dtype, (residual ? 1 : 0));
     if (!x || !y || !gamma || !beta || !save_mean || !save_rstd || !workspace)
         return set_error(COT_ERR_INVALID_ARG, "NULL device pointer");
     if (N <= 0 || C <= 0 || HW <= 0 || act < 0 || act > 2) return set_error(COT_ERR_INVALID_ARG, "bad N/C/HW/act");
-    if ((running_mean == NULL) != (running_var == NULL))
-        return set_error(COT_ERR_INVALID_ARG, "running_mean and running_var must be given together");
+    if (check_running_pair(running_mean, running_var)) return COT_ERR_INVALID_ARG;
     int rc = check_align16({x, residual, y});
     if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == COT_F32)
-        return bn_act_forward<float>(x, residual, y, gamma, beta, save_mean, save_rstd, running_mean, running_var,
-                                     (long long*)num_batches_tracked, workspace, N, C, HW, eps, momentum, act, sample_scale, s);
-    if (dtype == COT_BF16)
-        return bn_act_forward<bf16_t>(x, residual, y, gamma, beta, save_mean, save_rstd, running_mean, running_var,
-                                      (long long*)num_batches_tracked, workspace, N, C, HW, eps, momentum, act, sample_scale, s);
-    return set_error(COT_ERR_UNSUPPORTED, "bn_act: dtype %d (float32 / bfloat16 only)", dtype);
+    DISPATCH_F32_BF16(dtype, "bn_act", bn_act_forward<T>(x, residual, y, gamma, beta, save_mean, save_rstd, running_mean, running_var,
+                                                         (long long*)num_batches_tracked, workspace, N, C, HW, eps, momentum, act,
+                                                         sample_scale, mask, (hipStream_t)stream));
 }
 int cot_bn_act_forward_ps(const void* x, const void* residual, void* y, const float* gamma, const float* beta,
                           float* save_mean, float* save_rstd, float* running_mean, float* running_var,
                           int64_t* num_batches_tracked, float* workspace, const float* sample_scale, int N, int C, int HW,
                           float eps, float momentum, int act, int dtype, void* stream) {
-    const bool p = prof::enabled();
-    if (p) prof::mark();
-    const int rc = cot_bn_act_forward_ps_impl(x, residual, y, gamma, beta, save_mean, save_rstd, running_mean, running_var, num_batches_tracked, workspace, sample_scale, N, C, HW, eps, momentum, act, dtype, stream);
-    if (p) prof::annotate_op(20, N, C, C, HW, 1, dtype, (residual ? 1 : 0));
-    return rc;
+    return bn_act_forward_body(x, residual, y, nullptr, gamma, beta, save_mean, save_rstd, running_mean, running_var, num_batches_tracked,
+                               workspace, sample_scale, N, C, HW, eps, momentum, act, dtype, stream);
 }
 int cot_bn_act_forward(const void* x, const void* residual, void* y, const float* gamma, const float* beta,
                        float* save_mean, float* save_rstd, float* running_mean, float* running_var,
@@ -1760,9 +1419,13 @@ int cot_bn_act_forward(const void* x, const void* residual, void* y, const float
     return cot_bn_act_forward_ps(x, residual, y, gamma, beta, save_mean, save_rstd, running_mean, running_var,
                                  num_batches_tracked, workspace, NULL, N, C, HW, eps, momentum, act, dtype, stream);
 }
-static int cot_bn_act_backward_ps_impl(const void* dy, const void* x, const void* y, void* dx, void* dresidual, const float* gamma,
-                           const float* beta, const float* save_mean, const float* save_rstd, float* dgamma, float* dbeta,
-                           float* workspace, const float* sample_scale, int N, int C, int HW, int act, int dtype, void* stream) {
+// `y` selects the sign-from-output kernels (ACT_RELU_Y) and is what they read.  With a mask the caller passes the MASK in y's place:
+// the same kernels are selected, read the mask and never dereference y.  prof_flags: bit 0 residual, bit 1 saved output read.
+static int bn_act_backward_body(const void* dy, const void* x, const void* y, const uint8_t* mask, void* dx, void* dresidual,
+                                const float* gamma, const float* beta, const float* save_mean, const float* save_rstd, float* dgamma,
+                                float* dbeta, float* workspace, const float* sample_scale, int N, int C, int HW, int act, int dtype,
+                                int prof_flags, void* stream) {
+    prof::Scope scope(21, N, C, C, HW, 1, dtype, prof_flags);
     if (!dy || !x || !dx || !gamma || !beta || !save_mean || !save_rstd || !dgamma || !dbeta || !workspace)
         return set_error(COT_ERR_INVALID_ARG, "NULL device pointer");
     if (act == 1 && !y && dresidual)
@@ -1772,23 +1435,14 @@ static int cot_bn_act_backward_ps_impl(const void* dy, const void* x, const void
     if (N <= 0 || C <= 0 || HW <= 0 || act < 0 || act > 2) return set_error(COT_ERR_INVALID_ARG, "bad N/C/HW/act");
     int rc = check_align16({dy, x, y, dx, dresidual});
     if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == COT_F32)
-        return bn_act_backward<float>(dy, x, y, dx, dresidual, gamma, beta, save_mean, save_rstd, dgamma, dbeta,
-                                      workspace, N, C, HW, act, sample_scale, s);
-    if (dtype == COT_BF16)
-        return bn_act_backward<bf16_t>(dy, x, y, dx, dresidual, gamma, beta, save_mean, save_rstd, dgamma, dbeta,
-                                       workspace, N, C, HW, act, sample_scale, s);
-    return set_error(COT_ERR_UNSUPPORTED, "bn_act: dtype %d (float32 / bfloat16 only)", dtype);
+    DISPATCH_F32_BF16(dtype, "bn_act", bn_act_backward<T>(dy, x, y, dx, dresidual, gamma, beta, save_mean, save_rstd, dgamma, dbeta, workspace,
+                                                          N, C, HW, act, sample_scale, mask, (hipStream_t)stream));
 }
 int cot_bn_act_backward_ps(const void* dy, const void* x, const void* y, void* dx, void* dresidual, const float* gamma,
                            const float* beta, const float* save_mean, const float* save_rstd, float* dgamma, float* dbeta,
                            float* workspace, const float* sample_scale, int N, int C, int HW, int act, int dtype, void* stream) {
-    const bool p = prof::enabled();
-    if (p) prof::mark();
-    const int rc = cot_bn_act_backward_ps_impl(dy, x, y, dx, dresidual, gamma, beta, save_mean, save_rstd, dgamma, dbeta, workspace, sample_scale, N, C, HW, act, dtype, stream);
-    if (p) prof::annotate_op(21, N, C, C, HW, 1, dtype, (dresidual ? 1 : 0) | (y ? 2 : 0));
-    return rc;
+    return bn_act_backward_body(dy, x, y, nullptr, dx, dresidual, gamma, beta, save_mean, save_rstd, dgamma, dbeta, workspace, sample_scale,
+                                N, C, HW, act, dtype, (dresidual ? 1 : 0) | (y ? 2 : 0), stream);
 }
 int cot_bn_act_backward(const void* dy, const void* x, const void* y, void* dx, void* dresidual, const float* gamma,
                         const float* beta, const float* save_mean, const float* save_rstd, float* dgamma, float* dbeta,
@@ -1808,17 +1462,14 @@ int cot_bn_act_forward_lay(const void* x, const void* residual, void* y, void* y
                            void* stream) {
     if (!x || !y || !gamma || !beta || !save_mean || !save_rstd) return set_error(COT_ERR_INVALID_ARG, "NULL device pointer");
     if (N <= 0 || C <= 0 || HW <= 0 || act < 0 || act > 2 || (lay & ~15)) return set_error(COT_ERR_INVALID_ARG, "bad N/C/HW/act/lay");
-    if ((running_mean == NULL) != (running_var == NULL))
-        return set_error(COT_ERR_INVALID_ARG, "running_mean and running_var must be given together");
+    if (check_running_pair(running_mean, running_var)) return COT_ERR_INVALID_ARG;
     if (dtype != COT_BF16) return set_error(COT_ERR_UNSUPPORTED, "cot_bn_act_*_lay: COT_BF16 only (dtype %d given)", dtype);
     int rc = check_align16({x, residual, y, y2});
     if (rc) return rc;
-    const bool p = prof::enabled();
-    if (p) prof::mark();
+    prof::Scope scope(20, N, C, C, HW, 1, dtype, (residual ? 1 : 0) | (y2 ? 4 : 0));
     rc = bn_act_forward_lay(x, residual, y, y2, gamma, beta, save_mean, save_rstd, running_mean, running_var, (long long*)num_batches_tracked,
                             N, C, HW, eps, momentum, act, sample_scale, lay, (hipStream_t)stream);
     if (rc == -2) return set_error(COT_ERR_UNSUPPORTED, "cot_bn_act_forward_lay: N=%d C=%d HW=%d is off the channel-resident kernels (cot_bn_act_lay_covers)", N, C, HW);
-    if (p) prof::annotate_op(20, N, C, C, HW, 1, dtype, (residual ? 1 : 0) | (y2 ? 4 : 0));
     return rc;
 }
 int cot_bn_act_backward_lay(const void* dy, const void* dy2, const void* x, const void* y, void* dx, void* dresidual, const float* gamma,
@@ -1833,12 +1484,10 @@ int cot_bn_act_backward_lay(const void* dy, const void* dy2, const void* x, cons
     if (dtype != COT_BF16) return set_error(COT_ERR_UNSUPPORTED, "cot_bn_act_*_lay: COT_BF16 only (dtype %d given)", dtype);
     int rc = check_align16({dy, dy2, x, y, dx, dresidual});
     if (rc) return rc;
-    const bool p = prof::enabled();
-    if (p) prof::mark();
+    prof::Scope scope(21, N, C, C, HW, 1, dtype, (dresidual ? 1 : 0) | (y ? 2 : 0) | (dy2 ? 4 : 0));
     rc = bn_act_backward_lay(dy, dy2, x, y, dx, dresidual, gamma, beta, save_mean, save_rstd, dgamma, dbeta, N, C, HW, act, sample_scale, lay,
                              (hipStream_t)stream);
     if (rc == -2) return set_error(COT_ERR_UNSUPPORTED, "cot_bn_act_backward_lay: N=%d C=%d HW=%d is off the channel-resident kernels (cot_bn_act_lay_covers)", N, C, HW);
-    if (p) prof::annotate_op(21, N, C, C, HW, 1, dtype, (dresidual ? 1 : 0) | (y ? 2 : 0) | (dy2 ? 4 : 0));
     return rc;
 }
 
@@ -1848,10 +1497,6 @@ int64_t cot_bn_relu_mask_bytes(int N, int C, int HW, int dtype) {
     if (N <= 0 || C <= 0 || HW <= 0) return 0;
     return bn_relu_mask_bytes(N, C, HW, dtype == COT_BF16 ? 2 : (dtype == COT_F32 ? 4 : 0));
 }
-struct BnMaskScope {  // (the kernels' launch code reads the mask of the call in flight from a thread-local)
-    explicit BnMaskScope(uint8_t* m) { t_bn_mask = m; }
-    ~BnMaskScope() { t_bn_mask = nullptr; }
-};
 int cot_bn_act_forward_mask(const void* x, const void* residual, void* y, void* relu_mask, const float* gamma, const float* beta,
                             float* save_mean, float* save_rstd, float* running_mean, float* running_var,
                             int64_t* num_batches_tracked, float* workspace, const float* sample_scale, int N, int C, int HW,
@@ -1859,9 +1504,8 @@ int cot_bn_act_forward_mask(const void* x, const void* residual, void* y, void* 
     if (!relu_mask) return set_error(COT_ERR_INVALID_ARG, "relu_mask is NULL (cot_bn_act_forward_ps is the call without one)");
     if (act != 1 || cot_bn_relu_mask_bytes(N, C, HW, dtype) == 0)
         return set_error(COT_ERR_UNSUPPORTED, "cot_bn_act_forward_mask: ReLU, and a geometry cot_bn_relu_mask_bytes accepts");
-    BnMaskScope scope((uint8_t*)relu_mask);
-    const int rc = cot_bn_act_forward_ps(x, residual, y, gamma, beta, save_mean, save_rstd, running_mean, running_var, num_batches_tracked,
-                                         workspace, sample_scale, N, C, HW, eps, momentum, act, dtype, stream);
+    const int rc = bn_act_forward_body(x, residual, y, (uint8_t*)relu_mask, gamma, beta, save_mean, save_rstd, running_mean, running_var,
+                                       num_batches_tracked, workspace, sample_scale, N, C, HW, eps, momentum, act, dtype, stream);
     if (rc == -3) return set_error(COT_ERR_UNSUPPORTED, "cot_bn_act_forward_mask: the kernel serving N=%d C=%d HW=%d cannot write a sign mask", N, C, HW);
     return rc;
 }
@@ -1871,13 +1515,9 @@ int cot_bn_act_backward_mask(const void* dy, const void* x, const void* relu_mas
     if (!relu_mask) return set_error(COT_ERR_INVALID_ARG, "relu_mask is NULL");
     if (act != 1 || cot_bn_relu_mask_bytes(N, C, HW, dtype) == 0)
         return set_error(COT_ERR_UNSUPPORTED, "cot_bn_act_backward_mask: ReLU, and a geometry cot_bn_relu_mask_bytes accepts");
-    BnMaskScope scope((uint8_t*)const_cast<void*>(relu_mask));
-    // (`y` of the ordinary entry point only selects the sign-from-output kernels; with a mask they never dereference it)
-    const bool p = prof::enabled();
-    if (p) prof::mark();
-    const int rc = cot_bn_act_backward_ps_impl(dy, x, /*y=*/relu_mask, dx, dresidual, gamma, beta, save_mean, save_rstd, dgamma, dbeta,
-                                               workspace, sample_scale, N, C, HW, act, dtype, stream);
-    if (p) prof::annotate_op(21, N, C, C, HW, 1, dtype, (dresidual ? 1 : 0));  // (no saved-output read: the mask is 1/16 of it)
+    // (the mask in y's place, see bn_act_backward_body; no saved-output read in the flags: the mask is 1/16 of it)
+    const int rc = bn_act_backward_body(dy, x, /*y=*/relu_mask, (const uint8_t*)relu_mask, dx, dresidual, gamma, beta, save_mean, save_rstd,
+                                        dgamma, dbeta, workspace, sample_scale, N, C, HW, act, dtype, (dresidual ? 1 : 0), stream);
     if (rc == -3) return set_error(COT_ERR_UNSUPPORTED, "cot_bn_act_backward_mask: the kernel serving N=%d C=%d HW=%d cannot read a sign mask", N, C, HW);
     return rc;
 }
@@ -1891,12 +1531,8 @@ int cot_bn_act_apply_forward(const void* x, const void* residual, void* y, void*
         return set_error(COT_ERR_UNSUPPORTED, "cot_bn_act_apply_forward: a sign mask needs ReLU and a geometry cot_bn_relu_mask_bytes accepts");
     int rc = check_align16({x, residual, y});
     if (rc) return rc;
-    BnMaskScope scope((uint8_t*)relu_mask);
-    const bool p = prof::enabled();
-    if (p) prof::mark();
-    rc = bn_apply_forward(x, residual, y, gamma, beta, mean, rstd, N, C, HW, act, (hipStream_t)stream);
-    if (p) prof::annotate_op(20, N, C, C, HW, 1, dtype, (residual ? 1 : 0) | 8);
-    return rc;
+    prof::Scope scope(20, N, C, C, HW, 1, dtype, (residual ? 1 : 0) | 8);
+    return bn_apply_forward(x, residual, y, gamma, beta, mean, rstd, N, C, HW, act, (uint8_t*)relu_mask, (hipStream_t)stream);
 }
 
 int cot_bn_act_inference(const void* x, const void* residual, void* y, const float* gamma, const float* beta,
@@ -1906,10 +1542,7 @@ int cot_bn_act_inference(const void* x, const void* residual, void* y, const flo
     if (N <= 0 || C <= 0 || HW <= 0 || act < 0 || act > 2) return set_error(COT_ERR_INVALID_ARG, "bad N/C/HW/act");
     int rc = check_align16({x, residual, y});
     if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == COT_F32) return bn_act_inference<float>(x, residual, y, gamma, beta, running_mean, running_var, N, C, HW, eps, act, s);
-    if (dtype == COT_BF16) return bn_act_inference<bf16_t>(x, residual, y, gamma, beta, running_mean, running_var, N, C, HW, eps, act, s);
-    return set_error(COT_ERR_UNSUPPORTED, "bn_act: dtype %d (float32 / bfloat16 only)", dtype);
+    DISPATCH_F32_BF16(dtype, "bn_act", bn_act_inference<T>(x, residual, y, gamma, beta, running_mean, running_var, N, C, HW, eps, act, (hipStream_t)stream));
 }
 
 int cot_profile_begin(void) {
@@ -1950,8 +1583,7 @@ int cot_agg_forward(const void* x, const void* w, void* out, const cot_agg_geom*
     if (!x || !w || !out) return set_error(COT_ERR_INVALID_ARG, "NULL device pointer");
     if (layout != COT_NCHW && layout != COT_NHWC) return set_error(COT_ERR_UNSUPPORTED, "unknown layout %d", layout);
     if ((rc = check_align16({x, w, out}))) return rc;
-    const bool p = prof::enabled();
-    if (p) prof::mark();
+    prof::Scope scope(*g, dtype, layout, 0, 0);
     switch (dtype) {
         case COT_F32: rc = fwd_t<float>(x, w, out, *g, Ho, Wo, layout, (hipStream_t)stream); break;
         case COT_F64: rc = fwd_t<double>(x, w, out, *g, Ho, Wo, layout, (hipStream_t)stream); break;
@@ -1959,7 +1591,6 @@ int cot_agg_forward(const void* x, const void* w, void* out, const cot_agg_geom*
         case COT_F16: rc = fwd_t<f16_t>(x, w, out, *g, Ho, Wo, layout, (hipStream_t)stream); break;
         default: return set_error(COT_ERR_UNSUPPORTED, "unknown dtype %d", dtype);
     }
-    if (p) prof::annotate(*g, dtype, layout, 0, 0);
     return rc;
 }
 
@@ -1973,8 +1604,7 @@ int cot_agg_backward(const void* gout, const void* x, const void* w, void* gx, v
     if (gw && !x) return set_error(COT_ERR_INVALID_ARG, "gw requested but x is NULL");
     if (layout != COT_NCHW && layout != COT_NHWC) return set_error(COT_ERR_UNSUPPORTED, "unknown layout %d", layout);
     if ((rc = check_align16({gout, x, w, gx, gw}))) return rc;
-    const bool p = prof::enabled();
-    if (p) prof::mark();
+    prof::Scope scope(*g, dtype, layout, 1, (gx ? 1 : 0) | (gw ? 2 : 0));
     switch (dtype) {
         case COT_F32: rc = bwd_t<float>(gout, x, w, gx, gw, *g, Ho, Wo, layout, (hipStream_t)stream); break;
         case COT_F64: rc = bwd_t<double>(gout, x, w, gx, gw, *g, Ho, Wo, layout, (hipStream_t)stream); break;
@@ -1982,7 +1612,6 @@ int cot_agg_backward(const void* gout, const void* x, const void* w, void* gx, v
         case COT_F16: rc = bwd_t<f16_t>(gout, x, w, gx, gw, *g, Ho, Wo, layout, (hipStream_t)stream); break;
         default: return set_error(COT_ERR_UNSUPPORTED, "unknown dtype %d", dtype);
     }
-    if (p) prof::annotate(*g, dtype, layout, 1, (gx ? 1 : 0) | (gw ? 2 : 0));
     return rc;
 }
 

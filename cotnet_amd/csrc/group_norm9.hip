@@ -13,6 +13,7 @@
 // 8*(r*NT + t): all channel indices are compile-time, so per-channel accumulators stay in registers.
 #include "cot_common.h"
 #include "mfma_common.h"
+#include "cot_host.h"
 
 namespace cot {
 

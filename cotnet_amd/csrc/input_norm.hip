@@ -5,6 +5,7 @@
 //   writes them with 16-byte stores.
 // The per-pixel arithmetic (norm_one<T>) is in input_norm.h: cot_mix_normalize (mix_loss.hip) shares it.
 #include "input_norm.h"
+#include "cot_host.h"
 
 namespace cot {
 

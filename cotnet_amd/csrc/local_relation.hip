@@ -19,11 +19,9 @@
 //   lr_softmax_bwd  gv and gL for the geometries the LDS-staged softmax aggregation backward (agg_nchw.hip) does not take
 //                   (its 16-byte plane-stride rule); direct loads, one thread per (n, g, pixel).
 #include "cot_common.h"
+#include "cot_host.h"
 
 namespace cot {
-
-template <typename T>
-int agg_softmax_backward_nchw(const T*, const T*, const T*, T*, T*, const cot_agg_geom&, hipStream_t);
 
 static const char* g_lr_kernel = "";
 const char* last_kernel_lr() { return g_lr_kernel; }

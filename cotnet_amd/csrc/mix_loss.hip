@@ -19,6 +19,7 @@
 #include <math.h>
 
 #include "input_norm.h"
+#include "cot_host.h"
 
 namespace cot {
 

@@ -11,6 +11,7 @@
 #include <type_traits>
 
 #include "cot_common.h"
+#include "cot_host.h"
 
 namespace cot {
 

@@ -8,6 +8,7 @@
 // (the tiny se MLP + softmax between gap and mix stay in torch).  One wavefront per (b,c) plane: the per-plane scalars
 // are wave-uniform, plane rows are contiguous, loads are V-wide vectors when H*W allows.
 #include "cot_common.h"
+#include "cot_host.h"
 
 namespace cot {
 

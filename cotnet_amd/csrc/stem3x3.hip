@@ -13,11 +13,9 @@
 //             fragments are 8 stride-2 taps of one (ci, kh, kw) each; deterministic slices + the shared reduce kernel.
 #include "cot_common.h"
 #include "mfma_common.h"
+#include "cot_host.h"
 
 namespace cot {
-
-int conv1x1_wgrad_reduce_launch(const float* part, int S, int M, int J, int has_bias, void* gw, void* gb,
-                                hipStream_t stream);  // conv1x1.hip
 
 constexpr int kS3K = 27, kS3Kp = 32;
 

@@ -15,11 +15,9 @@
 //             contiguous), B fragments are 8 strided taps of one (ci, kh, kw) each; deterministic slices + reduce kernel.
 #include "cot_common.h"
 #include "mfma_common.h"
+#include "cot_host.h"
 
 namespace cot {
-
-int conv1x1_wgrad_reduce_launch(const float* part, int S, int M, int J, int has_bias, void* gw, void* gb,
-                                hipStream_t stream);  // conv1x1.hip
 
 constexpr int kStemK = 147, kStemKp = 160, kStemCo = 64;
 

@@ -10,6 +10,7 @@
 //             keeps its 37 partial sums in registers across the tiles it sees (dY tile [px][co] and the patch in LDS: the tap reads are
 //             wave-wide broadcasts), writes them to workspace[s][co][k] once; a second kernel adds the S slices in order.
 #include "cot_common.h"
+#include "cot_host.h"
 
 namespace cot {
 

@@ -107,6 +107,35 @@ def test_checked_view_follows_lib(monkeypatch):
     assert _lib.api()._raw is real._raw
 
 
+_TUNING_KEYS_CHILD = r"""
+import ctypes, sys
+from cotnet_amd import _lib
+L = ctypes.CDLL(_lib.LIB_PATH)
+L.cot_last_error.restype = ctypes.c_char_p
+assert L.cot_set_tuning(26, 1) == 0  # dry run: no launch, no HIP call
+bad = []
+for key in list(range(0, 35)) + list(range(36, 55)):
+    for value in (0, 1):
+        if L.cot_set_tuning(key, value) != 0:
+            bad.append((key, value, L.cot_last_error()))
+for key in (-1, 35, 55):
+    rc = L.cot_set_tuning(key, 1)
+    if rc != -1 or b"unknown tuning key" not in L.cot_last_error():
+        bad.append((key, rc, L.cot_last_error()))
+print("BAD", bad)
+sys.exit(1 if bad else 0)
+"""
+
+
+def test_tuning_keys():
+    """cot_set_tuning takes every key in {0-34, 36-54} with the values 0 and 1 and refuses -1, 35 and 55 as unknown -- in a child
+    process, so that the knobs it turns reach no other test"""
+    import subprocess
+    import sys
+    r = subprocess.run([sys.executable, "-c", _TUNING_KEYS_CHILD], cwd=ROOT, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+
+
 def test_product_has_no_cpu_fallback():
     """CPU tensors take the reference's route (copy to the GPU); without a GPU that must raise, not compute."""
     import torch
