@@ -30,6 +30,20 @@ def register_cache(d):
     return d
 
 
+def memo(cache):
+    """decorator: fn(L, *key) answered out of `cache` (a register_cache dictionary) from the second call with a key on; the
+    library handle L is passed on and is not part of the key"""
+    def deco(fn):
+        @functools.wraps(fn)
+        def wrapped(L, *key):
+            v = cache.get(key)
+            if v is None:
+                v = cache[key] = fn(L, *key)
+            return v
+        return wrapped
+    return deco
+
+
 class AggGeom(ctypes.Structure):
     """mirror of `cot_agg_geom`"""
     _fields_ = [(n, ctypes.c_int32) for n in (

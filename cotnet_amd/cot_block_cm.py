@@ -11,7 +11,8 @@ from ._lib import one_stream_query as _one_stream_query, ptr as _p, stream as _s
 from . import cot_layer_fused as clf
 from .cot_layer_fused import (  # noqa: E402  (helpers; the switches are read as clf.NAME at call time: tests rebind them there)
     BF16, NODE_COUNTS, _Side, _block_plan, _bn_bwd, _bn_bwd_lay, _bn_fwd, _bn_fwd_lay, _conv1_bwd, _conv1x1_bwd, _conv1x1_dgrad,
-    _conv1x1_wgrad, _cot_backward, _cot_forward, _drop_path_scale, _masks, _new_guarded, _pack, _plan, _relu_mask, _unpack)
+    _conv1x1_wgrad, _cot_backward, _cot_forward, _drop_path_scale, _input_ok, _masks, _modes_ok, _new_guarded, _pack, _plan, _relu_mask,
+    _unpack)
 
 # ---- channel-major Bottlenecks for the 14 x 14 / 7 x 7 stages (round 5).  The layers of these stages spend their time in
 # 1x1 convolutions and BatchNorms whose NCHW operands are N short rows per channel (392 / 98 bytes); stored channel-major --
@@ -74,59 +75,49 @@ def _cm_static_ok(blk):
     return bp.static_ok and (identity or opening)
 
 
+@_lib.memo(_CM_SIZES)
 def _cm_sizes(L, N, Cin, C, A, G, H, W, grouped=False, Cout=None):
     """Cin / Cout: the block's input / output channels (Cout given = the stage's opening block: conv1 on 2H x 2W NCHW planes, the
     projection on the sub-sampled input)"""
-    k = (N, Cin, C, A, G, H, W, grouped, Cout)
-    v = _CM_SIZES.get(k)
-    if v is None:
-        HW, M = H * W, N * H * W
-        gws = max(int(L.cot_convg_workspace(1, 2 * C, C // 2, 2, M, 1, 1)), int(L.cot_convg_workspace(1, C // 2, 9 * C // 8, 2, M, 1, 1)),
-                  int(L.cot_convg_workspace(1, C, C, 2, M, 1, 1))) if grouped else 0
-        ws = max(gws, int(L.cot_conv3x3g_workspace(N, C, C, G, H, W)), int(L.cot_conv1x1_workspace(1, 2 * C, C // 2, M, 0)),
-                 int(L.cot_conv1x1_workspace(1, C // 2, 9 * C // 8, M, 1)), int(L.cot_conv1x1_workspace(1, C, C, M, 0)),
-                 int(L.cot_conv1x1_workspace(1, C, A, N, 1)), int(L.cot_conv1x1_workspace(1, A, 2 * C, N, 1)),
-                 int(L.cot_conv1x1_workspace(1, Cin, C, M, 0)), int(L.cot_conv1x1_workspace(1, C, Cout or Cin, M, 0)),
-                 int(L.cot_conv1x1_workspace(N, Cin, C, HW, 0)),
-                 *((int(L.cot_conv1x1_workspace(N, Cin, C, 4 * HW, 0)), int(L.cot_conv1x1_workspace(N, Cin, Cout, HW, 0))) if Cout else ()))
-        v = _CM_SIZES[k] = (ws, int(L.cot_bn_act_workspace(N, C)), int(L.cot_bn_act_workspace(1, C)), int(L.cot_bn_act_workspace(1, C // 2)),
-                            int(L.cot_bn_act_workspace(1, A)), int(L.cot_bn_act_workspace(1, Cout or Cin)))
-    return v
+    HW, M = H * W, N * H * W
+    gws = max(int(L.cot_convg_workspace(1, 2 * C, C // 2, 2, M, 1, 1)), int(L.cot_convg_workspace(1, C // 2, 9 * C // 8, 2, M, 1, 1)),
+              int(L.cot_convg_workspace(1, C, C, 2, M, 1, 1))) if grouped else 0
+    ws = max(gws, int(L.cot_conv3x3g_workspace(N, C, C, G, H, W)), int(L.cot_conv1x1_workspace(1, 2 * C, C // 2, M, 0)),
+             int(L.cot_conv1x1_workspace(1, C // 2, 9 * C // 8, M, 1)), int(L.cot_conv1x1_workspace(1, C, C, M, 0)),
+             int(L.cot_conv1x1_workspace(1, C, A, N, 1)), int(L.cot_conv1x1_workspace(1, A, 2 * C, N, 1)),
+             int(L.cot_conv1x1_workspace(1, Cin, C, M, 0)), int(L.cot_conv1x1_workspace(1, C, Cout or Cin, M, 0)),
+             int(L.cot_conv1x1_workspace(N, Cin, C, HW, 0)),
+             *((int(L.cot_conv1x1_workspace(N, Cin, C, 4 * HW, 0)), int(L.cot_conv1x1_workspace(N, Cin, Cout, HW, 0))) if Cout else ()))
+    return (ws, int(L.cot_bn_act_workspace(N, C)), int(L.cot_bn_act_workspace(1, C)), int(L.cot_bn_act_workspace(1, C // 2)),
+            int(L.cot_bn_act_workspace(1, A)), int(L.cot_bn_act_workspace(1, Cout or Cin)))
 
 
+@_lib.memo(_CM_OK)
 def _cm_geometry_ok(L, N, Cin, C, H, W, grouped=False):
-    k = (N, Cin, C, H, W, grouped)
-    v = _CM_OK.get(k)
-    if v is None:
-        HW = H * W
-        v = bool(HW <= 256 and (N * HW) % 8 == 0 and N > 1 and C % 64 == 0
-                 and L.cot_bn_act_lay_covers(N, C, HW, BF16) and L.cot_bn_act_lay_covers(N, Cin, HW, BF16)
-                 and L.cot_conv1x1_lds_covers(Cin, Cin, 0, N * HW) and L.cot_conv1x1_lds_covers(C, C, 0, N * HW))
-        if v and not grouped:
-            v = bool(L.cot_conv1x1_lds_covers(2 * C, C, 1, N * HW) and L.cot_conv1x1_lds_covers(C // 2, C // 2, 0, N * HW))
-        _CM_OK[k] = v  # (CoXtLayer's grouped 1x1s: cot_conv1x1g_* routes each group to the tuned or the general kernels itself)
-    return v
+    HW = H * W
+    v = bool(HW <= 256 and (N * HW) % 8 == 0 and N > 1 and C % 64 == 0
+             and L.cot_bn_act_lay_covers(N, C, HW, BF16) and L.cot_bn_act_lay_covers(N, Cin, HW, BF16)
+             and L.cot_conv1x1_lds_covers(Cin, Cin, 0, N * HW) and L.cot_conv1x1_lds_covers(C, C, 0, N * HW))
+    if v and not grouped:
+        v = bool(L.cot_conv1x1_lds_covers(2 * C, C, 1, N * HW) and L.cot_conv1x1_lds_covers(C // 2, C // 2, 0, N * HW))
+    return v  # (CoXtLayer's grouped 1x1s: cot_conv1x1g_* routes each group to the tuned or the general kernels itself)
 
 
 def cm_block_eligible(blk, x):
-    """training-mode identity-shortcut cotnet.Bottleneck of a deep stage on a bf16 tensor that is NCHW-contiguous or channel-major"""
-    if not (clf.ENABLED and clf.CM_LAYOUT and blk.training and (x.is_cuda or not _lib.DEVICE_ONLY) and x.dim() == 4
-            and x.dtype == torch.bfloat16 and x.data_ptr() % 16 == 0 and (x.is_contiguous() or _is_cm(x))):
-        return False
-    if not _cm_static_ok(blk):
+    """training-mode cotnet.Bottleneck of a deep stage (planes of at most 256 pixels, _cm_geometry_ok) on a tensor that is NCHW-contiguous
+    or channel-major: an identity-shortcut block, or (CM_OPENING) the stage's stride-2 opening block on an NCHW tensor with even planes"""
+    if not (clf.ENABLED and clf.CM_LAYOUT and blk.training and _input_ok(x, cm_allowed=True) and _cm_static_ok(blk)):
         return False
     bp = _block_plan(blk)
-    pl = _plan(bp.cot)
     N, Cin, H, W = x.shape
+    if not (_modes_ok(bp, True) and Cin == bp.conv1.in_channels):
+        return False
     if bp.avd:
-        if not (x.is_contiguous() and H % 2 == 0 and W % 2 == 0 and bp.ds_bn.training):
+        if not (x.is_contiguous() and H % 2 == 0 and W % 2 == 0):
             return False
         H, W = H // 2, W // 2
-    return (x.shape[1] == bp.conv1.in_channels and bp.conv1.weight.dtype == torch.bfloat16 and bp.conv3.weight.dtype == torch.bfloat16
-            and bp.bn1.weight.dtype == torch.float32 and bp.bn1.training and bp.bn3.training
-            and pl.ke0.weight.dtype == torch.bfloat16 and pl.em3.weight.dtype == torch.bfloat16 and pl.gn.weight.dtype == torch.bfloat16
-            and pl.bn.weight.dtype == torch.float32 and pl.bn.training and pl.ke1.training
-            and _cm_geometry_ok(_lib.lib(), N, bp.conv3.out_channels, bp.conv1.out_channels, H, W, pl.grouped))
+    # (the library is asked last: a block that fails a test above never touches it)
+    return _cm_geometry_ok(_lib.lib(), N, bp.conv3.out_channels, bp.conv1.out_channels, H, W, _plan(bp.cot).grouped)
 
 
 def cm_block_forward(blk, x):

@@ -7,7 +7,7 @@ from . import _lib
 from ._lib import one_stream_query as _one_stream_query, ptr as _p, stream as _stream
 from . import cot_layer_fused as clf
 from .cot_layer_fused import (  # noqa: E402  (helpers; the switches are read as clf.NAME at call time: tests rebind them there)
-    BF16, NODE_COUNTS, _block_plan, _gn_fused_ok, _masks, _plan, _sizes)
+    BF16, NODE_COUNTS, _block_plan, _gn_fused_ok, _input_ok, _masks, _modes_ok, _plan, _sizes)
 
 # ---- inference (BASELINE config 2: forward only, eval mode, no autograd).  The same launch sequence as _BottleneckNode.forward with
 # the BatchNorms on their running statistics (cot_bn_act_inference, in place: one pass each) and nothing kept for a backward:
@@ -21,26 +21,16 @@ def _bn_inf(L, x, bn, N, C, HW, act, residual=None, out=None):
 
 
 def eval_block_eligible(blk, x):
-    """eval-mode cotnet.Bottleneck around an (ungrouped) CotLayer on a contiguous bf16 NCHW tensor, autograd off"""
-    if not (clf.ENABLED and not blk.training and not torch.is_grad_enabled() and (x.is_cuda or not _lib.DEVICE_ONLY) and x.dim() == 4
-            and x.dtype == torch.bfloat16 and x.is_contiguous() and x.data_ptr() % 16 == 0):
+    """eval-mode block around an (ungrouped) CotLayer, autograd off, planes of at most 32768 pixels: identity or stride-1 / stride-2
+    projection shortcut, average pooling in front of the layer.  Every BatchNorm runs on its RUNNING statistics here
+    (cot_bn_act_inference), so each one has to be in eval mode itself (_modes_ok): a block in eval() with an inner BatchNorm put back
+    into train() takes the module path"""
+    if not (clf.ENABLED and not blk.training and _input_ok(x)):
         return False
     bp = _block_plan(blk)
-    if not (bp.static_ok and x.shape[1] == bp.conv1.in_channels and bp.conv1.weight.dtype == torch.bfloat16
-            and bp.conv3.weight.dtype == torch.bfloat16 and bp.bn1.weight.dtype == torch.float32
+    return (bp.static_ok and _modes_ok(bp, False) and x.shape[1] == bp.conv1.in_channels
             and not bp.avd_post and not bp.ds_pool2  # (SE-CoTNetD's stage-opening blocks: training node only)
-            and (bp.ds_conv is not None or (bp.conv1.in_channels == bp.conv3.out_channels and not bp.avd))):
-        return False
-    pl = _plan(bp.cot)
-    # every BatchNorm of the block runs on its RUNNING statistics here (cot_bn_act_inference): each one has to be in eval mode
-    # itself (a block in eval() with an inner BatchNorm put back into train() takes the module path), carry running statistics and
-    # fp32 parameters (ADVICE r5)
-    bns = [bp.bn1, bp.bn3, pl.ke1, pl.em1, pl.cv1, pl.bn, pl.sebn] + ([bp.ds_bn] if bp.ds_conv is not None else [])
-    if not all((not bn.training) and bn.running_mean is not None and bn.running_var is not None and bn.weight is not None
-               and bn.weight.dtype == torch.float32 and bn.running_mean.dtype == torch.float32 for bn in bns):
-        return False
-    return (not pl.grouped and pl.ke0.weight.dtype == torch.bfloat16 and pl.em3.weight.dtype == torch.bfloat16
-            and pl.gn.weight.dtype == torch.bfloat16 and x.shape[2] * x.shape[3] <= 8192 * 4)
+            and not _plan(bp.cot).grouped and x.shape[2] * x.shape[3] <= 8192 * 4 and not torch.is_grad_enabled())
 
 
 @_one_stream_query

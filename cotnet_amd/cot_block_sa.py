@@ -1,7 +1,6 @@
 """SE-CoTNetD's SplitAttn block as ONE autograd node (split out of cot_layer_fused.py in round 6; the switches, the side-stream machinery
 and the BatchNorm / convolution helpers live there and are imported below).  Imported by cot_layer_fused at its end: import THAT module.
 """
-import weakref
 import torch
 from torch import nn
 from torch.autograd import Function
@@ -10,7 +9,7 @@ from ._lib import one_stream_query as _one_stream_query, ptr as _p, stream as _s
 from . import cot_layer_fused as clf
 from .cot_layer_fused import (  # noqa: E402  (helpers; the switches are read as clf.NAME at call time: tests rebind them there)
     BF16, NODE_COUNTS, _Side, _bn_bwd, _bn_fwd, _bn_static_ok, _conv1_bwd, _conv1x1_bwd, _conv3x3_bwd, _conv3x3_fwd, _conv_ok,
-    _drop_path_scale, _masks, _new_guarded, _pack, _relu_mask, _shortcut_bwd, _shortcut_fwd, _unpack)
+    _drop_path_scale, _input_ok, _masks, _modes_ok, _new_guarded, _pack, _plans_of, _relu_mask, _shortcut_bwd, _shortcut_fwd, _unpack)
 
 # ---- SE-CoTNetD's OTHER block kind as one node: CoTBottleneck whose conv2 is SplitAttnConv2d(radix = 1) (models/cotnet_hybrid.py:
 # 138-146, :172-202; models/layers/split_attn.py:62-88) -- conv1 -> bn1+relu -> dense 3x3 -> bn0+act -> SE gate x * sigmoid(fc2(act(
@@ -22,14 +21,13 @@ from .cot_layer_fused import (  # noqa: E402  (helpers; the switches are read as
 # small-batch kernel.
 class _SABlockPlan:
     __slots__ = ("conv1", "bn1", "conv", "bn0", "fc1", "sbn", "fc2", "conv3", "bn3", "params", "static_ok", "act0", "act1",
-                 "ds_conv", "ds_bn", "ds_pool2", "ds_stride", "avd_post")
+                 "ds_conv", "ds_bn", "ds_pool2", "ds_stride", "avd_post", "bns", "lowp", "handles")
 
     def __init__(self, blk):
         from .layers import SplitAttnConv2d
         sa = blk.conv2
         self.conv1, self.bn1, self.conv3, self.bn3 = blk.conv1, blk.bn1, blk.conv3, blk.bn3
-        self.static_ok = False
-        self.params = []
+        self.static_ok, self.params, self.bns, self.lowp = False, [], (), ()
         if not (isinstance(sa, SplitAttnConv2d) and sa.radix == 1):
             return
         self.conv, self.bn0, self.fc1, self.sbn, self.fc2 = sa.conv, sa.bn0, sa.fc1, sa.bn1, sa.fc2
@@ -69,31 +67,23 @@ class _SABlockPlan:
         self.params = [blk.conv1.weight, blk.bn1.weight, blk.bn1.bias, sa.conv.weight, sa.bn0.weight, sa.bn0.bias, sa.fc1.weight,
                        sa.fc1.bias, sa.bn1.weight, sa.bn1.bias, sa.fc2.weight, sa.fc2.bias, blk.conv3.weight, blk.bn3.weight,
                        blk.bn3.bias] + ([self.ds_conv.weight, self.ds_bn.weight, self.ds_bn.bias] if self.ds_conv is not None else [])
+        ds = () if self.ds_conv is None else (self.ds_conv, self.ds_bn)
+        self.bns = (blk.bn1, sa.bn0, sa.bn1, blk.bn3) + ds[1:]   # (what _modes_ok looks at)
+        self.lowp = (blk.conv1, sa.conv, sa.fc1, sa.fc2, blk.conv3) + ds[:1]
 
 
-_SA_PLANS = weakref.WeakKeyDictionary()
+_sa_plan = _plans_of(_SABlockPlan)
 _SASIZES = _lib.register_cache({})
 
 
-def _sa_plan(blk):
-    p = _SA_PLANS.get(blk)
-    if p is None:
-        p = _SA_PLANS[blk] = _SABlockPlan(blk)
-    return p
-
-
-def _sa_sizes(L, N, Cin, Cw, A, G, H, W, Cout=None, HWo=None):
-    """Cout / HWo: output channels / pixels of the block (a stage-opening block changes both; default: identity shortcut)"""
-    Cout, HWo = Cout or Cin, HWo or H * W
-    k = (N, Cin, Cw, A, G, H, W, Cout, HWo)
-    v = _SASIZES.get(k)
-    if v is None:
-        HW = H * W
-        ws = max(int(L.cot_conv1x1_workspace(N, Cin, Cw, HW, 0)), int(L.cot_conv1x1_workspace(N, Cw, Cout, HWo, 0)),
-                 int(L.cot_conv1x1_workspace(N, Cin, Cout, HWo, 0)), int(L.cot_conv3x3g_workspace(N, Cw, Cw, G, H, W)),
-                 int(L.cot_conv1x1_workspace(1, Cw, A, N, 1)), int(L.cot_conv1x1_workspace(1, A, Cw, N, 1)))  # (the gate's fc layers)
-        v = _SASIZES[k] = (ws, int(L.cot_bn_act_workspace(N, Cw)), int(L.cot_bn_act_workspace(N, Cout)), int(L.cot_bn_act_workspace(1, A)))
-    return v
+@_lib.memo(_SASIZES)
+def _sa_sizes(L, N, Cin, Cw, A, G, H, W, Cout, HWo):
+    """Cout / HWo: output channels / pixels of the block (a stage-opening block changes both)"""
+    HW = H * W
+    ws = max(int(L.cot_conv1x1_workspace(N, Cin, Cw, HW, 0)), int(L.cot_conv1x1_workspace(N, Cw, Cout, HWo, 0)),
+             int(L.cot_conv1x1_workspace(N, Cin, Cout, HWo, 0)), int(L.cot_conv3x3g_workspace(N, Cw, Cw, G, H, W)),
+             int(L.cot_conv1x1_workspace(1, Cw, A, N, 1)), int(L.cot_conv1x1_workspace(1, A, Cw, N, 1)))  # (the gate's fc layers)
+    return ws, int(L.cot_bn_act_workspace(N, Cw)), int(L.cot_bn_act_workspace(N, Cout)), int(L.cot_bn_act_workspace(1, A))
 
 
 class _SplitAttnBlockNode(Function):
@@ -210,16 +200,14 @@ class _SplitAttnBlockNode(Function):
 
 
 def sa_block_eligible(blk, x):
-    """training-mode cotnet_hybrid.CoTBottleneck with a SplitAttnConv2d(radix=1) conv2, identity shortcut, on a bf16 NCHW tensor"""
-    if not (clf.ENABLED and blk.training and (x.is_cuda or not _lib.DEVICE_ONLY) and x.dim() == 4 and x.dtype == torch.bfloat16
-            and x.is_contiguous() and x.data_ptr() % 16 == 0):
+    """training-mode cotnet_hybrid.CoTBottleneck with a SplitAttnConv2d(radix=1) conv2: identity shortcut, or the stage-opening form
+    (projection shortcut, `avg_down` and BlurPool behind conv2 when it strides; even planes then).  N >= 2: the gate's BatchNorm
+    takes its statistics over the batch"""
+    if not (clf.ENABLED and blk.training and _input_ok(x)):
         return False
     sp = _sa_plan(blk)
-    return (sp.static_ok and x.shape[1] == sp.conv1.in_channels and sp.conv1.weight.dtype == torch.bfloat16
-            and sp.conv.weight.dtype == torch.bfloat16 and sp.fc1.weight.dtype == torch.bfloat16 and sp.conv3.weight.dtype == torch.bfloat16
-            and sp.bn1.weight.dtype == torch.float32 and sp.bn1.training and sp.bn0.training and sp.sbn.training and sp.bn3.training
-            and x.shape[0] >= 2 and not (sp.avd_post and (x.shape[2] % 2 or x.shape[3] % 2))
-            and (sp.ds_bn is None or sp.ds_bn.training))
+    return (sp.static_ok and _modes_ok(sp, True) and x.shape[1] == sp.conv1.in_channels and x.shape[0] >= 2
+            and not (sp.avd_post and (x.shape[2] % 2 or x.shape[3] % 2)))
 
 
 def sa_block_forward(blk, x):

@@ -168,12 +168,9 @@ GN_FUSED = os.environ.get("COT_GN_FUSED", "1") != "0"  # GroupNorm-9 statistics 
 _GN_OK = _lib.register_cache({})
 
 
+@_lib.memo(_GN_OK)
 def _gn_fused_ok(L, Ch, HW, W):
-    k = (Ch, HW, W)
-    v = _GN_OK.get(k)
-    if v is None:
-        v = _GN_OK[k] = bool(L.cot_gn9_fused_covers(Ch, Ch, 0, HW, W))
-    return v
+    return bool(L.cot_gn9_fused_covers(Ch, Ch, 0, HW, W))
 
 
 # BatchNorm + SiLU of the aggregation's output folded into the radix tail (round 6; VERDICT r5 J1 / next #2b; models/cotnet.py:89-104):
@@ -232,23 +229,19 @@ _SIZES = _lib.register_cache({})  # (N, C, H, W, A) -> (workspace bytes, bn work
 _MASKS = {}
 
 
+@_lib.memo(_SIZES)
 def _sizes(L, N, C, H, W, A, G, grouped=False):
-    k = (N, C, H, W, A, G, grouped)
-    v = _SIZES.get(k)
-    if v is None:
-        HW = H * W
-        if grouped:  # CoXtLayer: the three 1x1 convolutions of the layer are grouped (groups = 2): general kernels' workspace
-            ws = max(int(L.cot_conv3x3g_workspace(N, C, C, G, H, W)), int(L.cot_conv3x3g_workspace(N, C, C, _conv3x3_ws_groups(C, G), H, W)),
-                     int(L.cot_convg_workspace(N, 2 * C, C // 2, 2, H, W, 1)),
-                     int(L.cot_convg_workspace(N, C // 2, 9 * C // 8, 2, H, W, 1)), int(L.cot_convg_workspace(N, C, C, 2, H, W, 1)),
-                     int(L.cot_conv1x1_workspace(1, C, A, N, 1)), int(L.cot_conv1x1_workspace(1, A, 2 * C, N, 1)))
-        else:
-            ws = max(int(L.cot_conv3x3g_workspace(N, C, C, G, H, W)), int(L.cot_conv1x1_workspace(N, 2 * C, C // 2, HW, 0)),
-                     int(L.cot_conv1x1_workspace(N, C // 2, 9 * C // 8, HW, 1)), int(L.cot_conv1x1_workspace(N, C, C, HW, 0)),
-                     int(L.cot_conv1x1_workspace(1, C, A, N, 1)), int(L.cot_conv1x1_workspace(1, A, 2 * C, N, 1)))
-        v = _SIZES[k] = (ws, int(L.cot_bn_act_workspace(N, C)), int(L.cot_bn_act_workspace(N, C // 2)),
-                         int(L.cot_bn_act_workspace(1, A)))
-    return v
+    HW = H * W
+    if grouped:  # CoXtLayer: the three 1x1 convolutions of the layer are grouped (groups = 2): general kernels' workspace
+        ws = max(int(L.cot_conv3x3g_workspace(N, C, C, G, H, W)), int(L.cot_conv3x3g_workspace(N, C, C, _conv3x3_ws_groups(C, G), H, W)),
+                 int(L.cot_convg_workspace(N, 2 * C, C // 2, 2, H, W, 1)),
+                 int(L.cot_convg_workspace(N, C // 2, 9 * C // 8, 2, H, W, 1)), int(L.cot_convg_workspace(N, C, C, 2, H, W, 1)),
+                 int(L.cot_conv1x1_workspace(1, C, A, N, 1)), int(L.cot_conv1x1_workspace(1, A, 2 * C, N, 1)))
+    else:
+        ws = max(int(L.cot_conv3x3g_workspace(N, C, C, G, H, W)), int(L.cot_conv1x1_workspace(N, 2 * C, C // 2, HW, 0)),
+                 int(L.cot_conv1x1_workspace(N, C // 2, 9 * C // 8, HW, 1)), int(L.cot_conv1x1_workspace(N, C, C, HW, 0)),
+                 int(L.cot_conv1x1_workspace(1, C, A, N, 1)), int(L.cot_conv1x1_workspace(1, A, 2 * C, N, 1)))
+    return ws, int(L.cot_bn_act_workspace(N, C)), int(L.cot_bn_act_workspace(N, C // 2)), int(L.cot_bn_act_workspace(1, A))
 
 
 def _masks(L, H, W, device):
@@ -427,7 +420,7 @@ def _conv3x3_dgrad(L, conv, gy, gx, accumulate, masks, ws, N, C, G, H, W, own=No
 class _Plan:
     """per-layer handles resolved once (nn.Sequential indexing and parameter walks cost more than a kernel launch)"""
     __slots__ = ("ke0", "ke1", "em0", "em1", "em3", "gn", "cv0", "cv1", "bn", "se0", "sebn", "se3", "params",
-                 "static_ok", "grouped")
+                 "static_ok", "grouped", "bns", "lowp", "handles")
 
     def __init__(self, layer):
         ke, em, cv = layer.key_embed, layer.embed, layer.conv1x1
@@ -438,6 +431,10 @@ class _Plan:
         self.ke0, self.ke1, self.em0, self.em1, self.em3, self.gn = ke[0], ke[1], em[0], em[1], em[3], em[4]
         se = layer.se
         self.cv0, self.cv1, self.bn, self.se0, self.sebn, self.se3 = cv[0], cv[1], layer.bn, se[0], se[1], se[3]
+        # what _modes_ok asks of the modules behind `params`: the BatchNorms the launch sequence normalises with, and the modules
+        # whose weight (and bias) the kernels read as bf16
+        self.bns = (ke[1], em[1], cv[1], layer.bn, se[1])
+        self.lowp = (ke[0], em[0], em[3], em[4], cv[0], se[0], se[3])
         self.params = [ke[0].weight, ke[1].weight, ke[1].bias, em[0].weight, em[1].weight, em[1].bias, em[3].weight,
                        em[3].bias, em[4].weight, em[4].bias, cv[0].weight, cv[1].weight, cv[1].bias, layer.bn.weight,
                        layer.bn.bias, se[0].weight, se[0].bias, se[1].weight, se[1].bias, se[3].weight, se[3].bias]
@@ -456,15 +453,24 @@ class _Plan:
             and all(_bn_static_ok(b) for b in (ke[1], em[1], cv[1], layer.bn, se[1])))
 
 
-_PLANS = weakref.WeakKeyDictionary()  # module -> plan (kept out of the module's __dict__: deepcopy / pickling / state_dict
-_BLOCK_PLANS = weakref.WeakKeyDictionary()  # never see it, and a copied module gets a plan of its own)
+def _plans_of(cls):
+    """-> the accessor module -> cls(module), made on first use.  The plans are kept out of the module's __dict__: deepcopy / pickling /
+    state_dict never see them, and a copied module gets a plan of its own"""
+    table = weakref.WeakKeyDictionary()
+
+    def get(mod):
+        p = table.get(mod)
+        if p is None:
+            p = table[mod] = cls(mod)
+            # what _modes_ok reads on every call, resolved once like `params` (reading a parameter off an nn.Module costs more than testing
+            # it): the BatchNorms' parameters, their buffer tables (module.to() REPLACES a buffer: looked up per call), `lowp`'s parameters
+            p.handles = p.static_ok and (tuple(q for bn in p.bns for q in (bn.weight, bn.bias)), tuple(bn._buffers for bn in p.bns),
+                                         tuple(q for m in p.lowp for q in (m.weight, m.bias) if q is not None))
+        return p
+    return get
 
 
-def _plan(layer):
-    p = _PLANS.get(layer)
-    if p is None:
-        p = _PLANS[layer] = _Plan(layer)
-    return p
+_plan = _plans_of(_Plan)
 
 
 def _new_guarded(N, C, H, W, dtype, dev):
@@ -494,16 +500,21 @@ RES_FOLD = os.environ.get("COT_RES_FOLD", "0") == "1"
 _RES_FOLD_OK = _lib.register_cache({})
 
 
+@_lib.memo(_RES_FOLD_OK)
+def _res_fold_covers(L, N, Ci, Co, HW):
+    return bool(L.cot_conv1x1_backward_data_relu_res_covers(N, Ci, Co, HW, BF16))
+
+
 def _res_fold_ok(L, N, Ci, Co, HW):
-    if not RES_FOLD:
-        return False
-    k = (N, Ci, Co, HW)
-    v = _RES_FOLD_OK.get(k)
-    if v is None:
-        v = _RES_FOLD_OK[k] = bool(L.cot_conv1x1_backward_data_relu_res_covers(N, Ci, Co, HW, BF16))
-    return v
+    return RES_FOLD and _res_fold_covers(L, N, Ci, Co, HW)
+
 
 _MASK_BYTES = _lib.register_cache({})
+
+
+@_lib.memo(_MASK_BYTES)
+def _relu_mask_bytes(L, N, C, HW):
+    return int(L.cot_bn_relu_mask_bytes(N, C, HW, BF16))
 
 
 def _relu_mask(L, N, C, HW, dev):
@@ -511,10 +522,7 @@ def _relu_mask(L, N, C, HW, dev):
     library does not take one for this geometry (then the backward reads the saved output as before)"""
     if not RELU_MASK:
         return None
-    k = (N, C, HW)
-    nb = _MASK_BYTES.get(k)
-    if nb is None:
-        nb = _MASK_BYTES[k] = int(L.cot_bn_relu_mask_bytes(N, C, HW, BF16))
+    nb = _relu_mask_bytes(L, N, C, HW)
     return torch.empty(nb, dtype=torch.uint8, device=dev) if nb > 0 else None
 
 
@@ -543,12 +551,9 @@ BN_EPILOGUE = os.environ.get("COT_BN_EPILOGUE", "0") == "1"  # measured +0.63 ms
 _EPI_OK = _lib.register_cache({})
 
 
+@_lib.memo(_EPI_OK)
 def _epi_ok(L, Ci, c1, two, HW):
-    k = (Ci, c1, two, HW)
-    v = _EPI_OK.get(k)
-    if v is None:
-        v = _EPI_OK[k] = bool(L.cot_conv1x1_stats_covers(Ci, c1, 1 if two else 0, HW))
-    return v
+    return bool(L.cot_conv1x1_stats_covers(Ci, c1, 1 if two else 0, HW))
 
 
 def _conv_bn_fwd(L, x1, x2, c1, conv, y_pre, y, bn, stats, nws_off, N, Ci, Co, HW, act, residual=None, ps=None, mask=None, epi=True):
@@ -1046,17 +1051,37 @@ def _conv_ok(conv, k, groups=None):
             and conv.padding == (k // 2, k // 2) and conv.dilation == (1, 1) and (groups is None or conv.groups == groups))
 
 
+# ---- eligibility: what a module and its input have to be for a node to take them, stated once for every node kind.  A predicate is
+# ENABLED, the module's own mode, _input_ok, its plan's static_ok, _modes_ok, then what only that node asks (shapes; library queries last).
+def _input_ok(x, cm_allowed=False):
+    """the tensor every node takes: bf16 [N, C, H, W] on the device (anywhere once the tests lift DEVICE_ONLY), 16-byte aligned and
+    NCHW-contiguous -- or, cm_allowed, stored channel-major (_is_cm)"""
+    return ((x.is_cuda or not _lib.DEVICE_ONLY) and x.dim() == 4 and x.dtype == torch.bfloat16 and x.data_ptr() % 16 == 0
+            and (x.is_contiguous() or (cm_allowed and _is_cm(x))))
+
+
+def _modes_ok(plan, training):
+    """(plan.static_ok holds.)  Mixed precision as cotnet_amd.flat_sgd.to_mixed_bf16 sets it up -- fp32 BatchNorm parameters and running
+    statistics, everything else bf16 --, and EVERY BatchNorm of the node in the node's mode.  A training node normalises with batch
+    statistics and updates the running ones, the eval node reads the running ones: a BatchNorm in the other mode (a frozen one inside a
+    training block, say) would be treated as what it is not, so such a module takes the module path"""
+    f32, bf16 = torch.float32, torch.bfloat16
+    fp32, stats, lowp = plan.handles
+    if any(bn.training != training for bn in plan.bns) or any(p.dtype != f32 for p in fp32) or any(p.dtype != bf16 for p in lowp):
+        return False
+    for b in stats:
+        mean, var = b["running_mean"], b["running_var"]
+        if mean is None or var is None or mean.dtype != f32 or var.dtype != f32:
+            return False
+    return True
+
+
 def eligible(layer, x):
-    """training-mode CotLayer on a bf16 NCHW tensor whose every piece the kernels cover (mixed precision as
-    cotnet_amd.flat_sgd.to_mixed_bf16 sets it up: bf16 convolution / GroupNorm parameters, fp32 BatchNorm parameters)"""
-    if not (ENABLED and layer.training and (x.is_cuda or not _lib.DEVICE_ONLY) and x.dim() == 4
-            and x.dtype == torch.bfloat16 and x.is_contiguous() and x.data_ptr() % 16 == 0
-            and x.shape[1] == layer.dim):
+    """training-mode CotLayer / CoXtLayer of a width the kernels cover (_Plan.static_ok) on a tensor of its width"""
+    if not (ENABLED and layer.training and _input_ok(x)):
         return False
     pl = _plan(layer)
-    return (pl.static_ok and pl.ke0.weight.dtype == torch.bfloat16 and pl.em3.weight.dtype == torch.bfloat16
-            and pl.gn.weight.dtype == torch.bfloat16 and pl.bn.weight.dtype == torch.float32 and pl.bn.training
-            and pl.ke1.training)
+    return pl.static_ok and _modes_ok(pl, True) and x.shape[1] == layer.dim
 
 
 # how many times each node kind ran since the last reset (bench.py reports what actually executed, per step)
@@ -1082,7 +1107,7 @@ def cot_layer_forward(layer, x):
 # (`accumulate`).
 class _BlockPlan:
     __slots__ = ("conv1", "bn1", "cot", "conv3", "bn3", "ds_conv", "ds_bn", "ds_stride", "avd", "avd_post", "ds_pool2", "params",
-                 "static_ok")
+                 "static_ok", "bns", "lowp", "handles")
 
     def __init__(self, blk):
         from .cotnet import CotLayer, CoXtLayer
@@ -1114,37 +1139,38 @@ class _BlockPlan:
             ds_ok = (isinstance(c, nn.Conv2d) and c.kernel_size == (1, 1) and c.padding == (0, 0) and c.groups == 1
                      and c.stride == (self.ds_stride, self.ds_stride) and c.bias is None and _bn_static_ok(ds[-1])
                      and (pool is None or (self.ds_pool2 and avd is not None)))
+        self.static_ok, self.params, self.bns, self.lowp = False, [], (), ()
+        if not isinstance(blk.conv2, (CotLayer, CoXtLayer)):  # (SE-CoTNetD's SplitAttn blocks: cot_block_sa.py)
+            return
+        pl = _plan(blk.conv2)
         self.static_ok = (
-            ds_ok and avd_ok and isinstance(blk.conv2, (CotLayer, CoXtLayer)) and blk.drop_block is None
+            ds_ok and avd_ok and blk.drop_block is None
             and (blk.drop_path is None or hasattr(blk.drop_path, "drop_prob")) and getattr(blk, "se", None) is None
             and isinstance(blk.act1, nn.ReLU)
             and isinstance(blk.act3, nn.ReLU) and _conv_ok(blk.conv1, 1, 1) and blk.conv1.bias is None
             and _conv_ok(blk.conv3, 1, 1) and blk.conv3.bias is None and _bn_static_ok(blk.bn1)
             and _bn_static_ok(blk.bn3) and blk.conv1.in_channels % 8 == 0 and blk.conv3.out_channels % 8 == 0
-            and _plan(blk.conv2).static_ok)
-        self.params = [blk.conv1.weight, blk.bn1.weight, blk.bn1.bias] + _plan(blk.conv2).params + \
+            and (self.ds_conv is not None or blk.conv1.in_channels == blk.conv3.out_channels)  # (no projection: `ds_ok` says no pooling)
+            and pl.static_ok)
+        ds = () if self.ds_conv is None else (self.ds_conv, self.ds_bn)
+        self.params = [blk.conv1.weight, blk.bn1.weight, blk.bn1.bias] + pl.params + \
             [blk.conv3.weight, blk.bn3.weight, blk.bn3.bias] + \
-            ([self.ds_conv.weight, self.ds_bn.weight, self.ds_bn.bias] if self.ds_conv is not None else [])
+            ([self.ds_conv.weight, self.ds_bn.weight, self.ds_bn.bias] if ds else [])
+        self.bns = (blk.bn1,) + pl.bns + (blk.bn3,) + ds[1:]
+        self.lowp = (blk.conv1,) + pl.lowp + (blk.conv3,) + ds[:1]
 
 
-def _block_plan(blk):
-    p = _BLOCK_PLANS.get(blk)
-    if p is None:
-        p = _BLOCK_PLANS[blk] = _BlockPlan(blk)
-    return p
+_block_plan = _plans_of(_BlockPlan)
 
 
 _BSIZES = _lib.register_cache({})
 
 
+@_lib.memo(_BSIZES)
 def _block_sizes(L, N, Cin, Cw, Cout, HW):
-    k = (N, Cin, Cw, Cout, HW)
-    v = _BSIZES.get(k)
-    if v is None:
-        ws = max(int(L.cot_conv1x1_workspace(N, Cin, Cw, HW, 0)), int(L.cot_conv1x1_workspace(N, Cw, Cout, HW, 0)),
-                 int(L.cot_conv1x1_workspace(N, Cin, Cout, HW, 0)))
-        v = _BSIZES[k] = (ws, int(L.cot_bn_act_workspace(N, Cw)), int(L.cot_bn_act_workspace(N, Cout)))
-    return v
+    ws = max(int(L.cot_conv1x1_workspace(N, Cin, Cw, HW, 0)), int(L.cot_conv1x1_workspace(N, Cw, Cout, HW, 0)),
+             int(L.cot_conv1x1_workspace(N, Cin, Cout, HW, 0)))
+    return ws, int(L.cot_bn_act_workspace(N, Cw)), int(L.cot_bn_act_workspace(N, Cout))
 
 
 # ---- the pieces every block node shares: the projection shortcut (`p`: a block plan with ds_conv, ds_bn, ds_pool2, ds_stride) and conv1's backward
@@ -1295,24 +1321,31 @@ class _BottleneckNode(Function):
 
 
 def block_eligible(blk, x):
-    """training-mode cotnet.Bottleneck (no avd pooling, no drop-block/path) whose CotLayer is eligible"""
-    if not (ENABLED and blk.training and (x.is_cuda or not _lib.DEVICE_ONLY) and x.dim() == 4
-            and x.dtype == torch.bfloat16 and x.is_contiguous() and x.data_ptr() % 16 == 0):
+    """training-mode cotnet.Bottleneck / cotnet_hybrid.CoTBottleneck around a CotLayer or CoXtLayer, every form _BlockPlan.static_ok
+    admits: identity or projection shortcut (stride 2 or `avg_down`), average pooling in front of the layer or BlurPool behind it,
+    stochastic depth"""
+    if not (ENABLED and blk.training and _input_ok(x)):
         return False
     bp = _block_plan(blk)
-    if not (bp.static_ok and x.shape[1] == bp.conv1.in_channels and bp.conv1.weight.dtype == torch.bfloat16
-            and bp.conv3.weight.dtype == torch.bfloat16 and bp.bn1.weight.dtype == torch.float32 and bp.bn1.training
-            and (bp.ds_conv is not None or (bp.conv1.in_channels == bp.conv3.out_channels and not bp.avd))
-            and not (bp.ds_pool2 and (x.shape[2] % 2 or x.shape[3] % 2))):  # (cot_avgpool2x2s2_*: even planes)
-        return False
-    pl = _plan(bp.cot)
-    return (pl.ke0.weight.dtype == torch.bfloat16 and pl.em3.weight.dtype == torch.bfloat16
-            and pl.gn.weight.dtype == torch.bfloat16 and pl.bn.weight.dtype == torch.float32 and pl.bn.training)
+    return (bp.static_ok and _modes_ok(bp, True) and x.shape[1] == bp.conv1.in_channels
+            and not (bp.ds_pool2 and (x.shape[2] % 2 or x.shape[3] % 2)))  # (cot_avgpool2x2s2_*: even planes)
 
 
 def block_forward(blk, x):
     NODE_COUNTS["bottleneck"] += 1
     return _BottleneckNode.apply(blk, x, *_block_plan(blk).params)
+
+
+def dispatch(blk, x):
+    """-> blk(x) by the first node kind that takes it, or None: the caller runs the module path.  A block class states the kinds it
+    tries, in order, as `node_kinds` (cotnet.Bottleneck, cotnet_hybrid.CoTBottleneck); a kind is the NAME of this module's
+    NAME_eligible / NAME_forward pair, looked up per call (tests rebind them)"""
+    if ENABLED:
+        g = globals()
+        for kind in blk.node_kinds:
+            if g[kind + "_eligible"](blk, x):
+                return g[kind + "_forward"](blk, x)
+    return None
 
 
 # ---- the other node kinds live in their own modules (round 6 split; VERDICT r5 #9): SplitAttn blocks, channel-major Bottlenecks, the
@@ -1321,7 +1354,7 @@ def block_forward(blk, x):
 CM_LAYOUT = os.environ.get("COT_CM_LAYOUT", "1") != "0"
 CM_OPENING = os.environ.get("COT_CM_OPENING", "1") != "0"  # the stage's stride-2 opening block on the channel-major node too (A/B switch)
 GX_SLABS = os.environ.get("COT_GX_SLABS", "1") != "0"  # CoXtLayer.embed[0] in channel-major blocks: two-slab kernels per group instead of torch.stack (_cot_forward)
-from .cot_block_sa import (_SABlockPlan, _SA_PLANS, _SASIZES, _sa_plan, _sa_sizes, _SplitAttnBlockNode, sa_block_eligible,  # noqa: E402,F401
+from .cot_block_sa import (_SABlockPlan, _SASIZES, _sa_plan, _sa_sizes, _SplitAttnBlockNode, sa_block_eligible,  # noqa: E402,F401
                            sa_block_forward)
 from .cot_block_cm import (_CM_OK, _CM_SIZES, _BottleneckCMNode, _cm_buf, _cm_geometry_ok, _cm_sizes, _cm_static_ok, _cm_view,  # noqa: E402,F401
                            _is_cm, cm_block_eligible, cm_block_forward, plan_stage_layouts)

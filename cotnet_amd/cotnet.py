@@ -189,6 +189,8 @@ class CoXtLayer(nn.Module):
 
 class Bottleneck(nn.Module):
     expansion = 4
+    # the single-node forms cot_layer_fused.dispatch tries, in this order: inference, channel-major (deep stages), NCHW
+    node_kinds = ("eval_block", "cm_block", "block")
 
     def __init__(self, inplanes, planes, stride=1, downsample=None, cardinality=1, base_width=64, reduce_first=1,
                  dilation=1, first_dilation=None, act_layer=nn.ReLU, norm_layer=nn.BatchNorm2d, attn_layer=None,
@@ -221,12 +223,9 @@ class Bottleneck(nn.Module):
         nn.init.zeros_(self.bn3.weight)
 
     def forward(self, x):
-        if cot_layer_fused.ENABLED and not self.training and cot_layer_fused.eval_block_eligible(self, x):
-            return cot_layer_fused.eval_block_forward(self, x)  # inference: the block's launches back to back, nothing kept
-        if cot_layer_fused.ENABLED and cot_layer_fused.cm_block_eligible(self, x):
-            return cot_layer_fused.cm_block_forward(self, x)  # deep-stage identity block: one node, 1x1 operands channel-major
-        if cot_layer_fused.ENABLED and cot_layer_fused.block_eligible(self, x):
-            return cot_layer_fused.block_forward(self, x)  # the whole block as one autograd node (opt-in)
+        y = cot_layer_fused.dispatch(self, x)  # the whole block as one node (or one call sequence, inference)
+        if y is not None:
+            return y
         residual = x
         a1, a3 = act_name(self.act1), act_name(self.act3)
         fusable = self.drop_block is None and a1 is not False and a3 is not False

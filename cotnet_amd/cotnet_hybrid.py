@@ -33,6 +33,9 @@ class CoTLayer(CotLayer):
 
 class CoTBottleneck(nn.Module):
     expansion = 4
+    # the single-node forms cot_layer_fused.dispatch tries: `block` takes a block whose conv2 is a CotLayer, `sa_block` one whose
+    # conv2 is a SplitAttnConv2d -- one of the two per block; neither the inference nor the channel-major form
+    node_kinds = ("block", "sa_block")
 
     def __init__(self, block_idx, inplanes, planes, stride=1, downsample=None, cardinality=1, base_width=64,
                  reduce_first=1, dilation=1, first_dilation=None, act_layer=nn.ReLU, norm_layer=nn.BatchNorm2d,
@@ -85,12 +88,9 @@ class CoTBottleneck(nn.Module):
         nn.init.zeros_(self.bn3.weight)
 
     def forward(self, x):
-        if cot_layer_fused.ENABLED:  # the whole block as one autograd node (identity-shortcut / AvgPool-first blocks of both kinds)
-            if isinstance(self.conv2, CotLayer):
-                if cot_layer_fused.block_eligible(self, x):
-                    return cot_layer_fused.block_forward(self, x)
-            elif cot_layer_fused.sa_block_eligible(self, x):
-                return cot_layer_fused.sa_block_forward(self, x)
+        y = cot_layer_fused.dispatch(self, x)  # the whole block as one autograd node
+        if y is not None:
+            return y
         residual = x
         if self.drop_block is None:
             x = fused_bn_act(conv1x1(self.conv1, x), self.bn1, "relu")  # act1 is hard-wired ReLU (ref :124)

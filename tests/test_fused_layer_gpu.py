@@ -58,6 +58,45 @@ def test_ineligible_inputs_take_the_ordinary_forward(monkeypatch):
     assert y.shape == x.shape
 
 
+def test_a_frozen_batchnorm_keeps_a_training_block_off_the_block_nodes():
+    """partial freezing: bn3.eval() inside a training Bottleneck.  The block nodes normalise every BatchNorm with batch statistics and
+    overwrite its running statistics, so the block has to take the module path, which leaves bn3's buffers alone; back in train() the
+    block is one node again"""
+    torch.manual_seed(3)
+    blk = to_mixed_bf16(Bottleneck(256, 64).to(DEV).train())
+    with torch.no_grad():
+        blk.bn3.weight.fill_(0.8)
+        blk.bn3.running_mean.normal_(0, 0.3)
+        blk.bn3.running_var.uniform_(0.5, 1.5)
+    x = torch.randn(2, 256, 14, 14, device=DEV).bfloat16()
+    g = torch.randn(2, 256, 14, 14, device=DEV).bfloat16()
+    bns = {n: m for n, m in blk.named_modules() if isinstance(m, torch.nn.BatchNorm2d)}
+    assert len(bns) == 7
+
+    def step():
+        before = {n: int(m.num_batches_tracked) for n, m in bns.items()}
+        clf.reset_node_counts()
+        xi = x.clone().requires_grad_(True)
+        blk(xi).backward(g)
+        torch.cuda.synchronize()
+        assert xi.grad is not None and blk.conv1.weight.grad is not None and blk.conv3.weight.grad is not None
+        return {n: int(m.num_batches_tracked) - before[n] for n, m in bns.items()}
+
+    with truth.switches(**truth.SINGLE_NODE, cm=True):
+        blk.bn3.eval()
+        frozen = [t.clone() for t in (blk.bn3.running_mean, blk.bn3.running_var, blk.bn3.num_batches_tracked)]
+        moved = step()
+        assert clf.NODE_COUNTS["bottleneck"] == clf.NODE_COUNTS["bottleneck_channel_major"] == 0
+        for a, b in zip(frozen, (blk.bn3.running_mean, blk.bn3.running_var, blk.bn3.num_batches_tracked)):
+            assert torch.equal(a, b)
+        assert moved == {n: (0 if n == "bn3" else 1) for n in bns}
+        blk.bn3.train()
+        moved = step()
+        assert clf.NODE_COUNTS["bottleneck"] + clf.NODE_COUNTS["bottleneck_channel_major"] == 1
+        assert moved == {n: 1 for n in bns}
+        assert not torch.equal(frozen[0], blk.bn3.running_mean)
+
+
 def test_bottleneck_trains_with_the_single_node_layer():
     """two SGD steps of a Bottleneck with the fused layer node inside: loss decreases, parameters stay finite"""
     torch.manual_seed(0)
