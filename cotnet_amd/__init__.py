@@ -8,6 +8,7 @@ Public surface mirrors the reference (JDAI-CV/CoTNet):
     models.lr_net                        -> cotnet_amd.lr_net               (SelfAttLayer, Bottleneck, lrnet50, lrnet50_ks3)
     datasets.mixup (batch mode)          -> cotnet_amd.mixup                (DeviceMixup: host draw, device mixing)
     loss.cross_entropy                   -> cotnet_amd.loss                 (soft_target_cross_entropy, LabelSmoothingCrossEntropy)
+    evaler.evaler / utils.meters         -> cotnet_amd.evaler               (Evaler, DeviceTestMeter, accuracy: scored on the device)
     models.factory / models.registry     -> cotnet_amd.registry             (create_model, register_model)
 Device code lives in cotnet_amd/csrc (HIP, gfx950) behind the C ABI of include/cotnet_amd.h.
 """
@@ -24,6 +25,7 @@ from . import local_relation  # noqa: F401  (the sub-module: import the function
 from .lr_net import Bottleneck_Ks3, SelfAttLayer, lrnet50, lrnet50_ks3  # noqa: F401
 from .loss import LabelSmoothingCrossEntropy, MixedSoftTargetCrossEntropy, soft_target_cross_entropy  # noqa: F401
 from .mixup import DeviceMixup  # noqa: F401
+from .evaler import DeviceTestMeter, Evaler, accuracy  # noqa: F401
 from .registry import create_model, list_models, load_checkpoint, register_model  # noqa: F401
 from .resnet import ResNet  # noqa: F401
 

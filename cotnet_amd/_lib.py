@@ -146,6 +146,7 @@ SYMBOLS = {
     "cot_mix_normalize": (_I, [_P] * 5 + [_I] * 5 + [_P]),
     "cot_soft_target_ce_forward": (_I, [_P, _P, _P, ctypes.c_double, _P, _P, _P, _I, _I, _I, _P]),
     "cot_soft_target_ce_backward": (_I, [_P, _P, _P, ctypes.c_double, _P, _P, _P, _I, _I, _I, _P]),
+    "cot_eval_score": (_I, [_P] * 5 + [_I, _I, _I, _P]),
     "cot_bn_act_workspace": (_I, [_I, _I]),
     "cot_bn_act_forward": (_I, [_P] * 11 + [_I, _I, _I, ctypes.c_float, ctypes.c_float, _I, _I, _P]),
     "cot_bn_act_backward": (_I, [_P] * 12 + [_I, _I, _I, _I, _I, _P]),

@@ -1386,6 +1386,20 @@ int cot_soft_target_ce_backward(const void* logits, const void* labels, const vo
                             (hipStream_t)stream);
 }
 
+int cot_eval_score(const void* logits, const void* labels, void* acc, void* row_rank, void* row_nll, int N, int K, int dtype,
+                   void* stream) {
+    if (!logits || !labels) return set_error(COT_ERR_INVALID_ARG, "NULL device pointer");
+    if (!acc) return set_error(COT_ERR_INVALID_ARG, "NULL acc (the device block the batch is added to)");
+    if (N < 1 || K < 1) return set_error(COT_ERR_INVALID_ARG, "bad N=%d / K=%d", N, K);
+    if ((uintptr_t)acc % 8 != 0) return set_error(COT_ERR_INVALID_ARG, "acc %p is not 8-byte aligned", acc);
+    if ((uintptr_t)labels % 8 != 0) return set_error(COT_ERR_INVALID_ARG, "labels %p is not 8-byte aligned (int64)", labels);
+    if (dtype != COT_F32 && dtype != COT_BF16)
+        return set_error(COT_ERR_UNSUPPORTED, "cot_eval_score: logits dtype %d (float32 / bfloat16)", dtype);
+    if ((uintptr_t)logits % (dtype == COT_F32 ? 4 : 2) != 0) return set_error(COT_ERR_INVALID_ARG, "logits %p is not element-aligned", logits);
+    if ((uintptr_t)row_rank % 4 || (uintptr_t)row_nll % 4) return set_error(COT_ERR_INVALID_ARG, "row_rank / row_nll must be 4-byte aligned");
+    return eval_score(logits, labels, acc, (int*)row_rank, (float*)row_nll, N, K, dtype, (hipStream_t)stream);
+}
+
 int cot_bn_act_workspace(int N, int C) { return (N > 0 && C > 0) ? bn_workspace_floats(N, C) : 0; }
 
 // the bodies of the BatchNorm entry points without / with a ReLU sign mask (`mask`, NULL = none; -3 = the kernel serving the geometry

@@ -238,4 +238,7 @@ int soft_ce_forward(const void* logits, const void* labels, const void* params, 
 int soft_ce_backward(const void* logits, const void* labels, const void* params, double smoothing, const float* row_lse, const float* grad_out,
                      void* dlogits, int N, int K, int dtype, hipStream_t s);
 
+// ---- eval_score.hip: top-1 / top-5 / loss of a validation batch, added to an accumulator block in device memory
+int eval_score(const void* logits, const void* labels, void* acc, int* row_rank, float* row_nll, int N, int K, int dtype, hipStream_t s);
+
 }  // namespace cot

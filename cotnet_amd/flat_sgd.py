@@ -15,6 +15,8 @@ On MI355X the step is bound by HBM passes and launch count, so this module
 Arithmetic = torch.optim.SGD (dampening 0) evaluated in fp32 on the master weights; checked against it in
 tests/test_flat_sgd_gpu.py.
 """
+import contextlib
+
 import torch
 from torch import nn
 
@@ -143,6 +145,46 @@ class FlatSGD:
                 bf = bufs[k]
                 out[k] = by_buf[id(bf)].clone() if id(bf) in by_buf else bf.detach().clone()
         return out
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """`with opt.ema_weights(): evaler(epoch, model)`: run the AVERAGED weights through the model's own parameters -- what the
+        reference does with a second model (`evaler(epoch, model_ema.module)`, train.py:352-355) and `ema_state_dict()` could only
+        serve through a clone of every tensor, a second network and its own packings.
+
+        On entry each bucket's flat parameters receive its fp32 average cast to the bucket's dtype (round to nearest even, as
+        `.to(torch.bfloat16)` does) and every floating-point buffer its averaged value; the caches keyed on the parameters' version are
+        moved on.  The parameters keep their addresses, so a HIP graph that captured the model's forward runs the average when it is
+        replayed inside the context.  On exit everything is put back bit for bit and the caches are moved on again: buckets with a
+        master from the master (the working copy is always the rounded master), fp32 buckets and the buffers from copies taken on
+        entry.  Masters, momentum, the averages and integer buffers are never written.  No step() inside the context; refused while a
+        HIP graph is being captured (the recorded copies would swap the weights at every replay)."""
+        assert self.ema_decay is not None, "FlatSGD was built without ema_decay"
+        if _lib.capturing():
+            raise RuntimeError("FlatSGD.ema_weights() inside a HIP-graph capture: the copies would be recorded and swap the weights at "
+                               "every replay -- enter the context outside the capture (a captured forward reads the weights when it runs)")
+        from . import cot_layer_fused
+        buckets = self.reducer.buckets
+        device = buckets[0].pflat.device if buckets else None
+        kept = [b.pflat.clone() if st["master"] is None else None for b, st in zip(buckets, self.state)]
+        kept_bufs = [bf.detach().clone() for bf in self._buf_src]
+        with torch.no_grad():
+            for b, st in zip(buckets, self.state):
+                b.pflat.copy_(st["ema"])
+            for bf, e in zip(self._buf_src, self._buf_ema):
+                bf.copy_(e)
+        if buckets:
+            cot_layer_fused.after_optimizer_step(device)
+        try:
+            yield self
+        finally:
+            with torch.no_grad():
+                for b, st, k in zip(buckets, self.state, kept):
+                    b.pflat.copy_(st["master"] if k is None else k)
+                for bf, k in zip(self._buf_src, kept_bufs):
+                    bf.copy_(k)
+            if buckets:
+                cot_layer_fused.after_optimizer_step(device)
 
     def set_lr(self, lr):
         """the rate of the steps issued from here on.

@@ -537,6 +537,29 @@ int cot_soft_target_ce_forward(const void* logits, const void* labels, const voi
 int cot_soft_target_ce_backward(const void* logits, const void* labels, const void* params, double smoothing, const void* row_lse,
                                 const void* grad_out, void* dlogits, int N, int K, int dtype, void* stream);
 
+/* ---- scoring a validation pass on the device (reference: utils/meters.py `accuracy`, :12-19, and TestMeter.update_stats, :154-157;
+ * evaler/evaler.py:50-52 reads the counts back and synchronises after every batch).  One call ADDS a batch to an accumulator block in
+ * DEVICE memory, 8-byte aligned, which the caller zeroes before a pass and reads once after it; the calls of a pass are ordered by
+ * the stream.  logits [N, K] row-major (COT_F32 or COT_BF16), labels int64 [N].  With y the label of row n and t = logit[n, y]:
+ *     rank = #{j : greater(logit[n,j], t)} + #{j < y : same(logit[n,j], t)}    the target's place in a stable descending sort, where
+ *            greater(a, b) = a > b || (isnan(a) && !isnan(b)),  same(a, b) = a == b || (isnan(a) && isnan(b))   (NaN sorts first)
+ *     samples += 1,  top1 += rank == 0,  top5 += rank < 5
+ *     nll  = logsumexp_j(logit[n,j]) - t: the maximum in fp32, the sum of exponentials and the result in fp64;  nll_sum += nll
+ * A label outside [0, K) makes the row SKIPPED: it adds nothing, row_rank[n] = -1, row_nll[n] = +0.0f -- a padded last batch carries
+ * the label -1 in its tail.  Labels are only compared with column indices, never used as an address.
+ * row_rank (int32 [N]) and row_nll (fp32 [N], the fp64 value rounded once) receive the rows' results; either may be NULL.
+ * Two launches (rows, then one workgroup that adds the rows in ascending order and updates the block with a plain read-modify-write)
+ * per 4096 rows; no atomics: the same bits on every run, recorded into a HIP graph or not.  Nothing about the batch but N, K and
+ * the pointers is a kernel argument.  The rows' results pass between the launches through device memory the library owns, one area per
+ * device: calls on different streams of one device must be ordered by the caller.
+ * NULL logits / labels / acc, N < 1, K < 1 or a misaligned pointer: COT_ERR_INVALID_ARG; any other dtype: COT_ERR_UNSUPPORTED. */
+typedef struct cot_eval_acc {
+    int64_t samples, top1, top5;
+    double nll_sum;
+} cot_eval_acc;
+int cot_eval_score(const void* logits, const void* labels, void* acc, void* row_rank, void* row_nll, int N, int K, int dtype,
+                   void* stream);
+
 /* ---- training-mode BatchNorm2d fused with activation and residual add, NCHW.
  * Replaces nn.BatchNorm2d + in-place ReLU/SiLU (+ `x += residual`) sequences of the reference's blocks
  * (models/cotnet.py:231-235, :248-262, :89-90):
