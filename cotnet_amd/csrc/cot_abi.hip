@@ -341,6 +341,44 @@ int cot_sgd_step_lr(void* param, void* master, void* momentum_buf, const void* g
                        nesterov, param_dtype, grad_dtype, (hipStream_t)stream);
 }
 
+int cot_grad_norm_parts(void) { return COT_GRAD_NORM_PARTS; }
+
+int cot_grad_sumsq(const void* grad, int64_t n, int grad_dtype, void* partials, void* stream) {
+    if (!grad) return set_error(COT_ERR_INVALID_ARG, "NULL device pointer");
+    if (!partials) return set_error(COT_ERR_INVALID_ARG, "NULL partials (the %d floats the launch writes)", COT_GRAD_NORM_PARTS);
+    if (n <= 0) return set_error(COT_ERR_INVALID_ARG, "non-positive element count %lld", (long long)n);
+    int rc = check_align16({grad});
+    if (rc) return rc;
+    if ((uintptr_t)partials % 4 != 0) return set_error(COT_ERR_INVALID_ARG, "partials %p is not 4-byte aligned", partials);
+    if (grad_dtype != COT_F32 && grad_dtype != COT_BF16)
+        return set_error(COT_ERR_UNSUPPORTED, "cot_grad_sumsq: gradient dtype %d (float32 / bfloat16)", grad_dtype);
+    return grad_sumsq(grad, n, grad_dtype, (float*)partials, (hipStream_t)stream);
+}
+
+int cot_grad_clip_finish(const void* partials, int64_t nparts, float max_norm, void* state, void* stream) {
+    if (!partials) return set_error(COT_ERR_INVALID_ARG, "NULL partials");
+    if (!state) return set_error(COT_ERR_INVALID_ARG, "NULL clip_state (the device block the step's coefficient is written to)");
+    if (nparts <= 0) return set_error(COT_ERR_INVALID_ARG, "non-positive partial count %lld", (long long)nparts);
+    if (!(max_norm > 0.f)) return set_error(COT_ERR_INVALID_ARG, "max_norm %g is not positive (+inf: guard only)", (double)max_norm);
+    if ((uintptr_t)partials % 4 != 0) return set_error(COT_ERR_INVALID_ARG, "partials %p is not 4-byte aligned", partials);
+    if ((uintptr_t)state % 4 != 0) return set_error(COT_ERR_INVALID_ARG, "clip_state %p is not 4-byte aligned", state);
+    return grad_clip_finish((const float*)partials, nparts, max_norm, state, (hipStream_t)stream);
+}
+
+int cot_sgd_step_clip(void* param, void* master, void* momentum_buf, const void* grad, int64_t n, float lr, const void* lr_dev,
+                      const void* clip_state, float momentum, float weight_decay, float grad_scale, int nesterov, int param_dtype,
+                      int grad_dtype, void* stream) {
+    if (!param || !momentum_buf || !grad) return set_error(COT_ERR_INVALID_ARG, "NULL device pointer");
+    if (!clip_state) return set_error(COT_ERR_INVALID_ARG, "NULL clip_state (the device block the step's coefficient is read from)");
+    if (n <= 0) return set_error(COT_ERR_INVALID_ARG, "non-positive element count %lld", (long long)n);
+    int rc = check_align16({param, master, momentum_buf, grad});
+    if (rc) return rc;
+    if ((uintptr_t)lr_dev % 4 != 0) return set_error(COT_ERR_INVALID_ARG, "lr_dev %p is not 4-byte aligned", lr_dev);
+    if ((uintptr_t)clip_state % 4 != 0) return set_error(COT_ERR_INVALID_ARG, "clip_state %p is not 4-byte aligned", clip_state);
+    return sgd_flat_clip(param, master, momentum_buf, grad, n, lr, (const float*)lr_dev, (const cot_clip_state*)clip_state, momentum,
+                         weight_decay, grad_scale, nesterov, param_dtype, grad_dtype, (hipStream_t)stream);
+}
+
 int cot_ema_step(void* ema, const void* src, int64_t n, float decay, int src_dtype, void* stream) {
     if (!ema || !src) return set_error(COT_ERR_INVALID_ARG, "NULL device pointer");
     if (n <= 0) return set_error(COT_ERR_INVALID_ARG, "non-positive element count %lld", (long long)n);

@@ -54,6 +54,12 @@ int sgd_flat(void* param, void* master, void* mom, const void* grad, int64_t n, 
              int param_dtype, int grad_dtype, hipStream_t s);
 int sgd_flat_lr(void* param, void* master, void* mom, const void* grad, int64_t n, const float* lr_dev, float momentum, float wd, float gscale,
                 int nesterov, int param_dtype, int grad_dtype, hipStream_t s);
+int sgd_flat_clip(void* param, void* master, void* mom, const void* grad, int64_t n, float lr, const float* lr_dev, const cot_clip_state* clip,
+                  float momentum, float wd, float gscale, int nesterov, int param_dtype, int grad_dtype, hipStream_t s);
+
+// ---- grad_clip.hip: the gradients' global norm -> clip coefficient / skip flag in a block in device memory (read by sgd_flat_clip)
+int grad_sumsq(const void* grad, int64_t n, int grad_dtype, float* partials, hipStream_t s);
+int grad_clip_finish(const float* partials, int64_t nparts, float max_norm, void* state, hipStream_t s);
 
 // ---- bn_act.hip: BatchNorm (+ activation, residual); `mask`: ReLU sign mask or NULL; -2 / -3 = geometry not covered / kernel takes no mask
 extern int g_bn_fold, g_bn_grid_cap, g_bn_split_target, g_bn_small_m, g_bn_chan, g_bn_chan7, g_bn_chan_rr;

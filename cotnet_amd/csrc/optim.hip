@@ -22,12 +22,30 @@ namespace cot {
 __device__ __forceinline__ float sgd_rate(float lr) { return lr; }
 __device__ __forceinline__ float sgd_rate(const float* __restrict__ lr_dev) { return *lr_dev; }
 
+// LR = SgdClipped (cot_sgd_step_clip): the rate from either source, behind the clip block that cot_grad_clip_finish left in device
+// memory (grad_clip.hip).  Every lane reads the block's `scale` and `skip` once in front of the loop, next to the rate: skip != 0
+// ends the kernel before it has written anything; otherwise the gradient's factor becomes the ONE fp32 product gscale * scale, and
+// the expression below is the same.  The other two forms have no block: their sgd_gate is the constant `true`.
+struct SgdClipped {
+    float lr;
+    const float* lr_dev;  // NULL: `lr`
+    const cot_clip_state* clip;
+};
+__device__ __forceinline__ float sgd_rate(const SgdClipped& a) { return a.lr_dev ? *a.lr_dev : a.lr; }
+__device__ __forceinline__ bool sgd_gate(float, float&) { return true; }
+__device__ __forceinline__ bool sgd_gate(const float*, float&) { return true; }
+__device__ __forceinline__ bool sgd_gate(const SgdClipped& a, float& gscale) {
+    gscale *= a.clip->scale;
+    return a.clip->skip == 0;
+}
+
 template <typename PT, typename GT, bool HAS_MASTER, int V, typename LR>
 __global__ __launch_bounds__(256) void sgd_flat_kernel(PT* __restrict__ param, float* __restrict__ master,
                                                       float* __restrict__ mom, const GT* __restrict__ grad,
                                                       int64_t n, LR lr_arg, float momentum, float wd, float gscale,
                                                       int nesterov) {
     const float lr = sgd_rate(lr_arg);
+    if (!sgd_gate(lr_arg, gscale)) return;
     const int64_t nvec = n / V;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nvec; i += (int64_t)gridDim.x * blockDim.x) {
         const Vec<GT, V> gv = ldv<GT, V>(grad + i * V);
@@ -110,10 +128,12 @@ static int launch_sgd(void* param, void* master, void* mom, const void* grad, in
     if (blocks > 2048) blocks = 2048;  // grid-stride: 8 blocks per CU
     COT_LAUNCH((sgd_flat_kernel<PT, GT, HAS_MASTER, V, LR>), dim3((unsigned)blocks), dim3(256), 0, s, (PT*)param,
                (float*)master, (float*)mom, (const GT*)grad, n, lr, momentum, wd, gscale, nesterov);
-    return check_launch(std::is_pointer<LR>::value ? "sgd_flat_kernel<lr_dev>" : "sgd_flat_kernel");
+    return check_launch(std::is_same<LR, SgdClipped>::value ? "sgd_flat_kernel<clip>"
+                        : std::is_pointer<LR>::value        ? "sgd_flat_kernel<lr_dev>"
+                                                            : "sgd_flat_kernel");
 }
 
-template <typename LR>  // float (cot_sgd_step) or const float* (cot_sgd_step_lr)
+template <typename LR>  // float (cot_sgd_step), const float* (cot_sgd_step_lr) or SgdClipped (cot_sgd_step_clip)
 static int sgd_dispatch(void* param, void* master, void* mom, const void* grad, int64_t n, LR lr, float momentum, float wd,
                         float gscale, int nesterov, int param_dtype, int grad_dtype, hipStream_t s) {
     if (param_dtype == COT_BF16 && grad_dtype == COT_BF16 && master)
@@ -137,6 +157,13 @@ int sgd_flat_lr(void* param, void* master, void* mom, const void* grad, int64_t 
                 float wd, float gscale, int nesterov, int param_dtype, int grad_dtype, hipStream_t s) {
     return sgd_dispatch<const float*>(param, master, mom, grad, n, lr_dev, momentum, wd, gscale, nesterov, param_dtype,
                                       grad_dtype, s);
+}
+
+int sgd_flat_clip(void* param, void* master, void* mom, const void* grad, int64_t n, float lr, const float* lr_dev,
+                  const cot_clip_state* clip, float momentum, float wd, float gscale, int nesterov, int param_dtype, int grad_dtype,
+                  hipStream_t s) {
+    return sgd_dispatch<SgdClipped>(param, master, mom, grad, n, SgdClipped{lr, lr_dev, clip}, momentum, wd, gscale, nesterov,
+                                    param_dtype, grad_dtype, s);
 }
 
 }  // namespace cot

@@ -10,7 +10,9 @@ On MI355X the step is bound by HBM passes and launch count, so this module
     (cotnet_amd.data_parallel.GradBucketReducer with flatten_params=True, grad_mode="copy": autograd's gradients are
     moved into the bucket with one multi-tensor copy, then all-reduced over RCCL on the side stream);
   * updates each bucket with ONE hand-written HIP kernel (`cot_sgd_step`, csrc/optim.hip; `cot_sgd_step_lr` with
-    device_lr=True: the rate read from device memory, so that a step replayed from a HIP graph follows a schedule).
+    device_lr=True: the rate read from device memory, so that a step replayed from a HIP graph follows a schedule;
+    `cot_sgd_step_clip` with clip_grad / skip_nonfinite: behind the gradients' global norm, formed on the device by
+    `cot_grad_sumsq` + `cot_grad_clip_finish`, csrc/grad_clip.hip -- the reference's `dispatch_clip_grad`, train.py:269-274).
 
 Arithmetic = torch.optim.SGD (dampening 0) evaluated in fp32 on the master weights; checked against it in
 tests/test_flat_sgd_gpu.py.
@@ -41,7 +43,8 @@ def _decay_group(name, p):
 
 class FlatSGD:
     def __init__(self, model, lr, momentum=0.9, weight_decay=0.0, nesterov=True, bucket_mb=10.0, process_group=None,
-                 broadcast_params=True, ema_decay=None, force_collectives=False, grad_dtype=None, device_lr=False):
+                 broadcast_params=True, ema_decay=None, force_collectives=False, grad_dtype=None, device_lr=False, clip_grad=None,
+                 clip_mode="norm", skip_nonfinite=False):
         """bucket_mb: size of the flat gradient buckets.  10 MiB cuts CoTNet-50's 44 MB of bf16 weight gradients into five
         buckets in the order backward produces them (classifier and stage 4 first, the stem last), so four all-reduces are
         already on the communication stream when backward ends and only the last, small one is exposed; round 2's 48 MiB
@@ -62,7 +65,24 @@ class FlatSGD:
         was captured with (set_lr).  True: the rate lives in `self.lr_dev`, one fp32 element on the parameters' device, allocated
         here once (its address never changes); step() issues `cot_sgd_step_lr`, whose kernel reads that element when it runs, so a
         capture bakes no rate and set_lr between replays moves the replayed step (lr_schedule.CosineSchedule.apply).  Same
-        arithmetic on the same fp32 rate: the two forms are bit-equal (tests/test_sgd_device_lr_gpu.py)."""
+        arithmetic on the same fp32 rate: the two forms are bit-equal (tests/test_sgd_device_lr_gpu.py).
+        clip_grad: clip the gradients to this global L2 norm before the step, as the reference does between backward and
+        optimizer.step() (train.py:269-274, `dispatch_clip_grad(..., mode='norm')` = torch.nn.utils.clip_grad_norm_); None or <= 0: no
+        clipping (the reference's convention, train.py:270).  The norm runs over EVERY bucket, decay and no-decay alike, on the
+        averaged gradients (after the all-reduce: the same coefficient on every rank).
+        clip_mode: only "norm"; the reference's 'value' and 'agc' (utils/clip_grad.py:36-39) are not built.
+        skip_nonfinite: a step whose gradients hold an inf or a NaN (or whose sum of squares overflows) writes no parameter, master
+        or momentum; the EMA still moves, as the reference's does behind a step its scaler skipped (train.py:276-277).
+        With either, step() issues `cot_grad_sumsq` per bucket, one `cot_grad_clip_finish` and `cot_sgd_step_clip` per bucket
+        (csrc/grad_clip.hip): norm, coefficient and skip flag stay in `self.clip_state` (int32[8] = cot_clip_state, allocated here
+        once next to the partial sums; the addresses never change), nothing about a batch is a kernel argument, and one HIP-graph
+        capture serves clipped, unclipped and skipped steps alike.  A non-finite step is ALWAYS skipped when clip_grad is set
+        (torch's clip_grad_norm_ multiplies every gradient by the NaN coefficient, and the step then poisons every weight);
+        skip_nonfinite=True alone asks for the guard with the coefficient 1.  `clip_stats()` reads the block.  With neither,
+        nothing is allocated and the launches are the ones of the plain optimizer."""
+        if clip_mode != "norm":
+            raise ValueError(f"FlatSGD(clip_mode={clip_mode!r}): only 'norm' (clipping by the global L2 norm) is built; the reference's "
+                             "other modes 'value' and 'agc' are not")
         self.lr, self.momentum, self.weight_decay, self.nesterov = float(lr), float(momentum), float(weight_decay), nesterov
         self.ema_decay = None if ema_decay is None else float(ema_decay)
         self._captured_lr = None  # the rate a HIP-graph capture of step() baked into its cot_sgd_step launches (set_lr)
@@ -83,6 +103,14 @@ class FlatSGD:
         if device_lr:
             dev = self.reducer.buckets[0].pflat.device if self.reducer.buckets else next(model.parameters()).device
             self.lr_dev = torch.full((1,), self.lr, dtype=torch.float32, device=dev)
+        self.clip_grad = float(clip_grad) if clip_grad is not None and clip_grad > 0 else None
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self.clip_state = self._clip_parts = None
+        if self.clip_grad is not None or self.skip_nonfinite:
+            dev = self.reducer.buckets[0].pflat.device if self.reducer.buckets else next(model.parameters()).device
+            self.clip_state = torch.zeros(8, dtype=torch.int32, device=dev)
+            self._clip_parts = torch.zeros(max(len(self.reducer.buckets), 1) * _lib.lib().cot_grad_norm_parts(), dtype=torch.float32,
+                                           device=dev)
         if self.ema_decay is not None:
             self._buf_src = [bf for bf in model.buffers() if bf.is_floating_point()]
             self._buf_ema = [bf.detach().float().clone() for bf in self._buf_src]
@@ -101,18 +129,29 @@ class FlatSGD:
         L = _lib.api()
         stream = _lib.stream()
         if self.lr_dev is not None:  # the kernel reads the rate when it runs: a capture bakes none
-            sgd, rate = L.cot_sgd_step_lr, self.lr_dev.data_ptr()
+            sgd, rate = L.cot_sgd_step_lr, (self.lr_dev.data_ptr(),)
         else:
-            sgd, rate = L.cot_sgd_step, self.lr
+            sgd, rate = L.cot_sgd_step, (self.lr,)
             if _lib.capturing():  # cot_sgd_step takes the rate by value: every replay of this capture steps with it (set_lr)
                 self._captured_lr = self.lr
+        if self.clip_state is not None and self.reducer.buckets:
+            # the norm of the AVERAGED gradients over every bucket -> coefficient and skip flag in self.clip_state, which the SGD
+            # kernels below read when they run
+            parts = L.cot_grad_norm_parts()
+            for i, b in enumerate(self.reducer.buckets):
+                g = self.reducer.reduced(b)
+                L.cot_grad_sumsq(g.data_ptr(), g.numel(), _lib.dtype_code(g.dtype), self._clip_parts.data_ptr() + 4 * parts * i, stream)
+            L.cot_grad_clip_finish(self._clip_parts.data_ptr(), self._clip_parts.numel(),
+                                   self.clip_grad if self.clip_grad is not None else float("inf"), self.clip_state.data_ptr(), stream)
+            sgd = L.cot_sgd_step_clip
+            rate = (self.lr, self.lr_dev.data_ptr() if self.lr_dev is not None else None, self.clip_state.data_ptr())
         for b, st in zip(self.reducer.buckets, self.state):
             key = b.key
             wd = self.weight_decay if key == "decay" else 0.0
             sgd(b.pflat.data_ptr(),
                 st["master"].data_ptr() if st["master"] is not None else None,
                 st["mom"].data_ptr(), self.reducer.reduced(b).data_ptr(),
-                b.pflat.numel(), rate, self.momentum, wd, 1.0, 1 if self.nesterov else 0,
+                b.pflat.numel(), *rate, self.momentum, wd, 1.0, 1 if self.nesterov else 0,
                 _lib.dtype_code(b.pflat.dtype), _lib.dtype_code(self.reducer.reduced(b).dtype), stream)
             if self.ema_decay is not None:
                 src = st["master"] if st["master"] is not None else b.pflat
@@ -124,6 +163,21 @@ class FlatSGD:
         if self.reducer.buckets:  # the parameters changed behind torch's version counters: caches keyed on them move on
             from . import cot_layer_fused
             cot_layer_fused.after_optimizer_step(self.reducer.buckets[0].pflat.device)
+
+    def clip_stats(self):
+        """ONE host read of the clip block: dict(total_norm, scale, skip, steps, clipped, skipped) -- the last step's norm, coefficient
+        and skip flag, and the counts since construction (or since the caller last zeroed `self.clip_state`).  It synchronises with
+        the device, so it belongs at a logging interval, not in every step; refused while a HIP graph is being captured (the read
+        would see what the block held before the capture: recorded launches have not run)."""
+        if self.clip_state is None:
+            raise RuntimeError("FlatSGD.clip_stats(): built with neither clip_grad nor skip_nonfinite")
+        if _lib.capturing():
+            raise RuntimeError("FlatSGD.clip_stats() inside a HIP-graph capture: the launches that fill the block are only recorded, "
+                               "and a host read cannot be -- read the block between replays")
+        w = self.clip_state.cpu()
+        scale, total_norm = w[:2].view(torch.float32).tolist()
+        skip, steps, clipped, skipped = w[2:6].tolist()
+        return dict(total_norm=total_norm, scale=scale, skip=skip, steps=steps, clipped=clipped, skipped=skipped)
 
     def ema_state_dict(self):
         """the averaged weights under the model's own state_dict keys (fp32; integer buffers are copied as they are) --

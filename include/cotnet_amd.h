@@ -475,6 +475,70 @@ int cot_sgd_step_lr(void* param, void* master, void* momentum_buf, const void* g
                     float momentum, float weight_decay, float grad_scale, int nesterov, int param_dtype, int grad_dtype,
                     void* stream);
 
+/* ---- clipping the gradients by their global norm, and skipping a step whose gradients are not finite, on the device (reference:
+ * `loss.backward(); dispatch_clip_grad(...); optimizer.step()`, train.py:269-274; utils/clip_grad.py:26-41 with mode 'norm' ->
+ * torch.nn.utils.clip_grad_norm_; config/config.py:114-115).  The gradients live in flat buckets and a replayed HIP graph has no host
+ * code between its kernels, so the norm, the coefficient and the decision to skip stay in device memory:
+ *   1. cot_grad_sumsq        per bucket: COT_GRAD_NORM_PARTS fp32 partial sums of squares
+ *   2. cot_grad_clip_finish  once: the partials of every bucket -> one 32-byte block, cot_clip_state
+ *   3. cot_sgd_step_clip     per bucket: cot_sgd_step / cot_sgd_step_lr with the block's coefficient on the gradient, or no write at
+ *                            all when the block says skip
+ * Nothing about a batch is a kernel argument: one recorded sequence serves clipped, unclipped and skipped steps alike.  No atomics:
+ * which workgroup adds which element, and in what order, depends on n and the constants below alone, so equal gradients give equal
+ * bits on every run, eager or replayed.
+ *
+ * The block (4-byte aligned, device memory; the caller zeroes it once, cot_grad_clip_finish writes every word of it, the SGD kernel
+ * only reads it; successive calls are ordered by the stream): */
+typedef struct cot_clip_state {
+    float scale;         /* the last step's coefficient min(1, max_norm / (total_norm + 1e-6)); 0 when that step is skipped */
+    float total_norm;    /* the last step's global L2 norm; inf or NaN when it is not finite */
+    int32_t skip;        /* 1 if the last step's sum of squares is not finite, else 0 */
+    int32_t steps;       /* calls since the caller last zeroed the block */
+    int32_t clipped;     /* ... of them with a finite norm and scale < 1 */
+    int32_t skipped;     /* ... of them with skip == 1 */
+    int32_t reserved[2]; /* written 0 */
+} cot_clip_state;
+
+/* Workgroups of one cot_grad_sumsq launch = fp32 partials it writes.  256 lanes each, 16 bytes per lane and load, four loads of a
+ * lane issued before the first is used.  Measured on the MI355X at CoTNet-50's seven bucket sizes, every bucket's launch plus the
+ * finish replayed from one HIP graph, operands rotating through > 512 MB (profiles/grad_clip_bench.log; bf16 / fp32 gradients):
+ *     64: 55.1 / 77.0 us    128: 46.5 / 56.4    256: 46.2 / 53.4    512: 53.7 / 58.6    1024: 72.0 / 77.6
+ * At these sizes (<= 10 MB per launch) the sequence is bound by its eight launches and by the finish, not by HBM: every partial is
+ * one more fp64 addition in the ONE chain of the lane that finishes (~5 ns each: 17 us for 7 x 256, 46 us for 7 x 1024), and one
+ * workgroup per CU already keeps the loads of a bucket in flight.  256 is the fastest for both dtypes. */
+#define COT_GRAD_NORM_PARTS 256
+int cot_grad_norm_parts(void); /* = COT_GRAD_NORM_PARTS; makes no HIP call */
+
+/* partials[i] = the sum of squares of workgroup i's share of grad[0..n), fp32; 0 for a workgroup without a share.  ALWAYS
+ * COT_GRAD_NORM_PARTS workgroups and as many floats written, whatever n.  grad COT_F32 or COT_BF16 (16-byte aligned), squares and
+ * sums in fp32: a lane adds its squares in ascending order of address into one sum per vector slot, the slots pairwise, the tail
+ * element (n % V, first lanes of workgroup 0), then the wave's 64 lanes by six exchange stages and the workgroup's four waves in
+ * order (csrc/grad_clip.hip states the length of the longest chain as a function of n).  An inf, a NaN or a square that overflows
+ * fp32 makes its workgroup's partial inf or NaN; the others stay finite.
+ * NULL grad / partials, n < 1, grad not 16-byte or partials not 4-byte aligned: COT_ERR_INVALID_ARG; any other dtype:
+ * COT_ERR_UNSUPPORTED -- reported through cot_last_error() before any device work. */
+int cot_grad_sumsq(const void* grad, int64_t n, int grad_dtype, void* partials, void* stream);
+
+/* One workgroup adds partials[0..nparts) in ascending index order in fp64 (nparts = buckets x COT_GRAD_NORM_PARTS, contiguous) and
+ * writes the block:
+ *     total_norm = (float)sqrt(sum)
+ *     sum finite:      c = max_norm / (total_norm + 1e-6f) in fp32, scale = c < 1 ? c : 1   (torch's clip_grad_norm_), skip = 0
+ *     sum not finite:  scale = 0, skip = 1   (a partial that only overflowed fp32 on the way counts: its bucket cannot be scaled)
+ *     steps += 1, clipped += (skip == 0 && scale < 1), skipped += skip    lane 0's plain read-modify-write
+ * max_norm = +inf is valid and means "guard only": scale is 1 whenever the norm is finite.  max_norm <= 0 or NaN, NULL or
+ * misaligned (4 bytes) partials / state, nparts < 1: COT_ERR_INVALID_ARG before any device work. */
+int cot_grad_clip_finish(const void* partials, int64_t nparts, float max_norm, void* state, void* stream);
+
+/* cot_sgd_step (lr_dev == NULL: the rate by value) or cot_sgd_step_lr (lr_dev given: read from memory when the kernel runs, `lr`
+ * ignored) behind the block: every lane reads scale and skip once in front of its loop, as it reads the rate.  skip != 0: the kernel
+ * returns without writing anything -- param, master and momentum_buf keep their bits.  Otherwise the same expression with the one
+ * fp32 factor grad_scale * scale in place of grad_scale, so that a block {scale = c, skip = 0} is bit-identical to cot_sgd_step with
+ * grad_scale' = fp32(grad_scale * c).  The block is only read.  clip_state NULL or not 4-byte aligned: COT_ERR_INVALID_ARG; every
+ * other argument is validated as for cot_sgd_step / cot_sgd_step_lr. */
+int cot_sgd_step_clip(void* param, void* master, void* momentum_buf, const void* grad, int64_t n, float lr, const void* lr_dev,
+                      const void* clip_state, float momentum, float weight_decay, float grad_scale, int nesterov, int param_dtype,
+                      int grad_dtype, void* stream);
+
 /* ---- exponential moving average of the weights over a flat buffer (replaces the per-tensor
  * `ema = decay*ema + (1-decay)*model` of ModelEmaV2._update, utils/model_ema.py:45-53):  ema fp32 [n], src the fp32
  * master copy / fp32 parameters (COT_F32) or bf16 parameters (COT_BF16). */
