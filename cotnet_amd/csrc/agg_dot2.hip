@@ -45,7 +45,7 @@ typedef __attribute__((ext_vector_type(2))) __bf16 cot_bf16x2;
 // acc + a.lo*b.lo + a.hi*b.hi on packed bf16 pairs (v_dot2c_f32_bf16)
 #define COT_DOT2_BF16(a, b, acc) \
     __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(cot_bf16x2, (uint32_t)(a)), __builtin_bit_cast(cot_bf16x2, (uint32_t)(b)), (acc), false)
-// lane l <- lane l-1 / l+1 inside its 16-lane DPP row; the row's first / last lane <- 0 (bound_ctrl)
+// lane l <- lane l-1 / l+1 inside its 16-lane DPP row; the row's first / last lane <- 0 (bound_ctrl).  Exchanges, not reductions: not in cot_reduce.h
 #define COT_ROW_PREV(v) ((uint32_t)__builtin_amdgcn_update_dpp(0, (int)(v), 0x111, 0xf, 0xf, true))
 #define COT_ROW_NEXT(v) ((uint32_t)__builtin_amdgcn_update_dpp(0, (int)(v), 0x101, 0xf, 0xf, true))
 // v_perm_b32: (lo half of a, lo half of b) / (hi half of a, hi half of b)

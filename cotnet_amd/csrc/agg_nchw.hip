@@ -319,6 +319,7 @@ __global__ __launch_bounds__(256) void agg_bwd_nchw_k3(const T* __restrict__ gou
 
 // (bound_ctrl: a lane without a source -- lane 0 of wave_shr, lane 63 of wave_shl -- reads 0; with it and full masks the
 // "old" operand is dead, so no register has to be zeroed per exchange and the move can fold into its consumer)
+// (lane_prev / lane_next hand a value to the neighbouring lane: exchanges, not reductions, so they are not in cot_reduce.h)
 template <int XCHG> __device__ __forceinline__ float lane_prev(float v) {
     if (XCHG == 0) return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x138, 0xf, 0xf, true));
     return __shfl_up(v, 1);

@@ -13,7 +13,7 @@
 //
 // All kernels are HBM-bound.  Algorithmic traffic per element (e = storage bytes): forward 3e (+e with residual)
 // [stats read, apply read, write], backward 5e (+e) [reduce reads dy,x(,y); apply reads dy,x(,y), writes dx(,dres)].
-#include "cot_common.h"
+#include "cot_reduce.h"
 #include "cot_host.h"
 
 namespace cot {
@@ -66,31 +66,6 @@ struct ChannelWalk {  // i = start, start + step, ... -> c = (i / vpp) % C  (and
         if (c >= C) c -= C;
     }
 };
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-    return v;
-}
-
-// block-wide sum of up to 3 values; result valid in thread 0
-template <int NV> __device__ __forceinline__ void block_sum(float (&v)[NV], float* smem /* >= NV*4 floats */) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-#pragma unroll
-    for (int k = 0; k < NV; ++k) v[k] = wave_sum(v[k]);
-    if (lane == 0)
-#pragma unroll
-        for (int k = 0; k < NV; ++k) smem[k * 16 + wave] = v[k];
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int k = 0; k < NV; ++k) {
-            float s = 0.f;
-            for (int w = 0; w < nw; ++w) s += smem[k * 16 + w];
-            v[k] = s;
-        }
-    }
-}
 
 // ---- forward statistics: grid (C, SPLIT); block handles images [s*nper, (s+1)*nper) of channel c -----------------
 template <typename T, int V>
@@ -607,13 +582,6 @@ static int bn_bwd_launch(const T* dy, const T* x, const T* y, T* dx, T* dres, co
 // (statistics recomputed from x in the backward, not taken from the fp32 saves): one launch each way, a few KB of traffic.
 int g_bn_small_m = 256;  // cot_set_tuning(18, M): per-channel sample count up to which the fp64 path is taken (0 = never); one thread walks a whole channel, so this must stay small
 
-// sum over the 64 lanes in fp64, result in every lane (butterfly with a fixed order: deterministic)
-__device__ __forceinline__ double wave_allsum_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 // one WAVE per channel: lane l takes the samples l, l+64, .. of the channel's N*H*W
 template <typename T, int ACT>
 __global__ __launch_bounds__(64) void bn_small_fwd(const T* __restrict__ x, const T* __restrict__ res, T* __restrict__ y,
@@ -629,14 +597,14 @@ __global__ __launch_bounds__(64) void bn_small_fwd(const T* __restrict__ x, cons
         const int n = e / HW, p = e - n * HW;
         sm += (double)(float)x[((int64_t)n * C + c) * HW + p];
     }
-    const double mu = wave_allsum_d(sm) / M;
+    const double mu = wave_allsum(sm) / M;
     double m2 = 0.0;
     for (int e = lane; e < M; e += 64) {
         const int n = e / HW, p = e - n * HW;
         const double d = (double)(float)x[((int64_t)n * C + c) * HW + p] - mu;
         m2 += d * d;
     }
-    m2 = wave_allsum_d(m2);
+    m2 = wave_allsum(m2);
     const double var = m2 / M, r = 1.0 / sqrt(var + (double)eps);
     if (lane == 0) {
         mean[c] = (float)mu;
@@ -673,7 +641,7 @@ __global__ __launch_bounds__(64) void bn_small_bwd(const T* __restrict__ dy, con
     }
     // mean recomputed in fp64 (so that sum(xhat) == 0 to fp64 accuracy); rstd is the forward's (its own rounding only
     // scales the result by 1 + 6e-8, it does not enter the cancellation)
-    const double mu = wave_allsum_d(sm) / M, r = (double)rstd[c], ga = gamma[c], be = beta[c];
+    const double mu = wave_allsum(sm) / M, r = (double)rstd[c], ga = gamma[c], be = beta[c];
     auto gof = [&](int64_t i, double xh) {
         const double d = (double)(float)dy[i];
         if (ACT == ACT_RELU_Y) return (float)y[i] > 0.f ? d : 0.0;
@@ -693,8 +661,8 @@ __global__ __launch_bounds__(64) void bn_small_bwd(const T* __restrict__ dy, con
         sg += g;
         sgx += g * xh;
     }
-    sg = wave_allsum_d(sg);
-    sgx = wave_allsum_d(sgx);
+    sg = wave_allsum(sg);
+    sgx = wave_allsum(sgx);
     if (lane == 0) {
         dbeta[c] = (float)sg;
         dgamma[c] = (float)sgx;
@@ -753,11 +721,12 @@ template <typename T, int V, bool BWD> struct ChanRounds {  // most rounds (vect
                                  : (sizeof(T) <= 2 ? (V == 8 ? (BWD ? 4 : 8) : (V == 4 ? (BWD ? 8 : 16) : 16)) : (V == 4 ? 8 : 16));
 };
 
-// sums of NV doubles over the workgroup, result in every lane; fixed order (deterministic)
+// sums of NV doubles over the workgroup, result in every lane; fixed order (deterministic).  Not cot_reduce.h's block_allsum: that
+// one is fp32 on the lane-0 tree, this one fp64 on the butterfly (wave_allsum), and only this file sums doubles over a workgroup
 template <int NV> __device__ __forceinline__ void block_allsum_d(double (&v)[NV], double* smem /* NV * 16 */) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
 #pragma unroll
-    for (int k = 0; k < NV; ++k) v[k] = wave_allsum_d(v[k]);
+    for (int k = 0; k < NV; ++k) v[k] = wave_allsum(v[k]);
     __syncthreads();  // the previous use of smem is over
     if (lane == 0)
 #pragma unroll
@@ -1131,11 +1100,7 @@ __global__ __launch_bounds__(64) void bn_tile_stats_finalize(const float* __rest
         s1 += (double)p[0];
         s2 += (double)p[1];
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        s1 += __shfl_xor(s1, o);
-        s2 += __shfl_xor(s2, o);
-    }
+    wave_allsum2(s1, s2);
     if (lane == 0) {
         const double cnt = (double)N * HW, m = s1 / cnt;
         double var = s2 / cnt - m * m;  // (fp64 on sums of bf16-exact squares: no visible cancellation at these counts)

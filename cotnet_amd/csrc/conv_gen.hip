@@ -267,6 +267,7 @@ template <typename T> __global__ __launch_bounds__(256) void convg_wgrad_kernel(
         }
     }
     if (do_bias) {  // the four lanes of a row sit next to each other in the wave
+        // (not cot_reduce.h's seg_allsum<4>: this adds neighbours first, offsets 1 then 2, and the butterfly's 2 then 1 rounds differently)
         bsum += __shfl_xor(bsum, 1);
         bsum += __shfl_xor(bsum, 2);
         if (qq == 0 && mok) a.part[(int64_t)a.splits * PS + (int64_t)split * a.Co + g * a.Og + m] = bsum;

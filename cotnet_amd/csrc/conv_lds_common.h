@@ -230,6 +230,8 @@ __device__ __forceinline__ void tile_epilogue(const f32x4_t (&acc)[CB][MB], cons
                     }
                 }
             }
+            // cot_reduce.h's two-value butterfly over TPR lanes, left open-coded: as a call it is unrolled before it is inlined, which reschedules all 48
+            // conv1x1_lds_fwd2 instances (same arithmetic, one instruction more or fewer each; profiles/reduce_header_isa_diff.log)
 #pragma unroll
             for (int o = TPR >> 1; o > 0; o >>= 1) {
                 s1 += __shfl_xor(s1, o);

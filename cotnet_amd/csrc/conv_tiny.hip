@@ -144,6 +144,7 @@ __global__ __launch_bounds__(256) void tiny_wgrad(const bf16_t* __restrict__ gy,
         }
     }
     if (gb && k0 == 0) {  // the four lane groups hold the four 8-pixel chunks of a 32-pixel step
+        // (not one of cot_reduce.h's sums: lane bits 4 and 5 -- lanes l, l + 16, l + 32, l + 48 -- are no contiguous segment)
         bsum += __shfl_xor(bsum, 16);
         bsum += __shfl_xor(bsum, 32);
         if (g == 0 && m0 + i < M) gb[m0 + i] = (bf16_t)bsum;

@@ -23,6 +23,7 @@
 // and must be ordered by the caller.
 #include <math.h>
 
+#include "cot_reduce.h"
 #include "cot_host.h"
 
 namespace cot {
@@ -41,23 +42,6 @@ struct EvalRow {
 constexpr int EVAL_ROWS_CAP = 4096;  // rows per launch pair (64 KB)
 constexpr int EVAL_REG = 16;         // columns a lane holds: rows of up to 64 * 16 columns are read once
 __device__ EvalRow g_eval_rows[EVAL_ROWS_CAP];
-
-// (file-unique names: the host build of the kernels links every source into one library, where equal inline names would merge)
-template <typename V> __device__ __forceinline__ V ev_wave_sum(V v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);  // every lane ends with the same bits
-    return v;
-}
-__device__ __forceinline__ float ev_wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ __forceinline__ unsigned ev_wave_or(unsigned v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v |= __shfl_xor(v, o);
-    return v;
-}
 
 // the order of torch's descending sort: NaN above everything, NaNs equal among themselves
 __device__ __forceinline__ bool ev_greater(float a, float b) { return a > b || (a != a && b == b); }
@@ -102,8 +86,8 @@ __global__ __launch_bounds__(64) void eval_rows_kernel(const T* __restrict__ log
             if ((long long)j == y) tbits = __builtin_bit_cast(unsigned, x);
         }
     }
-    m = ev_wave_max(m);
-    const float t = __builtin_bit_cast(float, ev_wave_or(tbits));  // one lane holds it, the others 0
+    m = wave_allmax(m);
+    const float t = __builtin_bit_cast(float, wave_allor(tbits));  // one lane holds it, the others 0
     int rank = 0;
     double s = 0.0;
 #pragma unroll 16
@@ -116,8 +100,8 @@ __global__ __launch_bounds__(64) void eval_rows_kernel(const T* __restrict__ log
         }
     }
 #undef EV_AT
-    rank = ev_wave_sum(rank);
-    const double nll = log(ev_wave_sum(s)) - ((double)t - (double)m);  // = logsumexp(row) - t
+    rank = wave_allsum(rank);
+    const double nll = log(wave_allsum(s)) - ((double)t - (double)m);  // = logsumexp(row) - t
     if (lane == 0) {
         g_eval_rows[n].nll = nll;
         g_eval_rows[n].flags = 1 | (rank == 0 ? 2 : 0) | (rank < 5 ? 4 : 0);
@@ -139,7 +123,7 @@ __global__ __launch_bounds__(64) void eval_accumulate_kernel(EvalAcc* acc, int N
         __syncthreads();
         if (lane == 0) {
             const int cnt = N - base < 64 ? N - base : 64;
-            for (int i = 0; i < cnt; ++i) {
+            for (int i = 0; i < cnt; ++i) {  // (not shared with grad_clip_finish_kernel's ordered loop: that one runs under a prefetch)
                 const int f = s_flags[i];
                 if (f & 1) {
                     samples += 1;

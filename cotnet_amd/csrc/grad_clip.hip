@@ -24,12 +24,13 @@
 //     rounds = ceil((n / V) / (PARTS * 256))     a lane's sequential adds, one sum per vector slot (the first add, to 0, is counted)
 //     + log2(V)                                  the slots, pairwise
 //     + 1                                        the tail element (n % V; first lanes of workgroup 0)
-//     + 6                                        the wave's exchange stages
+//     + 6                                        the wave's exchange stages (cot_reduce.h: wave_allsum)
 //     + 3                                        the four waves' sums, added in order by lane 0
 // The finish is fp64 and adds nothing at that scale.
 #include <float.h>
 #include <math.h>
 
+#include "cot_reduce.h"
 #include "cot_host.h"
 
 namespace cot {
@@ -39,13 +40,6 @@ static_assert(sizeof(cot_clip_state) == 32, "the clip block is 8 x 32-bit words"
 constexpr int GC_BLOCK = 256;  // lanes per workgroup (four waves)
 constexpr int GC_AHEAD = 4;    // loads of a lane issued before the first is used
 constexpr int GC_FIN_BLOCK = 256, GC_FIN_CHUNK = 1024;  // the finish: partials staged per round, by how many lanes
-
-// (file-unique names: the host build of the kernels links every source into one library, where equal inline names would merge)
-__device__ __forceinline__ float gc_wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);  // every lane ends with the same bits
-    return v;
-}
 
 template <typename T, int V> __device__ __forceinline__ void gc_add_squares(float (&acc)[V], const Vec<T, V>& g) {
 #pragma unroll
@@ -84,7 +78,7 @@ __global__ __launch_bounds__(GC_BLOCK) void grad_sumsq_kernel(const T* __restric
         const float x = (float)grad[tail0 + threadIdx.x];
         s += x * x;
     }
-    s = gc_wave_sum(s);
+    s = wave_allsum(s);
     if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = s;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -119,7 +113,7 @@ __global__ __launch_bounds__(GC_FIN_BLOCK) void grad_clip_finish_kernel(const fl
         if (lane == 0) {
             const int cnt = nparts - base < GC_FIN_CHUNK ? (int)(nparts - base) : GC_FIN_CHUNK;
 #pragma unroll 16
-            for (int j = 0; j < cnt; ++j) sum += s_part[j];  // ONE chain, ascending index
+            for (int j = 0; j < cnt; ++j) sum += s_part[j];  // ONE chain, ascending index (not shared with eval_accumulate_kernel's: no prefetch there)
         }
         __syncthreads();
     }

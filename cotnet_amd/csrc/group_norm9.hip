@@ -11,47 +11,17 @@
 //             reduces them over the batch into dgamma / dbeta (deterministic).       (torch: 6R + 1W, 4-5 launches)
 // Thread t of a workgroup owns, for each of the 9 channels and each round r < R, the 8 consecutive pixels starting at
 // 8*(r*NT + t): all channel indices are compile-time, so per-channel accumulators stay in registers.
-#include "cot_common.h"
+#include "cot_reduce.h"
 #include "mfma_common.h"
 #include "cot_host.h"
 
 namespace cot {
 
-__device__ __forceinline__ float gn_wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-    return v;
-}
-
-// block-wide sums of NV values, result broadcast to every thread; smem >= NV * 16 floats, blockDim <= 1024
-template <int NV> __device__ __forceinline__ void gn_block_sum_all(float (&v)[NV], float* smem) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
-#pragma unroll
-    for (int k = 0; k < NV; ++k) v[k] = gn_wave_sum(v[k]);
-    __syncthreads();  // previous use of smem is over
-    if (lane == 0)
-#pragma unroll
-        for (int k = 0; k < NV; ++k) smem[k * 16 + wave] = v[k];
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < NV; ++k) {
-        float s = 0.f;
-        for (int w = 0; w < nw; ++w) s += smem[k * 16 + w];
-        v[k] = s;
-    }
-}
-
 // SEG < 64 (round 5): SEG lanes per (image, group), 64 / SEG groups per wave -- small planes leave most of a wave idle otherwise
 // (8 pixels per lane: 7 lanes of 64 at 7 x 7, one wave per group: 5120 single-wave workgroups at B = 80; 11.1 -> 6.9 us forward,
 // 24.3 -> 13.2 us backward there, profiles/r05_gn9_packed_small_planes_ab.log).
-// The sums run over the SEG-lane segment (xor butterfly: every lane of the segment ends with the total).
-template <int NV, int SEG> __device__ __forceinline__ void gn_seg_sum_all(float (&v)[NV]) {
-#pragma unroll
-    for (int k = 0; k < NV; ++k)
-#pragma unroll
-        for (int o = SEG / 2; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o);
-}
-
+// The sums run over the SEG-lane segment (seg_allsum_n: every lane of the segment ends with the total).
+//
 // The group sits in registers PACKED (two bf16 per register; mfma_common.h "pieces"): all loads of a thread are issued
 // back to back and nothing touches them until the last one is on its way.  Rounds whose pieces run over a channel's end
 // (wave-uniform `tail`) are loaded wide all the same -- what follows is the next channel; lanes wholly past the end all
@@ -112,8 +82,8 @@ gn9_fwd_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ gamma, c
         for (int r = 0; r < R; ++r)
 #pragma unroll
             for (int e = 0; e < 8; ++e) s[0] += packed_get(v[cl][r], e);
-    if (SEG < 64) gn_seg_sum_all<1, SEG>(s);
-    else gn_block_sum_all<1>(s, smem);
+    if (SEG < 64) seg_allsum_n<1, SEG>(s);
+    else block_allsum<1>(s, smem);
     const float mean = s[0] * inv;
     float q[1] = {0.f};
 #pragma unroll
@@ -127,8 +97,8 @@ gn9_fwd_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ gamma, c
                 if (!tail[r] || e < left) q[0] += d * d;
             }
     }
-    if (SEG < 64) gn_seg_sum_all<1, SEG>(q);
-    else gn_block_sum_all<1>(q, smem);
+    if (SEG < 64) seg_allsum_n<1, SEG>(q);
+    else block_allsum<1>(q, smem);
     const float rstd = 1.f / sqrtf(q[0] * inv + eps);
     if (t == 0 && live) {
         mean_out[gid] = mean;
@@ -229,8 +199,8 @@ gn9_bwd_kernel(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ x, cons
                 COT_KEEP_PACKED(xv[cl][r][i]);
                 COT_KEEP_PACKED(gv[cl][r][i]);
             }
-    if (SEG < 64) gn_seg_sum_all<18, SEG>(s);
-    else gn_block_sum_all<18>(s, smem);
+    if (SEG < 64) seg_allsum_n<18, SEG>(s);
+    else block_allsum<18>(s, smem);
     float c1 = 0.f, c2 = 0.f;
 #pragma unroll
     for (int cl = 0; cl < 9; ++cl) {
@@ -316,14 +286,14 @@ __global__ __launch_bounds__(256) void gn9f_fwd_kernel(const float* __restrict__
     const float* xb = x + (int64_t)blockIdx.x * n9;
     float s[1] = {0.f};
     for (int i = t; i < n9; i += 256) s[0] += xb[i];
-    gn_block_sum_all<1>(s, smem);
+    block_allsum<1>(s, smem);
     const float mean = s[0] / (float)n9;
     float v[1] = {0.f};
     for (int i = t; i < n9; i += 256) {
         const float d = xb[i] - mean;
         v[0] += d * d;
     }
-    gn_block_sum_all<1>(v, smem);
+    block_allsum<1>(v, smem);
     const float rstd = 1.f / sqrtf(v[0] / (float)n9 + eps);
     if (t == 0) {
         mean_out[blockIdx.x] = mean;
@@ -358,7 +328,7 @@ __global__ __launch_bounds__(256) void gn9f_bwd_kernel(const float* __restrict__
         s[2 * cl] = a;
         s[2 * cl + 1] = b;
     }
-    gn_block_sum_all<18>(s, smem);
+    block_allsum<18>(s, smem);
     float c1 = 0.f, c2 = 0.f;
 #pragma unroll
     for (int cl = 0; cl < 9; ++cl) {
@@ -425,11 +395,7 @@ __global__ __launch_bounds__(64) void gn9_stats_finalize_kernel(const float* __r
         s1 += (double)p[0];
         s2 += (double)p[1];
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        s1 += __shfl_xor(s1, o);
-        s2 += __shfl_xor(s2, o);
-    }
+    wave_allsum2(s1, s2);
     if (lane == 0) {
         const double cnt = 9.0 * (double)HW, m = s1 / cnt;
         double var = s2 / cnt - m * m;

@@ -205,6 +205,8 @@ __global__ __launch_bounds__(LR_THREADS) void lr_bwd_rel(const T* __restrict__ g
             }
 #pragma unroll
             for (int t = 0; t < 9; ++t) {
+                // cot_reduce.h's wave_allsum, left open-coded: as a call it is unrolled before it is inlined, which reschedules every
+                // lr_bwd_rel instance (same arithmetic, 272 assembly lines moved; profiles/reduce_header_isa_diff.log)
                 float s = gp[t];
 #pragma unroll
                 for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m);

@@ -19,6 +19,7 @@
 #include <math.h>
 
 #include "input_norm.h"
+#include "cot_reduce.h"
 #include "cot_host.h"
 
 namespace cot {
@@ -154,18 +155,6 @@ __device__ __forceinline__ RowTarget row_target(const long long* __restrict__ la
     return t;
 }
 
-// (file-unique names: the host build of the kernels links every source into one library, where equal inline names would merge)
-template <typename V> __device__ __forceinline__ V ce_wave_sum(V v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);  // every lane ends with the same bits
-    return v;
-}
-__device__ __forceinline__ float ce_wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
-
 // one wave (= one workgroup) per row.  The probabilities are formed in fp64: the gradient p*sum(t) - t CANCELS wherever a probability
 // comes close to its target (every column holds off = smoothing/K, and some of 80 000 probabilities always land within 1e-4 of it), and
 // there an fp32 p -- 3e-7 relative from the rounding of log(sum) alone -- is tens of bf16 ulps off in the difference.  So the shifted
@@ -182,13 +171,13 @@ __global__ __launch_bounds__(64) void soft_ce_forward_kernel(const T* __restrict
     const RowTarget t = row_target(labels, pb, n, N, on, off);
     float m = -INFINITY;
     for (int j = lane; j < K; j += 64) m = fmaxf(m, (float)row[j]);
-    m = ce_wave_max(m);
+    m = wave_allmax(m);
     double s = 0.0;
     for (int j = lane; j < K; j += 64) s += exp((double)(float)row[j] - (double)m);
-    const double l = log(ce_wave_sum(s));
+    const double l = log(wave_allsum(s));
     double acc = 0.0;
     for (int j = lane; j < K; j += 64) acc += (double)t.at(j) * (((double)(float)row[j] - (double)m) - l);
-    acc = ce_wave_sum(acc);
+    acc = wave_allsum(acc);
     if (lane == 0) {
         const float hi = (float)l, loss = (float)-acc;
         row_loss[n] = loss;
@@ -206,7 +195,7 @@ __global__ __launch_bounds__(64) void row_mean_kernel(const float* __restrict__ 
                                                       float* __restrict__ mean, int N) {
     double s = 0.0;
     for (int n = threadIdx.x; n < N; n += 64) s += (double)row_loss[n] + (double)row_lo[n];
-    s = ce_wave_sum(s);
+    s = wave_allsum(s);
     if (threadIdx.x == 0) *mean = (float)(s / (double)N);
 }
 

@@ -7,16 +7,10 @@
 //   radix_mix_bwd  gy = g*a0, gk = g*a1, ga0[b,c] = sum_hw g*y, ga1 = sum_hw g*k one pass over g,y,k
 // (the tiny se MLP + softmax between gap and mix stay in torch).  One wavefront per (b,c) plane: the per-plane scalars
 // are wave-uniform, plane rows are contiguous, loads are V-wide vectors when H*W allows.
-#include "cot_common.h"
+#include "cot_reduce.h"
 #include "cot_host.h"
 
 namespace cot {
-
-__device__ __forceinline__ float wave_sum_f(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-    return v;
-}
 
 template <typename T, int V>
 __global__ __launch_bounds__(256) void radix_gap_kernel(const T* __restrict__ y, const T* __restrict__ k,
@@ -32,7 +26,7 @@ __global__ __launch_bounds__(256) void radix_gap_kernel(const T* __restrict__ y,
 #pragma unroll
         for (int j = 0; j < V; ++j) acc += (float)a.v[j] + (float)b.v[j];
     }
-    acc = wave_sum_f(acc);
+    acc = wave_sum(acc);
     if (lane == 0) gap[plane] = (T)(acc / (float)HW);
 }
 
@@ -81,8 +75,8 @@ __global__ __launch_bounds__(256) void radix_mix_bwd_kernel(const T* __restrict_
         stv<T, V>(gy + base + i, oy);
         stv<T, V>(gk + base + i, ok);
     }
-    s0 = wave_sum_f(s0);
-    s1 = wave_sum_f(s1);
+    s0 = wave_sum(s0);
+    s1 = wave_sum(s1);
     if (lane == 0) {
         gattn[plane * 2] = (T)s0;
         gattn[plane * 2 + 1] = (T)s1;
@@ -103,18 +97,11 @@ __device__ __forceinline__ int64_t tail_base(int cm, int n, int c, int N, int C,
 }
 
 // SEG < 64 (round 5): SEG lanes per plane, 64 / SEG planes per wave -- 7 x 7 planes as 7 lanes x 7 elements (V = 7, SEG = 8) instead of
-// 49 lanes x one 2-byte element and a wave per plane (40960 waves for 80 x 512 planes).  Sums: xor butterfly over the segment (every lane
-// ends with the total).  No early return in the kernels that shuffle: lanes of planes past the end follow along and store nothing.
+// 49 lanes x one 2-byte element and a wave per plane (40960 waves for 80 x 512 planes).  Sums: seg_sum / seg_allsum over the segment
+// (cot_reduce.h).  No early return in the kernels that shuffle: lanes of planes past the end follow along and store nothing.
 // y*a0 + k*a1 with the contraction spelled out (one rounding of k*a1, one of the sum): the radix mix and its BatchNorm-folded twin
 // must agree bit for bit, and left to the compiler the two kernels contracted differently (263 of 16 M outputs one bf16 ulp apart)
 __device__ __forceinline__ float mix2(float y, float a0, float k, float a1) { return __builtin_fmaf(y, a0, k * a1); }
-
-template <int SEG> __device__ __forceinline__ float seg_sum_f(float v) {
-    if (SEG == 64) return wave_sum_f(v);
-#pragma unroll
-    for (int o = SEG / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 template <typename T, int V, int SEG = 64>
 __global__ __launch_bounds__(256) void radix_gap_t_kernel(const T* __restrict__ y, const T* __restrict__ k,
@@ -141,7 +128,7 @@ __global__ __launch_bounds__(256) void radix_gap_t_kernel(const T* __restrict__ 
             for (int j = 0; j < V; ++j) acc += (float)a.v[j];
         }
     }
-    acc = seg_sum_f<SEG>(acc);
+    acc = seg_sum<SEG>(acc);
     if (lane == 0 && live) gapT[(int64_t)c * N + n] = (T)(acc / (float)HW);
 }
 
@@ -194,8 +181,8 @@ __global__ __launch_bounds__(256) void radix_mix_bwd_reduce_kernel(const T* __re
             s1 += gg * (float)b.v[j];
         }
     }
-    s0 = seg_sum_f<SEG>(s0);
-    s1 = seg_sum_f<SEG>(s1);
+    s0 = seg_sum<SEG>(s0);
+    s1 = seg_sum<SEG>(s1);
     if (lane == 0 && live) {
         const float a0 = (float)attn[plane * 2], a1 = (float)attn[plane * 2 + 1];
         const float gl = a0 * a1 * (s0 - s1);  // softmax backward for a pair: gl0 = a0*(s0 - (a0*s0 + a1*s1))
@@ -252,13 +239,6 @@ struct BnTail {
     const float* mean;
     const float* rstd;
 };
-
-// all-lanes sum over a segment of SEG lanes (xor butterfly; SEG = 64: the whole wave)
-template <int SEG> __device__ __forceinline__ float seg_allsum_f(float v) {
-#pragma unroll
-    for (int o = SEG / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 // Loads run two vectors ahead of the arithmetic (exp + rcp per element: ~80 instructions per 8 elements -- with one vector in flight per
 // lane and tensor the kernels added their VALU time to their memory time: gap_t_bn 24.4 us against gap_t's 11.2 at 56 x 56,
@@ -350,7 +330,7 @@ __global__ __launch_bounds__(256) void radix_gap_t_bn_kernel(const T* __restrict
 #pragma unroll
         for (int j = 0; j < V; ++j) acc += (float)(T)silu_fwd((float)x.v[j] * sc + sh) + (float)b.v[j];
     }
-    acc = seg_sum_f<SEG>(acc);
+    acc = seg_sum<SEG>(acc);
     if (lane == 0 && live) gapT[(int64_t)c * N + n] = (T)(acc / (float)HW);
 }
 
@@ -421,12 +401,12 @@ __global__ __launch_bounds__(256) void radix_mix_bwd_reduce_bn_kernel(const T* _
             t3 += sp * xh;
         }
     }
-    s0 = seg_sum_f<SEG>(s0);
-    s1 = seg_sum_f<SEG>(s1);
-    t0 = seg_sum_f<SEG>(t0);
-    t1 = seg_sum_f<SEG>(t1);
-    t2 = seg_sum_f<SEG>(t2);
-    t3 = seg_sum_f<SEG>(t3);
+    s0 = seg_sum<SEG>(s0);
+    s1 = seg_sum<SEG>(s1);
+    t0 = seg_sum<SEG>(t0);
+    t1 = seg_sum<SEG>(t1);
+    t2 = seg_sum<SEG>(t2);
+    t3 = seg_sum<SEG>(t3);
     if (lane == 0 && live) {
         const float a0 = (float)attn[plane * 2], a1 = (float)attn[plane * 2 + 1];
         const float gl = a0 * a1 * (s0 - s1);
@@ -468,8 +448,8 @@ __global__ __launch_bounds__(256) void radix_mix_bwd_apply_bn_kernel(const T* __
         sb += t.v[0] + qadd * t.v[1];
         sgm += t.v[2] + qadd * t.v[3];
     }
-    sb = seg_allsum_f<SEG>(sb);
-    sgm = seg_allsum_f<SEG>(sgm);
+    sb = seg_allsum<SEG>(sb);
+    sgm = seg_allsum<SEG>(sgm);
     if (n == 0 && lane == 0 && live) {
         dbeta[c] = sb;
         dgamma[c] = sgm;
@@ -519,7 +499,7 @@ __global__ __launch_bounds__(256) void se_gap_kernel(const T* __restrict__ x, T*
 #pragma unroll
         for (int j = 0; j < V; ++j) acc += (float)a.v[j];
     }
-    acc = wave_sum_f(acc);
+    acc = wave_sum(acc);
     if (lane == 0) gap[plane] = (T)(acc / (float)HW);
 }
 
@@ -562,7 +542,7 @@ __global__ __launch_bounds__(256) void se_gate_bwd_kernel(const T* __restrict__ 
         }
         stv<T, V>(gx + base + i, o);
     }
-    s = wave_sum_f(s);
+    s = wave_sum(s);
     if (lane == 0) glogit[plane] = (T)(s * a * (1.f - a));
 }
 

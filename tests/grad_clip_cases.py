@@ -35,7 +35,7 @@ def vec(gdt):
 def chain_length(n, V, parts):
     """the longest chain of fp32 additions a square passes through (grad_clip.hip, "The chain")"""
     rounds = -(-(n // V) // (parts * BLOCK))  # a lane's sequential adds, one sum per vector slot
-    return rounds + int(math.log2(V)) + 1 + 6 + 3  # + the slots pairwise, the tail element, the wave's stages, the four waves
+    return rounds + int(math.log2(V)) + 1 + 6 + 3  # + the slots pairwise, the tail element, the wave's stages (cot_reduce.h: wave_allsum), the four waves
 
 
 def norm_bound(n, V, parts):
