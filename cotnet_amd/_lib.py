@@ -124,6 +124,8 @@ SYMBOLS = {
     "cot_grad_clip_finish": (_I, [_P, ctypes.c_int64, ctypes.c_float, _P, _P]),
     "cot_sgd_step_clip": (_I, [_P, _P, _P, _P, ctypes.c_int64, ctypes.c_float, _P, _P, ctypes.c_float, ctypes.c_float, ctypes.c_float,
                                _I, _I, _I, _P]),
+    "cot_agc_max_groups": (_I, []),
+    "cot_agc_clip": (_I, [_P, _P, _P, ctypes.c_int64, ctypes.c_int64, ctypes.c_float, ctypes.c_float, _P, _I, _P]),
     "cot_conv1x1_workspace": (ctypes.c_int64, [_I, _I, _I, _I, _I]),
     "cot_conv1x1_forward": (_I, [_P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "cot_conv1x1_backward_data": (_I, [_P, _P, _P, _P, _I, _I, _P, _I, _I, _I, _I, _I, _P]),
@@ -191,7 +193,7 @@ SYMBOLS = {
 NOT_STATUS = frozenset((
     "cot_abi_version", "cot_agg_out_size", "cot_xchg_mode", "cot_launch_log", "cot_bn_act_workspace", "cot_profile_end",
     "cot_gn9_fused_covers", "cot_conv1x1_backward_data_relu_res_covers", "cot_conv1x1_lds_covers", "cot_bn_act_lay_covers",
-    "cot_conv1x1_stats_covers", "cot_grad_norm_parts"))
+    "cot_conv1x1_stats_covers", "cot_grad_norm_parts", "cot_agc_max_groups"))
 
 
 def build(verbose=False):

@@ -1,5 +1,6 @@
 // cot_abi.hip -- extern "C" entry points of libcotnet_hip.so (declared in include/cotnet_amd.h):
 // argument validation, dtype/layout dispatch, error strings.  No torch types anywhere.
+#include <float.h>
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -363,6 +364,27 @@ int cot_grad_clip_finish(const void* partials, int64_t nparts, float max_norm, v
     if ((uintptr_t)partials % 4 != 0) return set_error(COT_ERR_INVALID_ARG, "partials %p is not 4-byte aligned", partials);
     if ((uintptr_t)state % 4 != 0) return set_error(COT_ERR_INVALID_ARG, "clip_state %p is not 4-byte aligned", state);
     return grad_clip_finish((const float*)partials, nparts, max_norm, state, (hipStream_t)stream);
+}
+
+int cot_agc_max_groups(void) { return COT_AGC_MAX_GROUPS; }
+
+int cot_agc_clip(void* grad, const void* weight, const void* units, int64_t nunits, int64_t n, float clip_factor, float eps, void* coef,
+                 int grad_dtype, void* stream) {
+    if (!grad || !weight) return set_error(COT_ERR_INVALID_ARG, "NULL device pointer");
+    if (!units) return set_error(COT_ERR_INVALID_ARG, "NULL units (the device table of (start, len) pairs)");
+    if (!coef) return set_error(COT_ERR_INVALID_ARG, "NULL coef (the float per unit the launch writes)");
+    if (nunits <= 0) return set_error(COT_ERR_INVALID_ARG, "non-positive unit count %lld", (long long)nunits);
+    if (n <= 0) return set_error(COT_ERR_INVALID_ARG, "non-positive element count %lld", (long long)n);
+    int rc = check_align16({grad, weight});
+    if (rc) return rc;
+    if ((uintptr_t)units % 8 != 0) return set_error(COT_ERR_INVALID_ARG, "units %p is not 8-byte aligned", units);
+    if ((uintptr_t)coef % 4 != 0) return set_error(COT_ERR_INVALID_ARG, "coef %p is not 4-byte aligned", coef);
+    if (!(clip_factor > 0.f) || !(clip_factor <= FLT_MAX))
+        return set_error(COT_ERR_INVALID_ARG, "clip_factor %g is not a finite positive number", (double)clip_factor);
+    if (!(eps > 0.f) || !(eps <= FLT_MAX)) return set_error(COT_ERR_INVALID_ARG, "eps %g is not a finite positive number", (double)eps);
+    if (grad_dtype != COT_F32 && grad_dtype != COT_BF16)
+        return set_error(COT_ERR_UNSUPPORTED, "cot_agc_clip: gradient dtype %d (float32 / bfloat16)", grad_dtype);
+    return agc_clip(grad, (const float*)weight, (const int64_t*)units, nunits, clip_factor, eps, (float*)coef, grad_dtype, (hipStream_t)stream);
 }
 
 int cot_sgd_step_clip(void* param, void* master, void* momentum_buf, const void* grad, int64_t n, float lr, const void* lr_dev,

@@ -61,6 +61,10 @@ int sgd_flat_clip(void* param, void* master, void* mom, const void* grad, int64_
 int grad_sumsq(const void* grad, int64_t n, int grad_dtype, float* partials, hipStream_t s);
 int grad_clip_finish(const float* partials, int64_t nparts, float max_norm, void* state, hipStream_t s);
 
+// ---- agc.hip: adaptive gradient clipping, one wave per unit of a flat bucket (arguments validated by cot_agc_clip)
+int agc_clip(void* grad, const float* weight, const int64_t* units, int64_t nunits, float clip_factor, float eps, float* coef, int grad_dtype,
+             hipStream_t s);
+
 // ---- bn_act.hip: BatchNorm (+ activation, residual); `mask`: ReLU sign mask or NULL; -2 / -3 = geometry not covered / kernel takes no mask
 extern int g_bn_fold, g_bn_grid_cap, g_bn_split_target, g_bn_small_m, g_bn_chan, g_bn_chan7, g_bn_chan_rr;
 int64_t bn_relu_mask_bytes(int N, int C, int HW, int esize);

@@ -12,12 +12,14 @@ On MI355X the step is bound by HBM passes and launch count, so this module
   * updates each bucket with ONE hand-written HIP kernel (`cot_sgd_step`, csrc/optim.hip; `cot_sgd_step_lr` with
     device_lr=True: the rate read from device memory, so that a step replayed from a HIP graph follows a schedule;
     `cot_sgd_step_clip` with clip_grad / skip_nonfinite: behind the gradients' global norm, formed on the device by
-    `cot_grad_sumsq` + `cot_grad_clip_finish`, csrc/grad_clip.hip -- the reference's `dispatch_clip_grad`, train.py:269-274).
+    `cot_grad_sumsq` + `cot_grad_clip_finish`, csrc/grad_clip.hip -- the reference's `dispatch_clip_grad`, train.py:269-274; with
+    agc, one `cot_agc_clip` per bucket in front of it, csrc/agc.hip -- the same call's mode 'agc').
 
 Arithmetic = torch.optim.SGD (dampening 0) evaluated in fp32 on the master weights; checked against it in
 tests/test_flat_sgd_gpu.py.
 """
 import contextlib
+import math
 
 import torch
 from torch import nn
@@ -41,10 +43,33 @@ def _decay_group(name, p):
     return "no_decay" if (p.ndim <= 1 or name.endswith(".bias")) else "decay"
 
 
+def _agc_unit_table(params, offs, n):
+    """int64 [units, 2] = (start, len) in elements of a bucket whose parameter slots begin at `offs` (a CPU tensor): the reference's
+    unitwise_norm (utils/clip_grad.py:3-9) -- a parameter with ndim <= 1 is one unit, any other is shape[0] units of numel / shape[0]
+    consecutive elements.  The padding between the slots belongs to no unit.  Checked: len >= 1, ascending, disjoint, inside [0, n) --
+    `cot_agc_clip` trusts the table's contents."""
+    rows = []
+    for p, off in zip(params, offs):
+        if p.numel() == 0:
+            continue
+        if p.ndim <= 1:
+            rows.append(torch.tensor([[off, p.numel()]], dtype=torch.int64))
+        else:
+            per = p.numel() // p.shape[0]
+            start = off + per * torch.arange(p.shape[0], dtype=torch.int64)
+            rows.append(torch.stack([start, torch.full_like(start, per)], dim=1))
+    table = torch.cat(rows) if rows else torch.zeros((0, 2), dtype=torch.int64)
+    start, length = table[:, 0], table[:, 1]
+    ok = bool((length >= 1).all()) and bool((start >= 0).all()) and bool((start + length <= n).all())
+    if not (ok and bool((start[1:] >= (start + length)[:-1]).all())):
+        raise ValueError("FlatSGD(agc=...): the bucket's parameter slots do not give ascending, disjoint units inside the bucket")
+    return table.contiguous()
+
+
 class FlatSGD:
     def __init__(self, model, lr, momentum=0.9, weight_decay=0.0, nesterov=True, bucket_mb=10.0, process_group=None,
                  broadcast_params=True, ema_decay=None, force_collectives=False, grad_dtype=None, device_lr=False, clip_grad=None,
-                 clip_mode="norm", skip_nonfinite=False):
+                 clip_mode="norm", skip_nonfinite=False, agc=None, agc_eps=1e-3):
         """bucket_mb: size of the flat gradient buckets.  10 MiB cuts CoTNet-50's 44 MB of bf16 weight gradients into five
         buckets in the order backward produces them (classifier and stage 4 first, the stem last), so four all-reduces are
         already on the communication stream when backward ends and only the last, small one is exposed; round 2's 48 MiB
@@ -70,7 +95,8 @@ class FlatSGD:
         optimizer.step() (train.py:269-274, `dispatch_clip_grad(..., mode='norm')` = torch.nn.utils.clip_grad_norm_); None or <= 0: no
         clipping (the reference's convention, train.py:270).  The norm runs over EVERY bucket, decay and no-decay alike, on the
         averaged gradients (after the all-reduce: the same coefficient on every rank).
-        clip_mode: only "norm"; the reference's 'value' and 'agc' (utils/clip_grad.py:36-39) are not built.
+        clip_mode: only "norm".  Of the reference's other two modes (utils/clip_grad.py:36-39), 'agc' is the keyword `agc` below and
+        'value' is not built.
         skip_nonfinite: a step whose gradients hold an inf or a NaN (or whose sum of squares overflows) writes no parameter, master
         or momentum; the EMA still moves, as the reference's does behind a step its scaler skipped (train.py:276-277).
         With either, step() issues `cot_grad_sumsq` per bucket, one `cot_grad_clip_finish` and `cot_sgd_step_clip` per bucket
@@ -79,10 +105,35 @@ class FlatSGD:
         capture serves clipped, unclipped and skipped steps alike.  A non-finite step is ALWAYS skipped when clip_grad is set
         (torch's clip_grad_norm_ multiplies every gradient by the NaN coefficient, and the step then poisons every weight);
         skip_nonfinite=True alone asks for the guard with the coefficient 1.  `clip_stats()` reads the block.  With neither,
-        nothing is allocated and the launches are the ones of the plain optimizer."""
+        nothing is allocated and the launches are the ones of the plain optimizer.
+        agc: adaptive gradient clipping with this clip factor (the reference's `dispatch_clip_grad(..., mode='agc')` =
+        adaptive_clip_grad, utils/clip_grad.py:3-24, whose default factor is 0.01); None or <= 0: off -- nothing is allocated and the
+        launches are the ones of before.  Every output unit of every parameter (the reference's unitwise_norm: a parameter with
+        ndim <= 1 is ONE unit, any other is shape[0] rows) is clipped against the L2 norm of its own fp32 weights, the master where
+        the bucket has one: coef = gn < max(wn, agc_eps) * agc ? 1 : max(wn, agc_eps) * agc / max(gn, 1e-6), and a unit with coef < 1
+        is scaled IN PLACE in the bucket.  step() issues one `cot_agc_clip` per bucket (csrc/agc.hip) on the averaged gradients, after
+        the all-reduce (the same coefficients on every rank) and in front of everything else, so that the guard of skip_nonfinite
+        sees the gradients the step will consume.  The unit tables (int64 (start, len) pairs from the buckets' slots, checked here
+        on the host to be ascending, disjoint and in range, uploaded once) and the coefficient tensors (one float per unit) are
+        allocated here and keep their addresses; the factor and agc_eps travel by value, so one HIP-graph capture serves every step.
+        A unit whose weight or gradient norm is not finite is left as it is and marked coef = NaN (the reference would write NaN
+        into it); with skip_nonfinite=True the guard then skips the step.  The reference's zero-initialised `bn3.weight`
+        (cotnet.py:225-226) is a 1-D unit with wn = 0: it is clipped against agc_eps * agc, which is the reference's behaviour and
+        is kept.  Not together with clip_grad: the reference runs one mode per step.  `agc_stats()` and `agc_coefficients()` read
+        the last step's coefficients.
+        agc_eps: the floor of the weight norm (the reference's eps = 1e-3)."""
         if clip_mode != "norm":
-            raise ValueError(f"FlatSGD(clip_mode={clip_mode!r}): only 'norm' (clipping by the global L2 norm) is built; the reference's "
-                             "other modes 'value' and 'agc' are not")
+            raise ValueError(f"FlatSGD(clip_mode={clip_mode!r}): only 'norm' (clipping by the global L2 norm) is a value of clip_mode; "
+                             "the reference's other modes 'value' and 'agc' are not values of clip_mode: adaptive clipping is "
+                             "FlatSGD(agc=...), and clipping by value is not built")
+        self.agc = float(agc) if agc is not None and agc > 0 else None
+        self.agc_eps = float(agc_eps)
+        if self.agc is not None:
+            if clip_grad is not None and clip_grad > 0:
+                raise ValueError(f"FlatSGD(agc={agc!r}, clip_grad={clip_grad!r}): one clipping mode per step, as in the reference's "
+                                 "dispatch_clip_grad -- give agc or clip_grad, not both")
+            if not (math.isfinite(self.agc) and math.isfinite(self.agc_eps) and self.agc_eps > 0):
+                raise ValueError(f"FlatSGD(agc={agc!r}, agc_eps={agc_eps!r}): both must be finite and positive")
         self.lr, self.momentum, self.weight_decay, self.nesterov = float(lr), float(momentum), float(weight_decay), nesterov
         self.ema_decay = None if ema_decay is None else float(ema_decay)
         self._captured_lr = None  # the rate a HIP-graph capture of step() baked into its cot_sgd_step launches (set_lr)
@@ -111,6 +162,13 @@ class FlatSGD:
             self.clip_state = torch.zeros(8, dtype=torch.int32, device=dev)
             self._clip_parts = torch.zeros(max(len(self.reducer.buckets), 1) * _lib.lib().cot_grad_norm_parts(), dtype=torch.float32,
                                            device=dev)
+        self._agc_units = self._agc_coef = None
+        if self.agc is not None:
+            self._agc_units, self._agc_coef = [], []
+            for b in self.reducer.buckets:
+                table = _agc_unit_table(b.params, b.offs, b.pflat.numel())
+                self._agc_units.append(table.to(b.pflat.device))
+                self._agc_coef.append(torch.zeros(table.shape[0], dtype=torch.float32, device=b.pflat.device))
         if self.ema_decay is not None:
             self._buf_src = [bf for bf in model.buffers() if bf.is_floating_point()]
             self._buf_ema = [bf.detach().float().clone() for bf in self._buf_src]
@@ -134,6 +192,15 @@ class FlatSGD:
             sgd, rate = L.cot_sgd_step, (self.lr,)
             if _lib.capturing():  # cot_sgd_step takes the rate by value: every replay of this capture steps with it (set_lr)
                 self._captured_lr = self.lr
+        if self.agc is not None:
+            # unit-wise clipping of the AVERAGED gradients, in place in the buckets; what follows (guard, SGD) reads the clipped ones
+            for b, st, units, coef in zip(self.reducer.buckets, self.state, self._agc_units, self._agc_coef):
+                if units.shape[0] == 0:
+                    continue
+                g = self.reducer.reduced(b)
+                weight = st["master"] if st["master"] is not None else b.pflat
+                L.cot_agc_clip(g.data_ptr(), weight.data_ptr(), units.data_ptr(), units.shape[0], g.numel(), self.agc, self.agc_eps,
+                               coef.data_ptr(), _lib.dtype_code(g.dtype), stream)
         if self.clip_state is not None and self.reducer.buckets:
             # the norm of the AVERAGED gradients over every bucket -> coefficient and skip flag in self.clip_state, which the SGD
             # kernels below read when they run
@@ -178,6 +245,37 @@ class FlatSGD:
         scale, total_norm = w[:2].view(torch.float32).tolist()
         skip, steps, clipped, skipped = w[2:6].tolist()
         return dict(total_norm=total_norm, scale=scale, skip=skip, steps=steps, clipped=clipped, skipped=skipped)
+
+    def agc_stats(self):
+        """ONE host read of the coefficient tensors: dict(units, clipped, nonfinite, min_coef) of the last step -- how many units
+        there are, how many were scaled (coef < 1), how many were left alone because a norm was not finite (coef = NaN), and the
+        smallest coefficient (1.0 when nothing clipped).  Like clip_stats() it synchronises with the device and is refused while a HIP
+        graph is being captured."""
+        if self._agc_coef is None:
+            raise RuntimeError("FlatSGD.agc_stats(): built without agc")
+        if _lib.capturing():
+            raise RuntimeError("FlatSGD.agc_stats() inside a HIP-graph capture: the launches that fill the coefficients are only "
+                               "recorded, and a host read cannot be -- read them between replays")
+        c = torch.cat(self._agc_coef).cpu() if self._agc_coef else torch.zeros(0)
+        bad = torch.isnan(c)
+        fin = c[~bad]
+        return dict(units=c.numel(), clipped=int((fin < 1).sum()), nonfinite=int(bad.sum()),
+                    min_coef=float(fin.min()) if fin.numel() else 1.0)
+
+    def agc_coefficients(self):
+        """{parameter: view of its coefficients in the bucket's tensor}, of shape [shape[0]], or [1] for a parameter with ndim <= 1:
+        what the last step's `cot_agc_clip` launches left (1 = not clipped, NaN = a norm was not finite).  The views stay valid:
+        the tensors are never reallocated."""
+        if self._agc_coef is None:
+            raise RuntimeError("FlatSGD.agc_coefficients(): built without agc")
+        out = {}
+        for b, coef in zip(self.reducer.buckets, self._agc_coef):
+            at = 0
+            for p in b.params:
+                k = 0 if p.numel() == 0 else (1 if p.ndim <= 1 else p.shape[0])
+                out[p] = coef[at:at + k]
+                at += k
+        return out
 
     def ema_state_dict(self):
         """the averaged weights under the model's own state_dict keys (fp32; integer buffers are copied as they are) --

@@ -539,6 +539,47 @@ int cot_sgd_step_clip(void* param, void* master, void* momentum_buf, const void*
                       const void* clip_state, float momentum, float weight_decay, float grad_scale, int nesterov, int param_dtype,
                       int grad_dtype, void* stream);
 
+/* ---- adaptive gradient clipping (AGC, the NFNet rule) over a flat bucket, on the device (reference: dispatch_clip_grad(..., mode='agc')
+ * -> adaptive_clip_grad, utils/clip_grad.py:3-24: every output unit of every parameter is clipped against the norm of its own weights).
+ *
+ * grad    one bucket's reduced gradients, n elements, COT_F32 or COT_BF16, 16-byte aligned; clipped IN PLACE
+ * weight  the same bucket's fp32 weights, n floats, 16-byte aligned: the master copy where the bucket has one, else the fp32
+ *         parameters themselves (the reference clips against fp32 parameters, and the master is that parameter; a bf16 working copy is
+ *         never read)
+ * units   device memory, int64[nunits][2] = (start, len) in elements: ascending, disjoint, len >= 1, start + len <= n.  The
+ *         reference's unitwise_norm: a parameter with ndim <= 1 is ONE unit, any other is shape[0] units of numel / shape[0]
+ *         consecutive elements.  What lies between the units (the padding between parameter slots) is never read or written.  The
+ *         table's CONTENTS are trusted: the caller validates them once on the host (8-byte aligned)
+ * coef    float[nunits] (4-byte aligned); every entry is written on every call
+ *
+ * Per unit, all in fp32 (csrc/agc.hip states the order of the additions, a function of (start, len, dtype) alone, and the longest
+ * chain; no atomics, equal data give equal bits on every run, eager or replayed):
+ *     wn = sqrtf(sum w^2)    gn = sqrtf(sum g^2)
+ *     max_norm = fmaxf(wn, eps) * clip_factor
+ *     coef = gn < max_norm ? 1 : max_norm / fmaxf(gn, 1e-6f)
+ *     coef < 1:  g[i] = (T)((float)g[i] * coef) over the unit;    coef == 1: the unit is NOT written
+ * DEPARTURE from the reference: a unit whose wn or gn is not finite (an inf, a NaN, or squares that overflow fp32) gets coef = NaN as
+ * a marker and its gradient is left as it is -- the reference would multiply it by NaN or 0 * inf.  The non-finite guard
+ * (cot_grad_sumsq / cot_grad_clip_finish) then sees the untouched value and skips the step.
+ *
+ * One wave per unit, four units per workgroup: the grid is min(ceil(nunits / 4), COT_AGC_MAX_GROUPS) workgroups of 256 lanes, and wave
+ * w of the grid takes units w, w + W, ...  clip_factor and eps travel by value (constants of a run): nothing about a batch is a kernel
+ * argument, so one HIP-graph capture serves every step.
+ * NULL grad / weight / units / coef, grad or weight not 16-byte, units not 8-byte or coef not 4-byte aligned, nunits < 1, n < 1,
+ * clip_factor or eps not finite or not > 0: COT_ERR_INVALID_ARG; any other gradient dtype: COT_ERR_UNSUPPORTED -- reported through
+ * cot_last_error() before any device work. */
+/* The cap of the grid.  Measured on the MI355X on CoTNet-50's seven buckets (47227 units, at most ~2600 workgroups wanted per bucket),
+ * no unit clipping, the seven launches replayed from one HIP graph, operands rotating through > 512 MB (profiles/agc_bench.log;
+ * bf16 / fp32 gradients):    1024: 76.0 / 82.5 us    2048: 76.9 / 76.3    4096: 75.8 / 73.5
+ * The sequence is bound by each wave's chain of dependent round trips (table entry, loads, exchange stages), not by bytes, and the cap
+ * hardly moves it: 1024 costs 6 - 9 us with fp32 gradients; 2048 and 4096 differ by less than a form's place in the alternation does
+ * (~3 us: with the two swapped in the order, an earlier run of the same script measured 73.2 for 2048 and 76.2 for 4096 in fp32).
+ * 2048 = eight workgroups per compute unit. */
+#define COT_AGC_MAX_GROUPS 2048
+int cot_agc_max_groups(void); /* = COT_AGC_MAX_GROUPS; makes no HIP call */
+int cot_agc_clip(void* grad, const void* weight, const void* units, int64_t nunits, int64_t n, float clip_factor, float eps, void* coef,
+                 int grad_dtype, void* stream);
+
 /* ---- exponential moving average of the weights over a flat buffer (replaces the per-tensor
  * `ema = decay*ema + (1-decay)*model` of ModelEmaV2._update, utils/model_ema.py:45-53):  ema fp32 [n], src the fp32
  * master copy / fp32 parameters (COT_F32) or bf16 parameters (COT_BF16). */
