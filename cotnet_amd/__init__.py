@@ -10,6 +10,7 @@ Public surface mirrors the reference (JDAI-CV/CoTNet):
     loss.cross_entropy                   -> cotnet_amd.loss                 (soft_target_cross_entropy, LabelSmoothingCrossEntropy)
     evaler.evaler / utils.meters         -> cotnet_amd.evaler               (Evaler, DeviceTestMeter, accuracy: scored on the device)
     models.factory / models.registry     -> cotnet_amd.registry             (create_model, register_model)
+    utils.checkpoint_saver / models.helpers.resume_checkpoint -> cotnet_amd.checkpoint (CheckpointSaver, resume_checkpoint)
 Device code lives in cotnet_amd/csrc (HIP, gfx950) behind the C ABI of include/cotnet_amd.h.
 """
 from . import _lib  # noqa: F401
@@ -28,5 +29,6 @@ from .mixup import DeviceMixup  # noqa: F401
 from .evaler import DeviceTestMeter, Evaler, accuracy  # noqa: F401
 from .registry import create_model, list_models, load_checkpoint, register_model  # noqa: F401
 from .resnet import ResNet  # noqa: F401
+from .checkpoint import CheckpointSaver, resume_checkpoint  # noqa: F401
 
 __version__ = "0.1.0"

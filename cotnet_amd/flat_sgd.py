@@ -376,3 +376,181 @@ class FlatSGD:
             for p, off in zip(b.params, b.offs):
                 out[p] = src[off:off + p.numel()].view_as(p)
         return out
+
+    # ---- the whole training state, out and in (the reference: CheckpointSaver._save, utils/checkpoint_saver.py:103-120, and
+    # resume_checkpoint, models/helpers.py:51-88).  Everything below acts IN PLACE on the allocations made in __init__: no address
+    # changes, so a HIP graph captured before a load replays the loaded state.  Everything is refused while capturing.
+
+    STATE_FORMAT = 1
+
+    def _not_while_capturing(self, what):
+        if _lib.capturing():
+            raise RuntimeError(f"FlatSGD.{what} inside a HIP-graph capture: its copies and launches would be recorded and run again at "
+                               "every replay, and a host read cannot be recorded -- save and load between replays (the state keeps its "
+                               "addresses: a captured step replays what was loaded); nothing was changed")
+
+    def _groups(self):
+        """the reference's two parameter groups (optim/optim_factory.py:19-31): [[(name, parameter)] of no_decay, ... of decay], each in
+        named_parameters() order"""
+        in_bucket = {p: b.key for b in self.reducer.buckets for p in b.params}
+        groups = {"no_decay": [], "decay": []}
+        for name, p in self.model.named_parameters():
+            if p in in_bucket:
+                groups[in_bucket[p]].append((name, p))
+        return [groups["no_decay"], groups["decay"]]
+
+    def _slots(self, array):
+        """{parameter: view of its slot in the buckets' `array`} ('weights': the master, or the fp32 parameters where there is none)"""
+        out = {}
+        for b, st in zip(self.reducer.buckets, self.state):
+            flat = (st["master"] if st["master"] is not None else b.pflat) if array == "weights" else st[array]
+            for p, off in zip(b.params, b.offs):
+                out[p] = flat[off:off + p.numel()].view_as(p)
+        return out
+
+    def model_state_dict(self):
+        """the model's state_dict() keys with every parameter that has a master given as that fp32 master, every other parameter and
+        buffer as it is (clones): what the reference stores under `state_dict` (utils/checkpoint_saver.py:107), at the precision the
+        optimizer steps at.  `model.state_dict()` would hold the bf16 roundings."""
+        self._not_while_capturing("model_state_dict()")
+        weights = self._slots("weights")
+        params = dict(self.model.named_parameters())
+        out = {}
+        for k, v in self.model.state_dict().items():
+            p = params.get(k)
+            out[k] = (weights[p] if p is not None and p in weights else v).detach().clone()
+        return out
+
+    @staticmethod
+    def _strip(sd):
+        return {(k[7:] if k.startswith("module.") else k): v for k, v in sd.items()}
+
+    def _check_keys(self, sd, strict, shapes):
+        """missing / unexpected keys as nn.Module.load_state_dict reports them, and the shapes of those present"""
+        keys = list(self.model.state_dict().keys())
+        missing = [k for k in keys if k not in sd]
+        unexpected = [k for k in sd if k not in shapes]
+        errors = [f"size mismatch for {k}: copying a param with shape {tuple(sd[k].shape)} from checkpoint, the shape in current model is "
+                  f"{tuple(shapes[k])}." for k in keys if k in sd and tuple(sd[k].shape) != tuple(shapes[k])]
+        if strict:
+            if unexpected:
+                errors.insert(0, "Unexpected key(s) in state_dict: {}. ".format(", ".join(f'"{k}"' for k in unexpected)))
+            if missing:
+                errors.insert(0, "Missing key(s) in state_dict: {}. ".format(", ".join(f'"{k}"' for k in missing)))
+        if errors:
+            raise RuntimeError("Error(s) in loading state_dict for {}:\n\t{}".format(type(self.model).__name__, "\n\t".join(errors)))
+        return nn.modules.module._IncompatibleKeys(missing, unexpected)
+
+    def load_model_state_dict(self, sd, strict=True):
+        """the inverse of model_state_dict(): the masters receive the fp32 values, each working copy its master rounded to the bucket's
+        dtype (the invariant ema_weights() relies on), fp32 buckets and every other parameter and buffer the values themselves; the
+        caches keyed on the parameters move on.  A `module.` prefix is stripped.  `model.load_state_dict` alone would write the working
+        copies only, and the next step() would put the stale masters back over them.  strict: missing and unexpected keys raise, as
+        nn.Module.load_state_dict's do, before anything is written."""
+        self._not_while_capturing("load_model_state_dict()")
+        sd = self._strip(sd)
+        live = self.model.state_dict()
+        keys = self._check_keys(sd, strict, {k: v.shape for k, v in live.items()})
+        weights = self._slots("weights")
+        params = dict(self.model.named_parameters())
+        with torch.no_grad():
+            for k, v in live.items():
+                if k in sd:
+                    p = params.get(k)
+                    (weights[p] if p is not None and p in weights else v).copy_(sd[k])
+            for b, st in zip(self.reducer.buckets, self.state):
+                if st["master"] is not None:
+                    b.pflat.copy_(st["master"])
+        if self.reducer.buckets:
+            from . import cot_layer_fused
+            cot_layer_fused.after_optimizer_step(self.reducer.buckets[0].pflat.device)
+        return keys
+
+    def _clip_words(self):
+        return self.clip_state.cpu().tolist() if self.clip_state is not None else None
+
+    def state_dict(self):
+        """torch.optim.SGD's own layout over the reference's groups (optim/optim_factory.py:19-31, :54-56): param_groups =
+        [no_decay, decay], each listing its parameters in named_parameters() order with indices running on across the groups,
+        state[idx] = {'momentum_buffer': fp32 tensor of the parameter's shape}, the hyper-parameters (lr, momentum, dampening 0,
+        weight_decay, nesterov) in the groups -- torch.optim.SGD over the same groups of an fp32 twin loads its 'state' and
+        'param_groups'.  One more top-level key, 'cotnet_amd', holds what that layout cannot: format, device_lr (whether the rate lives
+        on the device) and clip_state (the eight words of the clip block: last coefficient and norm, the counters; None without one)."""
+        self._not_while_capturing("state_dict()")
+        momentum, groups, state, at = self._slots("mom"), [], {}, 0
+        for members, wd in zip(self._groups(), (0.0, self.weight_decay)):
+            idx = list(range(at, at + len(members)))
+            at += len(members)
+            groups.append(dict(lr=self.lr, momentum=self.momentum, dampening=0, weight_decay=wd, nesterov=bool(self.nesterov), params=idx))
+            for i, (_, p) in zip(idx, members):
+                state[i] = {"momentum_buffer": momentum[p].detach().clone()}
+        extra = dict(format=self.STATE_FORMAT, device_lr=self.lr_dev is not None, clip_state=self._clip_words())
+        return {"state": state, "param_groups": groups, "cotnet_amd": extra}
+
+    def load_state_dict(self, d):
+        """the inverse of state_dict().  Parameters are matched by group ([no_decay, decay]) and position, their shapes checked, all
+        before anything is written.  A dict without 'cotnet_amd' is accepted (a checkpoint the reference wrote): hyper-parameter keys a
+        group lacks keep the constructor's values, an index without a momentum_buffer (torch before its first step) gives zero momentum
+        -- with dampening 0 the same next step.  lr goes through set_lr (its rules hold)."""
+        self._not_while_capturing("load_state_dict()")
+        ours, theirs = self._groups(), d["param_groups"]
+        if len(theirs) != 2 or [len(g["params"]) for g in theirs] != [len(g) for g in ours]:
+            raise ValueError(f"FlatSGD.load_state_dict(): param_groups of {[len(g['params']) for g in theirs]} parameters, this optimizer "
+                             f"has [no_decay, decay] = {[len(g) for g in ours]} (the reference's add_weight_decay order)")
+        hp = {}
+        for key, group, default in (("lr", 0, self.lr), ("momentum", 0, self.momentum), ("nesterov", 0, self.nesterov),
+                                    ("weight_decay", 1, self.weight_decay)):
+            hp[key] = theirs[group].get(key, default)
+        if any(g.get("dampening", 0) != 0 for g in theirs) or theirs[0].get("weight_decay", 0.0) != 0.0 \
+                or any(g.get(k, hp[k]) != hp[k] for g in theirs for k in ("lr", "momentum", "nesterov")):
+            raise ValueError("FlatSGD.load_state_dict(): the step kernels take one lr / momentum / nesterov for both groups, dampening 0 and "
+                             f"no weight decay on the first group; the checkpoint's groups say {[{k: v for k, v in g.items() if k != 'params'} for g in theirs]}")
+        state = d.get("state", {})
+        values = {}
+        for members, g in zip(ours, theirs):
+            for (name, p), idx in zip(members, g["params"]):
+                buf = (state.get(idx) or state.get(str(idx)) or {}).get("momentum_buffer")
+                if buf is not None and tuple(buf.shape) != tuple(p.shape):
+                    raise ValueError(f"FlatSGD.load_state_dict(): momentum_buffer of index {idx} has shape {tuple(buf.shape)}, "
+                                     f"parameter '{name}' at that place has {tuple(p.shape)}")
+                values[p] = buf
+        extra = d.get("cotnet_amd") or {}
+        if extra and extra.get("format") != self.STATE_FORMAT:
+            raise ValueError(f"FlatSGD.load_state_dict(): 'cotnet_amd' format {extra.get('format')!r}, this build reads {self.STATE_FORMAT}")
+        self.set_lr(hp["lr"])
+        self.momentum, self.weight_decay, self.nesterov = float(hp["momentum"]), float(hp["weight_decay"]), bool(hp["nesterov"])
+        mom = self._slots("mom")
+        with torch.no_grad():
+            for p, buf in values.items():
+                mom[p].zero_() if buf is None else mom[p].copy_(buf)
+            words = extra.get("clip_state")
+            if self.clip_state is not None and words is not None:
+                self.clip_state.copy_(torch.tensor(words, dtype=torch.int32))
+
+    def load_ema_state_dict(self, sd=None):
+        """the inverse of ema_state_dict(), averaged buffers included (a `module.` prefix is stripped; integer buffers belong to the model
+        and are not touched).  sd None -- a checkpoint without `state_dict_ema` -- sets the average from the weights as they are now
+        (load the model first), as the reference's load_checkpoint(model_ema.module, resume, use_ema=True) does when the key is missing
+        (train.py:125-126, models/helpers.py:28-30)."""
+        assert self.ema_decay is not None, "FlatSGD was built without ema_decay"
+        self._not_while_capturing("load_ema_state_dict()")
+        with torch.no_grad():
+            if sd is None:
+                for b, st in zip(self.reducer.buckets, self.state):
+                    st["ema"].copy_(st["master"] if st["master"] is not None else b.pflat)
+                for bf, e in zip(self._buf_src, self._buf_ema):
+                    e.copy_(bf)
+                return
+            sd = self._strip(sd)
+            live = self.model.state_dict()
+            self._check_keys(sd, True, {k: v.shape for k, v in live.items()})
+            ema = self._slots("ema")
+            params = dict(self.model.named_parameters())
+            by_buf = {id(bf): e for bf, e in zip(self._buf_src, self._buf_ema)}
+            bufs = dict(self.model.named_buffers())
+            for k in live:
+                p = params.get(k)
+                if p is not None and p in ema:
+                    ema[p].copy_(sd[k])
+                elif k in bufs and id(bufs[k]) in by_buf:
+                    by_buf[id(bufs[k])].copy_(sd[k])

@@ -69,6 +69,9 @@ def load_state_dict(checkpoint_path, use_ema=False):
 
 
 def load_checkpoint(model, checkpoint_path, use_ema=False, strict=True):
+    """weights only, into the model's own tensors.  After a FlatSGD has been built on the model, load through the optimizer
+    (cotnet_amd.checkpoint.resume_checkpoint, FlatSGD.load_model_state_dict): it steps on fp32 masters it took when it was built, and
+    the next step() would write them back over what was loaded here."""
     return model.load_state_dict(load_state_dict(checkpoint_path, use_ema), strict=strict)
 
 
