@@ -401,6 +401,44 @@ int cot_sgd_step_clip(void* param, void* master, void* momentum_buf, const void*
                          weight_decay, grad_scale, nesterov, param_dtype, grad_dtype, (hipStream_t)stream);
 }
 
+// (the fp32 rounding of a beta the kernel multiplies by must stay below 1 too)
+static int check_betas(double beta1, double beta2) {
+    if (!(beta1 >= 0.0 && (float)beta1 < 1.f)) return set_error(COT_ERR_INVALID_ARG, "beta1 %g outside [0, 1)", beta1);
+    if (!(beta2 >= 0.0 && (float)beta2 < 1.f)) return set_error(COT_ERR_INVALID_ARG, "beta2 %g outside [0, 1)", beta2);
+    return COT_OK;
+}
+
+int cot_adam_tick(void* adam_state, const void* clip_state, double beta1, double beta2, void* stream) {
+    if (!adam_state) return set_error(COT_ERR_INVALID_ARG, "NULL adam_state (the device block the step count lives in)");
+    if ((uintptr_t)adam_state % 4 != 0) return set_error(COT_ERR_INVALID_ARG, "adam_state %p is not 4-byte aligned", adam_state);
+    if ((uintptr_t)clip_state % 4 != 0) return set_error(COT_ERR_INVALID_ARG, "clip_state %p is not 4-byte aligned", clip_state);
+    int rc = check_betas(beta1, beta2);
+    if (rc) return rc;
+    return adam_tick(adam_state, clip_state, beta1, beta2, (hipStream_t)stream);
+}
+
+int cot_adamw_step(void* param, void* master, void* exp_avg, void* exp_avg_sq, const void* grad, int64_t n, float lr, const void* lr_dev,
+                   const void* adam_state, const void* clip_state, double beta1, double beta2, float eps, float weight_decay,
+                   float grad_scale, int decoupled, int param_dtype, int grad_dtype, void* stream) {
+    if (!param || !exp_avg || !exp_avg_sq || !grad) return set_error(COT_ERR_INVALID_ARG, "NULL device pointer");
+    if (!adam_state) return set_error(COT_ERR_INVALID_ARG, "NULL adam_state (the device block the bias corrections are read from)");
+    if (n <= 0) return set_error(COT_ERR_INVALID_ARG, "non-positive element count %lld", (long long)n);
+    int rc = check_align16({param, master, exp_avg, exp_avg_sq, grad});
+    if (rc) return rc;
+    if ((uintptr_t)lr_dev % 4 != 0) return set_error(COT_ERR_INVALID_ARG, "lr_dev %p is not 4-byte aligned", lr_dev);
+    if ((uintptr_t)adam_state % 4 != 0) return set_error(COT_ERR_INVALID_ARG, "adam_state %p is not 4-byte aligned", adam_state);
+    if ((uintptr_t)clip_state % 4 != 0) return set_error(COT_ERR_INVALID_ARG, "clip_state %p is not 4-byte aligned", clip_state);
+    rc = check_betas(beta1, beta2);
+    if (rc) return rc;
+    if (!(eps > 0.f) || !(eps <= FLT_MAX)) return set_error(COT_ERR_INVALID_ARG, "eps %g is not a finite positive number", (double)eps);
+    if (!(lr >= 0.f) || !(lr <= FLT_MAX)) return set_error(COT_ERR_INVALID_ARG, "lr %g is not finite and >= 0", (double)lr);
+    if (!(weight_decay >= 0.f) || !(weight_decay <= FLT_MAX))
+        return set_error(COT_ERR_INVALID_ARG, "weight_decay %g is not finite and >= 0", (double)weight_decay);
+    return adamw_flat(param, master, exp_avg, exp_avg_sq, grad, n, lr, (const float*)lr_dev, (const cot_adam_state*)adam_state,
+                      (const cot_clip_state*)clip_state, beta1, beta2, eps, weight_decay, grad_scale, decoupled, param_dtype, grad_dtype,
+                      (hipStream_t)stream);
+}
+
 int cot_ema_step(void* ema, const void* src, int64_t n, float decay, int src_dtype, void* stream) {
     if (!ema || !src) return set_error(COT_ERR_INVALID_ARG, "NULL device pointer");
     if (n <= 0) return set_error(COT_ERR_INVALID_ARG, "non-positive element count %lld", (long long)n);

@@ -57,6 +57,12 @@ int sgd_flat_lr(void* param, void* master, void* mom, const void* grad, int64_t 
 int sgd_flat_clip(void* param, void* master, void* mom, const void* grad, int64_t n, float lr, const float* lr_dev, const cot_clip_state* clip,
                   float momentum, float wd, float gscale, int nesterov, int param_dtype, int grad_dtype, hipStream_t s);
 
+// ---- adamw.hip: Adam / AdamW over flat buffers behind one step count in device memory (arguments validated by cot_abi.hip)
+int adam_tick(void* adam_state, const void* clip_state, double beta1, double beta2, hipStream_t s);
+int adamw_flat(void* param, void* master, void* exp_avg, void* exp_avg_sq, const void* grad, int64_t n, float lr, const float* lr_dev,
+               const cot_adam_state* st, const cot_clip_state* clip, double beta1, double beta2, float eps, float wd, float gscale, int decoupled,
+               int param_dtype, int grad_dtype, hipStream_t s);
+
 // ---- grad_clip.hip: the gradients' global norm -> clip coefficient / skip flag in a block in device memory (read by sgd_flat_clip)
 int grad_sumsq(const void* grad, int64_t n, int grad_dtype, float* partials, hipStream_t s);
 int grad_clip_finish(const float* partials, int64_t nparts, float max_norm, void* state, hipStream_t s);

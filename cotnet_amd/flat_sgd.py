@@ -122,19 +122,32 @@ class FlatSGD:
         is kept.  Not together with clip_grad: the reference runs one mode per step.  `agc_stats()` and `agc_coefficients()` read
         the last step's coefficients.
         agc_eps: the floor of the weight norm (the reference's eps = 1e-3)."""
+        self.momentum, self.nesterov = float(momentum), nesterov
+        self._setup(model, lr, weight_decay, bucket_mb, process_group, broadcast_params, ema_decay, force_collectives, grad_dtype,
+                    device_lr, clip_grad, clip_mode, skip_nonfinite, agc, agc_eps)
+
+    def _bucket_state(self, b):
+        """what the update rule keeps per bucket next to the master: fp32 arrays of the bucket's length, allocated once"""
+        return {"mom": torch.zeros(b.pflat.numel(), dtype=torch.float32, device=b.pflat.device)}
+
+    def _setup(self, model, lr, weight_decay, bucket_mb, process_group, broadcast_params, ema_decay, force_collectives, grad_dtype,
+               device_lr, clip_grad, clip_mode, skip_nonfinite, agc, agc_eps):
+        """everything of the constructor that does not depend on the update rule (FlatAdamW, flat_adamw.py, shares it): the keywords'
+        checks, the buckets and masters, the device-resident rate, the clip block, the AGC tables, the averages"""
+        name = type(self).__name__
         if clip_mode != "norm":
-            raise ValueError(f"FlatSGD(clip_mode={clip_mode!r}): only 'norm' (clipping by the global L2 norm) is a value of clip_mode; "
+            raise ValueError(f"{name}(clip_mode={clip_mode!r}): only 'norm' (clipping by the global L2 norm) is a value of clip_mode; "
                              "the reference's other modes 'value' and 'agc' are not values of clip_mode: adaptive clipping is "
-                             "FlatSGD(agc=...), and clipping by value is not built")
+                             f"{name}(agc=...), and clipping by value is not built")
         self.agc = float(agc) if agc is not None and agc > 0 else None
         self.agc_eps = float(agc_eps)
         if self.agc is not None:
             if clip_grad is not None and clip_grad > 0:
-                raise ValueError(f"FlatSGD(agc={agc!r}, clip_grad={clip_grad!r}): one clipping mode per step, as in the reference's "
+                raise ValueError(f"{name}(agc={agc!r}, clip_grad={clip_grad!r}): one clipping mode per step, as in the reference's "
                                  "dispatch_clip_grad -- give agc or clip_grad, not both")
             if not (math.isfinite(self.agc) and math.isfinite(self.agc_eps) and self.agc_eps > 0):
-                raise ValueError(f"FlatSGD(agc={agc!r}, agc_eps={agc_eps!r}): both must be finite and positive")
-        self.lr, self.momentum, self.weight_decay, self.nesterov = float(lr), float(momentum), float(weight_decay), nesterov
+                raise ValueError(f"{name}(agc={agc!r}, agc_eps={agc_eps!r}): both must be finite and positive")
+        self.lr, self.weight_decay = float(lr), float(weight_decay)
         self.ema_decay = None if ema_decay is None else float(ema_decay)
         self._captured_lr = None  # the rate a HIP-graph capture of step() baked into its cot_sgd_step launches (set_lr)
         self.model = model
@@ -146,7 +159,7 @@ class FlatSGD:
         self.state = []
         for b in self.reducer.buckets:
             master = b.pflat.float().clone() if b.pflat.dtype != torch.float32 else None
-            st = {"master": master, "mom": torch.zeros(b.pflat.numel(), dtype=torch.float32, device=b.pflat.device)}
+            st = {"master": master, **self._bucket_state(b)}
             if self.ema_decay is not None:
                 st["ema"] = (master if master is not None else b.pflat).float().clone()
             self.state.append(st)
@@ -186,12 +199,9 @@ class FlatSGD:
             self.reducer.finish()
         L = _lib.api()
         stream = _lib.stream()
-        if self.lr_dev is not None:  # the kernel reads the rate when it runs: a capture bakes none
-            sgd, rate = L.cot_sgd_step_lr, (self.lr_dev.data_ptr(),)
-        else:
-            sgd, rate = L.cot_sgd_step, (self.lr,)
-            if _lib.capturing():  # cot_sgd_step takes the rate by value: every replay of this capture steps with it (set_lr)
-                self._captured_lr = self.lr
+        # (with lr_dev the kernel reads the rate when it runs: a capture bakes none)
+        if self.lr_dev is None and _lib.capturing():  # the rate travels by value: every replay of this capture steps with it (set_lr)
+            self._captured_lr = self.lr
         if self.agc is not None:
             # unit-wise clipping of the AVERAGED gradients, in place in the buckets; what follows (guard, SGD) reads the clipped ones
             for b, st, units, coef in zip(self.reducer.buckets, self.state, self._agc_units, self._agc_coef):
@@ -201,8 +211,9 @@ class FlatSGD:
                 weight = st["master"] if st["master"] is not None else b.pflat
                 L.cot_agc_clip(g.data_ptr(), weight.data_ptr(), units.data_ptr(), units.shape[0], g.numel(), self.agc, self.agc_eps,
                                coef.data_ptr(), _lib.dtype_code(g.dtype), stream)
-        if self.clip_state is not None and self.reducer.buckets:
-            # the norm of the AVERAGED gradients over every bucket -> coefficient and skip flag in self.clip_state, which the SGD
+        clipped = self.clip_state is not None and bool(self.reducer.buckets)
+        if clipped:
+            # the norm of the AVERAGED gradients over every bucket -> coefficient and skip flag in self.clip_state, which the update
             # kernels below read when they run
             parts = L.cot_grad_norm_parts()
             for i, b in enumerate(self.reducer.buckets):
@@ -210,16 +221,9 @@ class FlatSGD:
                 L.cot_grad_sumsq(g.data_ptr(), g.numel(), _lib.dtype_code(g.dtype), self._clip_parts.data_ptr() + 4 * parts * i, stream)
             L.cot_grad_clip_finish(self._clip_parts.data_ptr(), self._clip_parts.numel(),
                                    self.clip_grad if self.clip_grad is not None else float("inf"), self.clip_state.data_ptr(), stream)
-            sgd = L.cot_sgd_step_clip
-            rate = (self.lr, self.lr_dev.data_ptr() if self.lr_dev is not None else None, self.clip_state.data_ptr())
+        update = self._bucket_update(L, clipped, stream)
         for b, st in zip(self.reducer.buckets, self.state):
-            key = b.key
-            wd = self.weight_decay if key == "decay" else 0.0
-            sgd(b.pflat.data_ptr(),
-                st["master"].data_ptr() if st["master"] is not None else None,
-                st["mom"].data_ptr(), self.reducer.reduced(b).data_ptr(),
-                b.pflat.numel(), *rate, self.momentum, wd, 1.0, 1 if self.nesterov else 0,
-                _lib.dtype_code(b.pflat.dtype), _lib.dtype_code(self.reducer.reduced(b).dtype), stream)
+            update(b, st, self.weight_decay if b.key == "decay" else 0.0)
             if self.ema_decay is not None:
                 src = st["master"] if st["master"] is not None else b.pflat
                 L.cot_ema_step(st["ema"].data_ptr(), src.data_ptr(), src.numel(),
@@ -231,15 +235,34 @@ class FlatSGD:
             from . import cot_layer_fused
             cot_layer_fused.after_optimizer_step(self.reducer.buckets[0].pflat.device)
 
+    def _bucket_update(self, L, clipped, stream):
+        """the update rule's launches: called once per step() behind the clip launches (`clipped`: the block was filled), returns
+        update(bucket, its state, its weight decay), which step() calls per bucket in front of the bucket's EMA launch"""
+        if clipped:
+            sgd = L.cot_sgd_step_clip
+            rate = (self.lr, self.lr_dev.data_ptr() if self.lr_dev is not None else None, self.clip_state.data_ptr())
+        elif self.lr_dev is not None:
+            sgd, rate = L.cot_sgd_step_lr, (self.lr_dev.data_ptr(),)
+        else:
+            sgd, rate = L.cot_sgd_step, (self.lr,)
+
+        def update(b, st, wd):
+            sgd(b.pflat.data_ptr(),
+                st["master"].data_ptr() if st["master"] is not None else None,
+                st["mom"].data_ptr(), self.reducer.reduced(b).data_ptr(),
+                b.pflat.numel(), *rate, self.momentum, wd, 1.0, 1 if self.nesterov else 0,
+                _lib.dtype_code(b.pflat.dtype), _lib.dtype_code(self.reducer.reduced(b).dtype), stream)
+        return update
+
     def clip_stats(self):
         """ONE host read of the clip block: dict(total_norm, scale, skip, steps, clipped, skipped) -- the last step's norm, coefficient
         and skip flag, and the counts since construction (or since the caller last zeroed `self.clip_state`).  It synchronises with
         the device, so it belongs at a logging interval, not in every step; refused while a HIP graph is being captured (the read
         would see what the block held before the capture: recorded launches have not run)."""
         if self.clip_state is None:
-            raise RuntimeError("FlatSGD.clip_stats(): built with neither clip_grad nor skip_nonfinite")
+            raise RuntimeError(f"{type(self).__name__}.clip_stats(): built with neither clip_grad nor skip_nonfinite")
         if _lib.capturing():
-            raise RuntimeError("FlatSGD.clip_stats() inside a HIP-graph capture: the launches that fill the block are only recorded, "
+            raise RuntimeError(f"{type(self).__name__}.clip_stats() inside a HIP-graph capture: the launches that fill the block are only recorded, "
                                "and a host read cannot be -- read the block between replays")
         w = self.clip_state.cpu()
         scale, total_norm = w[:2].view(torch.float32).tolist()
@@ -252,9 +275,9 @@ class FlatSGD:
         smallest coefficient (1.0 when nothing clipped).  Like clip_stats() it synchronises with the device and is refused while a HIP
         graph is being captured."""
         if self._agc_coef is None:
-            raise RuntimeError("FlatSGD.agc_stats(): built without agc")
+            raise RuntimeError(f"{type(self).__name__}.agc_stats(): built without agc")
         if _lib.capturing():
-            raise RuntimeError("FlatSGD.agc_stats() inside a HIP-graph capture: the launches that fill the coefficients are only "
+            raise RuntimeError(f"{type(self).__name__}.agc_stats() inside a HIP-graph capture: the launches that fill the coefficients are only "
                                "recorded, and a host read cannot be -- read them between replays")
         c = torch.cat(self._agc_coef).cpu() if self._agc_coef else torch.zeros(0)
         bad = torch.isnan(c)
@@ -267,7 +290,7 @@ class FlatSGD:
         what the last step's `cot_agc_clip` launches left (1 = not clipped, NaN = a norm was not finite).  The views stay valid:
         the tensors are never reallocated."""
         if self._agc_coef is None:
-            raise RuntimeError("FlatSGD.agc_coefficients(): built without agc")
+            raise RuntimeError(f"{type(self).__name__}.agc_coefficients(): built without agc")
         out = {}
         for b, coef in zip(self.reducer.buckets, self._agc_coef):
             at = 0
@@ -280,7 +303,7 @@ class FlatSGD:
     def ema_state_dict(self):
         """the averaged weights under the model's own state_dict keys (fp32; integer buffers are copied as they are) --
         what the reference stores as `state_dict_ema` (utils/checkpoint_saver.py:103-120)"""
-        assert self.ema_decay is not None, "FlatSGD was built without ema_decay"
+        assert self.ema_decay is not None, f"{type(self).__name__} was built without ema_decay"
         by_param = {}
         esz = {}
         for b, st in zip(self.reducer.buckets, self.state):
@@ -311,9 +334,9 @@ class FlatSGD:
         master from the master (the working copy is always the rounded master), fp32 buckets and the buffers from copies taken on
         entry.  Masters, momentum, the averages and integer buffers are never written.  No step() inside the context; refused while a
         HIP graph is being captured (the recorded copies would swap the weights at every replay)."""
-        assert self.ema_decay is not None, "FlatSGD was built without ema_decay"
+        assert self.ema_decay is not None, f"{type(self).__name__} was built without ema_decay"
         if _lib.capturing():
-            raise RuntimeError("FlatSGD.ema_weights() inside a HIP-graph capture: the copies would be recorded and swap the weights at "
+            raise RuntimeError(f"{type(self).__name__}.ema_weights() inside a HIP-graph capture: the copies would be recorded and swap the weights at "
                                "every replay -- enter the context outside the capture (a captured forward reads the weights when it runs)")
         from . import cot_layer_fused
         buckets = self.reducer.buckets
@@ -356,14 +379,14 @@ class FlatSGD:
         lr = float(lr)
         if self.lr_dev is not None:
             if _lib.capturing():
-                raise RuntimeError(f"FlatSGD.set_lr({lr:g}) inside a HIP-graph capture: the fill of the device-resident rate would be "
+                raise RuntimeError(f"{type(self).__name__}.set_lr({lr:g}) inside a HIP-graph capture: the fill of the device-resident rate would be "
                                    "recorded and reset the rate at every replay -- set the rate outside the capture (replays read "
                                    "lr_dev when they run); the rate is left as it was")
             self.lr = lr
             self.lr_dev.fill_(self.lr)
             return
         if self._captured_lr is not None and lr != self._captured_lr and not _lib.capturing():
-            raise RuntimeError(f"FlatSGD.set_lr({lr:g}): step() was captured into a HIP graph at lr = {self._captured_lr:g}, and replays "
+            raise RuntimeError(f"{type(self).__name__}.set_lr({lr:g}): step() was captured into a HIP graph at lr = {self._captured_lr:g}, and replays "
                                "keep the captured rate -- capture the step again and set the new rate inside that capture (its "
                                "step() records it); the rate is left as it was")
         self.lr = lr
@@ -385,7 +408,7 @@ class FlatSGD:
 
     def _not_while_capturing(self, what):
         if _lib.capturing():
-            raise RuntimeError(f"FlatSGD.{what} inside a HIP-graph capture: its copies and launches would be recorded and run again at "
+            raise RuntimeError(f"{type(self).__name__}.{what} inside a HIP-graph capture: its copies and launches would be recorded and run again at "
                                "every replay, and a host read cannot be recorded -- save and load between replays (the state keeps its "
                                "addresses: a captured step replays what was loaded); nothing was changed")
 
@@ -532,7 +555,7 @@ class FlatSGD:
         and are not touched).  sd None -- a checkpoint without `state_dict_ema` -- sets the average from the weights as they are now
         (load the model first), as the reference's load_checkpoint(model_ema.module, resume, use_ema=True) does when the key is missing
         (train.py:125-126, models/helpers.py:28-30)."""
-        assert self.ema_decay is not None, "FlatSGD was built without ema_decay"
+        assert self.ema_decay is not None, f"{type(self).__name__} was built without ema_decay"
         self._not_while_capturing("load_ema_state_dict()")
         with torch.no_grad():
             if sd is None:

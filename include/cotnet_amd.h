@@ -580,6 +580,51 @@ int cot_agc_max_groups(void); /* = COT_AGC_MAX_GROUPS; makes no HIP call */
 int cot_agc_clip(void* grad, const void* weight, const void* units, int64_t nunits, int64_t n, float clip_factor, float eps, void* coef,
                  int grad_dtype, void* stream);
 
+/* ---- fused Adam / AdamW over a flat parameter bucket (reference: optim/optim_factory.py:60-65, `adam` -> torch.optim.Adam, `adamw` ->
+ * optim/adamw.py:72-115, one or more elementwise launches per parameter tensor and a host-side step count per parameter).  Here: one
+ * launch per bucket, and the step count and the bias corrections live in ONE 32-byte block in device memory, so that a HIP graph that
+ * recorded the step serves every step:
+ *   1. cot_adam_tick    once per step, in front of the bucket kernels: step += 1 and both corrections, or nothing on a skipped step
+ *   2. cot_adamw_step   per bucket: reads the block (and, where given, the clip block and the device-resident rate) when it runs
+ *
+ * The block (4-byte aligned, device memory; the caller zeroes it once; cot_adam_tick is its only writer on the device, cot_adamw_step
+ * only reads it; successive calls are ordered by the stream).  bc1 and sqrt_bc2 are a pure function of the integer `step` and the
+ * betas -- computed from `step` in double on every tick, never by repeated multiplication -- so a block whose `step` was set to t - 1
+ * and ticked once holds bit for bit what t ticks from zero leave: a resumed run is bit-equal to an uninterrupted one. */
+typedef struct cot_adam_state {
+    int32_t step;        /* steps taken: cot_adam_tick adds 1 unless the step is skipped; cot_adamw_step does not read it */
+    float bc1;           /* (float)(1 - beta1^step), the power in double; written by cot_adam_tick, read by cot_adamw_step */
+    float sqrt_bc2;      /* (float)sqrt(1 - beta2^step), in double; written by cot_adam_tick, read by cot_adamw_step */
+    int32_t refused;     /* ticks that found clip_state->skip != 0 and advanced nothing; written by cot_adam_tick only */
+    int32_t reserved[4]; /* never written by a kernel: they stay as the caller left them (0) */
+} cot_adam_state;
+
+/* One workgroup, lane 0's plain read-modify-write of the block.  clip_state given (cot_clip_state, as cot_grad_clip_finish left it) and
+ * its skip != 0: refused += 1 and nothing else.  Otherwise step += 1, bc1 = (float)(1 - pow(beta1, step)),
+ * sqrt_bc2 = (float)sqrt(1 - pow(beta2, step)): two `pow` per STEP, none per element.  The betas are doubles, as torch and the reference
+ * hold them (`1 - beta1 ** step` in Python): pow on their fp32 roundings would move the corrections by ~1e-5 after 1000 steps.
+ * NULL or misaligned (4 bytes) adam_state, misaligned clip_state, a beta outside [0, 1): COT_ERR_INVALID_ARG before any device work. */
+int cot_adam_tick(void* adam_state, const void* clip_state, double beta1, double beta2, void* stream);
+
+/* One bucket's step.  param / master / dtypes as for cot_sgd_step (param_dtype COT_BF16 needs the fp32 `master`, COT_F32 takes
+ * master == NULL; grad_dtype COT_BF16 or COT_F32); exp_avg and exp_avg_sq are fp32, n elements, updated in place.  lr_dev NULL: the
+ * rate is `lr`; given: one device float read when the kernel runs, `lr` ignored (cot_sgd_step_lr's rules).  clip_state NULL: no block;
+ * given: every lane reads its scale and skip once in front of the loop, skip != 0 ends the kernel before it has written anything, and
+ * the gradient's factor is the ONE fp32 product grad_scale * scale.  adam_state is only read (bc1, sqrt_bc2).  Per element, in fp32,
+ * in this order (csrc/adamw.hip states it in full; hipcc may contract a multiply and an add into one FMA):
+ *     g = grad * gs                      gs = grad_scale, or grad_scale * scale        (decoupled == 0:  g = g + weight_decay * p)
+ *     p = p * (1 - lr * weight_decay)    decoupled != 0 only (AdamW: the reference decays first)
+ *     m = m * b1 + o1 * g                b1 = (float)beta1, o1 = (float)(1 - beta1): the doubles rounded once each, as torch rounds them
+ *     v = v * b2 + (o2 * g) * g          b2 = (float)beta2, o2 = (float)(1 - beta2)
+ *     p = p - (lr / bc1) * (m / (sqrtf(v) / sqrt_bc2 + eps))
+ * m, v, the master if there is one and the working copy (p rounded to param_dtype) are written.  No amsgrad.
+ * NULL param / exp_avg / exp_avg_sq / grad / adam_state, an array not 16-byte or adam_state / clip_state / lr_dev not 4-byte aligned,
+ * n < 1, a beta outside [0, 1), eps not finite or not > 0, lr or weight_decay not finite or < 0: COT_ERR_INVALID_ARG; a dtype / master
+ * combination cot_sgd_step does not take: COT_ERR_UNSUPPORTED -- reported through cot_last_error() before any device work. */
+int cot_adamw_step(void* param, void* master, void* exp_avg, void* exp_avg_sq, const void* grad, int64_t n, float lr, const void* lr_dev,
+                   const void* adam_state, const void* clip_state, double beta1, double beta2, float eps, float weight_decay,
+                   float grad_scale, int decoupled, int param_dtype, int grad_dtype, void* stream);
+
 /* ---- exponential moving average of the weights over a flat buffer (replaces the per-tensor
  * `ema = decay*ema + (1-decay)*model` of ModelEmaV2._update, utils/model_ema.py:45-53):  ema fp32 [n], src the fp32
  * master copy / fp32 parameters (COT_F32) or bf16 parameters (COT_BF16). */
