@@ -219,6 +219,26 @@ static int check_align16(std::initializer_list<const void*> ptrs) {
     return COT_OK;
 }
 
+// What the flat step entry points (cot_sgd_step, _lr, _clip, cot_adamw_step) share: the bucket pointers (`master` may be NULL, the
+// others not) are 16-byte aligned, n > 0, and each optional word or block in device memory (`words`, named for the message) is 4-byte
+// aligned.  What an entry point REQUIRES of its words, and its value ranges, it checks itself.
+struct DevWord {
+    const char* name;
+    const void* p;
+};
+static int check_flat_step(std::initializer_list<const void*> required, const void* master, int64_t n,
+                           std::initializer_list<DevWord> words = {}) {
+    for (const void* p : required)
+        if (!p) return set_error(COT_ERR_INVALID_ARG, "NULL device pointer");
+    if (n <= 0) return set_error(COT_ERR_INVALID_ARG, "non-positive element count %lld", (long long)n);
+    int rc = check_align16(required);
+    if (!rc) rc = check_align16({master});
+    if (rc) return rc;
+    for (const DevWord& w : words)
+        if ((uintptr_t)w.p % 4 != 0) return set_error(COT_ERR_INVALID_ARG, "%s %p is not 4-byte aligned", w.name, w.p);
+    return COT_OK;
+}
+
 extern "C" {
 
 int cot_abi_version(void) { return COTNET_AMD_ABI_VERSION; }
@@ -321,9 +341,7 @@ int cot_debug_stamps(void* device_buffer) {
 
 int cot_sgd_step(void* param, void* master, void* momentum_buf, const void* grad, int64_t n, float lr, float momentum,
                  float weight_decay, float grad_scale, int nesterov, int param_dtype, int grad_dtype, void* stream) {
-    if (!param || !momentum_buf || !grad) return set_error(COT_ERR_INVALID_ARG, "NULL device pointer");
-    if (n <= 0) return set_error(COT_ERR_INVALID_ARG, "non-positive element count %lld", (long long)n);
-    int rc = check_align16({param, master, momentum_buf, grad});
+    int rc = check_flat_step({param, momentum_buf, grad}, master, n);
     if (rc) return rc;
     return sgd_flat(param, master, momentum_buf, grad, n, lr, momentum, weight_decay, grad_scale, nesterov, param_dtype,
                     grad_dtype, (hipStream_t)stream);
@@ -332,12 +350,9 @@ int cot_sgd_step(void* param, void* master, void* momentum_buf, const void* grad
 int cot_sgd_step_lr(void* param, void* master, void* momentum_buf, const void* grad, int64_t n, const void* lr_dev,
                     float momentum, float weight_decay, float grad_scale, int nesterov, int param_dtype, int grad_dtype,
                     void* stream) {
-    if (!param || !momentum_buf || !grad) return set_error(COT_ERR_INVALID_ARG, "NULL device pointer");
     if (!lr_dev) return set_error(COT_ERR_INVALID_ARG, "NULL lr_dev (the device float the rate is read from)");
-    if (n <= 0) return set_error(COT_ERR_INVALID_ARG, "non-positive element count %lld", (long long)n);
-    int rc = check_align16({param, master, momentum_buf, grad});
+    int rc = check_flat_step({param, momentum_buf, grad}, master, n, {{"lr_dev", lr_dev}});
     if (rc) return rc;
-    if ((uintptr_t)lr_dev % 4 != 0) return set_error(COT_ERR_INVALID_ARG, "lr_dev %p is not 4-byte aligned", lr_dev);
     return sgd_flat_lr(param, master, momentum_buf, grad, n, (const float*)lr_dev, momentum, weight_decay, grad_scale,
                        nesterov, param_dtype, grad_dtype, (hipStream_t)stream);
 }
@@ -390,13 +405,9 @@ int cot_agc_clip(void* grad, const void* weight, const void* units, int64_t nuni
 int cot_sgd_step_clip(void* param, void* master, void* momentum_buf, const void* grad, int64_t n, float lr, const void* lr_dev,
                       const void* clip_state, float momentum, float weight_decay, float grad_scale, int nesterov, int param_dtype,
                       int grad_dtype, void* stream) {
-    if (!param || !momentum_buf || !grad) return set_error(COT_ERR_INVALID_ARG, "NULL device pointer");
     if (!clip_state) return set_error(COT_ERR_INVALID_ARG, "NULL clip_state (the device block the step's coefficient is read from)");
-    if (n <= 0) return set_error(COT_ERR_INVALID_ARG, "non-positive element count %lld", (long long)n);
-    int rc = check_align16({param, master, momentum_buf, grad});
+    int rc = check_flat_step({param, momentum_buf, grad}, master, n, {{"lr_dev", lr_dev}, {"clip_state", clip_state}});
     if (rc) return rc;
-    if ((uintptr_t)lr_dev % 4 != 0) return set_error(COT_ERR_INVALID_ARG, "lr_dev %p is not 4-byte aligned", lr_dev);
-    if ((uintptr_t)clip_state % 4 != 0) return set_error(COT_ERR_INVALID_ARG, "clip_state %p is not 4-byte aligned", clip_state);
     return sgd_flat_clip(param, master, momentum_buf, grad, n, lr, (const float*)lr_dev, (const cot_clip_state*)clip_state, momentum,
                          weight_decay, grad_scale, nesterov, param_dtype, grad_dtype, (hipStream_t)stream);
 }
@@ -420,14 +431,10 @@ int cot_adam_tick(void* adam_state, const void* clip_state, double beta1, double
 int cot_adamw_step(void* param, void* master, void* exp_avg, void* exp_avg_sq, const void* grad, int64_t n, float lr, const void* lr_dev,
                    const void* adam_state, const void* clip_state, double beta1, double beta2, float eps, float weight_decay,
                    float grad_scale, int decoupled, int param_dtype, int grad_dtype, void* stream) {
-    if (!param || !exp_avg || !exp_avg_sq || !grad) return set_error(COT_ERR_INVALID_ARG, "NULL device pointer");
     if (!adam_state) return set_error(COT_ERR_INVALID_ARG, "NULL adam_state (the device block the bias corrections are read from)");
-    if (n <= 0) return set_error(COT_ERR_INVALID_ARG, "non-positive element count %lld", (long long)n);
-    int rc = check_align16({param, master, exp_avg, exp_avg_sq, grad});
+    int rc = check_flat_step({param, exp_avg, exp_avg_sq, grad}, master, n,
+                             {{"lr_dev", lr_dev}, {"adam_state", adam_state}, {"clip_state", clip_state}});
     if (rc) return rc;
-    if ((uintptr_t)lr_dev % 4 != 0) return set_error(COT_ERR_INVALID_ARG, "lr_dev %p is not 4-byte aligned", lr_dev);
-    if ((uintptr_t)adam_state % 4 != 0) return set_error(COT_ERR_INVALID_ARG, "adam_state %p is not 4-byte aligned", adam_state);
-    if ((uintptr_t)clip_state % 4 != 0) return set_error(COT_ERR_INVALID_ARG, "clip_state %p is not 4-byte aligned", clip_state);
     rc = check_betas(beta1, beta2);
     if (rc) return rc;
     if (!(eps > 0.f) || !(eps <= FLT_MAX)) return set_error(COT_ERR_INVALID_ARG, "eps %g is not a finite positive number", (double)eps);

@@ -50,8 +50,7 @@ class FlatAdamW(FlatSGD):
         self._captured_hp = None  # (betas, eps, weight_decay) a HIP-graph capture of step() baked into its launches
         self._setup(model, lr, weight_decay, bucket_mb, process_group, broadcast_params, ema_decay, force_collectives, grad_dtype,
                     device_lr, clip_grad, clip_mode, skip_nonfinite, agc, agc_eps)
-        dev = self.reducer.buckets[0].pflat.device if self.reducer.buckets else next(model.parameters()).device
-        self.adam_state = torch.zeros(8, dtype=torch.int32, device=dev)  # cot_adam_state: step, bc1, sqrt_bc2, refused, 4 reserved
+        self.adam_state = torch.zeros(8, dtype=torch.int32, device=self._device())  # cot_adam_state: step, bc1, sqrt_bc2, refused, 4 reserved
 
     def _bucket_state(self, b):
         n, dev = b.pflat.numel(), b.pflat.device

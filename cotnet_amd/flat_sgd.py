@@ -130,6 +130,15 @@ class FlatSGD:
         """what the update rule keeps per bucket next to the master: fp32 arrays of the bucket's length, allocated once"""
         return {"mom": torch.zeros(b.pflat.numel(), dtype=torch.float32, device=b.pflat.device)}
 
+    @staticmethod
+    def _weights(b, st):
+        """the bucket's fp32 weights: the master, or the parameters themselves where there is none"""
+        return st["master"] if st["master"] is not None else b.pflat
+
+    def _device(self):
+        """the device of the first bucket, else of the first parameter"""
+        return self.reducer.buckets[0].pflat.device if self.reducer.buckets else next(self.model.parameters()).device
+
     def _setup(self, model, lr, weight_decay, bucket_mb, process_group, broadcast_params, ema_decay, force_collectives, grad_dtype,
                device_lr, clip_grad, clip_mode, skip_nonfinite, agc, agc_eps):
         """everything of the constructor that does not depend on the update rule (FlatAdamW, flat_adamw.py, shares it): the keywords'
@@ -161,17 +170,16 @@ class FlatSGD:
             master = b.pflat.float().clone() if b.pflat.dtype != torch.float32 else None
             st = {"master": master, **self._bucket_state(b)}
             if self.ema_decay is not None:
-                st["ema"] = (master if master is not None else b.pflat).float().clone()
+                st["ema"] = self._weights(b, st).float().clone()
             self.state.append(st)
         self.lr_dev = None
         if device_lr:
-            dev = self.reducer.buckets[0].pflat.device if self.reducer.buckets else next(model.parameters()).device
-            self.lr_dev = torch.full((1,), self.lr, dtype=torch.float32, device=dev)
+            self.lr_dev = torch.full((1,), self.lr, dtype=torch.float32, device=self._device())
         self.clip_grad = float(clip_grad) if clip_grad is not None and clip_grad > 0 else None
         self.skip_nonfinite = bool(skip_nonfinite)
         self.clip_state = self._clip_parts = None
         if self.clip_grad is not None or self.skip_nonfinite:
-            dev = self.reducer.buckets[0].pflat.device if self.reducer.buckets else next(model.parameters()).device
+            dev = self._device()
             self.clip_state = torch.zeros(8, dtype=torch.int32, device=dev)
             self._clip_parts = torch.zeros(max(len(self.reducer.buckets), 1) * _lib.lib().cot_grad_norm_parts(), dtype=torch.float32,
                                            device=dev)
@@ -208,7 +216,7 @@ class FlatSGD:
                 if units.shape[0] == 0:
                     continue
                 g = self.reducer.reduced(b)
-                weight = st["master"] if st["master"] is not None else b.pflat
+                weight = self._weights(b, st)
                 L.cot_agc_clip(g.data_ptr(), weight.data_ptr(), units.data_ptr(), units.shape[0], g.numel(), self.agc, self.agc_eps,
                                coef.data_ptr(), _lib.dtype_code(g.dtype), stream)
         clipped = self.clip_state is not None and bool(self.reducer.buckets)
@@ -225,7 +233,7 @@ class FlatSGD:
         for b, st in zip(self.reducer.buckets, self.state):
             update(b, st, self.weight_decay if b.key == "decay" else 0.0)
             if self.ema_decay is not None:
-                src = st["master"] if st["master"] is not None else b.pflat
+                src = self._weights(b, st)
                 L.cot_ema_step(st["ema"].data_ptr(), src.data_ptr(), src.numel(),
                                self.ema_decay, _lib.dtype_code(src.dtype), stream)
         if self.ema_decay is not None and self._buf_src:
@@ -261,9 +269,7 @@ class FlatSGD:
         would see what the block held before the capture: recorded launches have not run)."""
         if self.clip_state is None:
             raise RuntimeError(f"{type(self).__name__}.clip_stats(): built with neither clip_grad nor skip_nonfinite")
-        if _lib.capturing():
-            raise RuntimeError(f"{type(self).__name__}.clip_stats() inside a HIP-graph capture: the launches that fill the block are only recorded, "
-                               "and a host read cannot be -- read the block between replays")
+        self._not_while_capturing("clip_stats()")
         w = self.clip_state.cpu()
         scale, total_norm = w[:2].view(torch.float32).tolist()
         skip, steps, clipped, skipped = w[2:6].tolist()
@@ -276,9 +282,7 @@ class FlatSGD:
         graph is being captured."""
         if self._agc_coef is None:
             raise RuntimeError(f"{type(self).__name__}.agc_stats(): built without agc")
-        if _lib.capturing():
-            raise RuntimeError(f"{type(self).__name__}.agc_stats() inside a HIP-graph capture: the launches that fill the coefficients are only "
-                               "recorded, and a host read cannot be -- read them between replays")
+        self._not_while_capturing("agc_stats()")
         c = torch.cat(self._agc_coef).cpu() if self._agc_coef else torch.zeros(0)
         bad = torch.isnan(c)
         fin = c[~bad]
@@ -304,11 +308,7 @@ class FlatSGD:
         """the averaged weights under the model's own state_dict keys (fp32; integer buffers are copied as they are) --
         what the reference stores as `state_dict_ema` (utils/checkpoint_saver.py:103-120)"""
         assert self.ema_decay is not None, f"{type(self).__name__} was built without ema_decay"
-        by_param = {}
-        esz = {}
-        for b, st in zip(self.reducer.buckets, self.state):
-            for p, off in zip(b.params, b.offs):
-                by_param[p] = st["ema"][off:off + p.numel()].view_as(p)
+        by_param = self._slots("ema")
         by_buf = {id(bf): e for bf, e in zip(self._buf_src, self._buf_ema)}
         out = {}
         params = dict(self.model.named_parameters())
@@ -393,12 +393,7 @@ class FlatSGD:
 
     def master_parameters(self):
         """fp32 view of every parameter (master copy for bf16 parameters), in module.parameters() order of the buckets"""
-        out = {}
-        for b, st in zip(self.reducer.buckets, self.state):
-            src = st["master"] if st["master"] is not None else b.pflat
-            for p, off in zip(b.params, b.offs):
-                out[p] = src[off:off + p.numel()].view_as(p)
-        return out
+        return self._slots("weights")
 
     # ---- the whole training state, out and in (the reference: CheckpointSaver._save, utils/checkpoint_saver.py:103-120, and
     # resume_checkpoint, models/helpers.py:51-88).  Everything below acts IN PLACE on the allocations made in __init__: no address
@@ -426,7 +421,7 @@ class FlatSGD:
         """{parameter: view of its slot in the buckets' `array`} ('weights': the master, or the fp32 parameters where there is none)"""
         out = {}
         for b, st in zip(self.reducer.buckets, self.state):
-            flat = (st["master"] if st["master"] is not None else b.pflat) if array == "weights" else st[array]
+            flat = self._weights(b, st) if array == "weights" else st[array]
             for p, off in zip(b.params, b.offs):
                 out[p] = flat[off:off + p.numel()].view_as(p)
         return out
@@ -560,7 +555,7 @@ class FlatSGD:
         with torch.no_grad():
             if sd is None:
                 for b, st in zip(self.reducer.buckets, self.state):
-                    st["ema"].copy_(st["master"] if st["master"] is not None else b.pflat)
+                    st["ema"].copy_(self._weights(b, st))
                 for bf, e in zip(self._buf_src, self._buf_ema):
                     e.copy_(bf)
                 return
