@@ -11,7 +11,8 @@ Public surface mirrors the reference (JDAI-CV/CoTNet):
     evaler.evaler / utils.meters         -> cotnet_amd.evaler               (Evaler, DeviceTestMeter, accuracy: scored on the device)
     models.factory / models.registry     -> cotnet_amd.registry             (create_model, register_model)
     utils.checkpoint_saver / models.helpers.resume_checkpoint -> cotnet_amd.checkpoint (CheckpointSaver, resume_checkpoint)
-    optim.optim_factory / optim.adamw    -> cotnet_amd.optim_factory        (create_optimizer -> FlatSGD, FlatAdam, FlatAdamW)
+    optim.optim_factory / optim.adamw / optim.lookahead -> cotnet_amd.optim_factory (create_optimizer -> FlatSGD, FlatAdam, FlatAdamW;
+                                            split_opt_name: `lookahead_*` -> the keywords lookahead_k, lookahead_alpha)
 Device code lives in cotnet_amd/csrc (HIP, gfx950) behind the C ABI of include/cotnet_amd.h.
 """
 from . import _lib  # noqa: F401
@@ -32,6 +33,6 @@ from .registry import create_model, list_models, load_checkpoint, register_model
 from .resnet import ResNet  # noqa: F401
 from .checkpoint import CheckpointSaver, resume_checkpoint  # noqa: F401
 from .flat_adamw import FlatAdam, FlatAdamW  # noqa: F401
-from .optim_factory import create_optimizer  # noqa: F401
+from .optim_factory import create_optimizer, split_opt_name  # noqa: F401
 
 __version__ = "0.1.0"

@@ -128,6 +128,8 @@ SYMBOLS = {
     "cot_agc_clip": (_I, [_P, _P, _P, ctypes.c_int64, ctypes.c_int64, ctypes.c_float, ctypes.c_float, _P, _I, _P]),
     "cot_adam_tick": (_I, [_P, _P, ctypes.c_double, ctypes.c_double, _P]),
     "cot_adamw_step": (_I, [_P] * 5 + [ctypes.c_int64, ctypes.c_float, _P, _P, _P, ctypes.c_double, ctypes.c_double] + [ctypes.c_float] * 3 + [_I, _I, _I, _P]),
+    "cot_lookahead_tick": (_I, [_P, _P, _I, _I, _P]),
+    "cot_lookahead_step": (_I, [_P, _P, _P, ctypes.c_int64, ctypes.c_double, _P, _I, _P]),
     "cot_conv1x1_workspace": (ctypes.c_int64, [_I, _I, _I, _I, _I]),
     "cot_conv1x1_forward": (_I, [_P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "cot_conv1x1_backward_data": (_I, [_P, _P, _P, _P, _I, _I, _P, _I, _I, _I, _I, _I, _P]),

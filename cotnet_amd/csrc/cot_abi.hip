@@ -219,7 +219,7 @@ static int check_align16(std::initializer_list<const void*> ptrs) {
     return COT_OK;
 }
 
-// What the flat step entry points (cot_sgd_step, _lr, _clip, cot_adamw_step) share: the bucket pointers (`master` may be NULL, the
+// What the flat step entry points (cot_sgd_step, _lr, _clip, cot_adamw_step, cot_lookahead_step) share: the bucket pointers (`master` may be NULL, the
 // others not) are 16-byte aligned, n > 0, and each optional word or block in device memory (`words`, named for the message) is 4-byte
 // aligned.  What an entry point REQUIRES of its words, and its value ranges, it checks itself.
 struct DevWord {
@@ -444,6 +444,24 @@ int cot_adamw_step(void* param, void* master, void* exp_avg, void* exp_avg_sq, c
     return adamw_flat(param, master, exp_avg, exp_avg_sq, grad, n, lr, (const float*)lr_dev, (const cot_adam_state*)adam_state,
                       (const cot_clip_state*)clip_state, beta1, beta2, eps, weight_decay, grad_scale, decoupled, param_dtype, grad_dtype,
                       (hipStream_t)stream);
+}
+
+int cot_lookahead_tick(void* lookahead_state, const void* clip_state, int k, int force, void* stream) {
+    if (!lookahead_state) return set_error(COT_ERR_INVALID_ARG, "NULL lookahead_state (the device block the step count and the decision live in)");
+    if ((uintptr_t)lookahead_state % 4 != 0)
+        return set_error(COT_ERR_INVALID_ARG, "lookahead_state %p is not 4-byte aligned", lookahead_state);
+    if ((uintptr_t)clip_state % 4 != 0) return set_error(COT_ERR_INVALID_ARG, "clip_state %p is not 4-byte aligned", clip_state);
+    if (k < 1) return set_error(COT_ERR_INVALID_ARG, "lookahead k %d is not >= 1", k);
+    return lookahead_tick(lookahead_state, clip_state, k, force, (hipStream_t)stream);
+}
+
+int cot_lookahead_step(void* param, void* master, void* slow, int64_t n, double alpha, const void* lookahead_state, int param_dtype,
+                       void* stream) {
+    if (!lookahead_state) return set_error(COT_ERR_INVALID_ARG, "NULL lookahead_state (the device block the decision is read from)");
+    int rc = check_flat_step({param, slow}, master, n, {{"lookahead_state", lookahead_state}});
+    if (rc) return rc;
+    if (!(alpha >= 0.0 && alpha <= 1.0)) return set_error(COT_ERR_INVALID_ARG, "lookahead alpha %g outside [0, 1]", alpha);
+    return lookahead_flat(param, master, slow, n, alpha, (const cot_lookahead_state*)lookahead_state, param_dtype, (hipStream_t)stream);
 }
 
 int cot_ema_step(void* ema, const void* src, int64_t n, float decay, int src_dtype, void* stream) {

@@ -63,6 +63,11 @@ int adamw_flat(void* param, void* master, void* exp_avg, void* exp_avg_sq, const
                const cot_adam_state* st, const cot_clip_state* clip, double beta1, double beta2, float eps, float wd, float gscale, int decoupled,
                int param_dtype, int grad_dtype, hipStream_t s);
 
+// ---- lookahead.hip: Lookahead's slow weights over flat buffers behind one decision in device memory (arguments validated by cot_abi.hip)
+int lookahead_tick(void* state, const void* clip_state, int k, int force, hipStream_t s);
+int lookahead_flat(void* param, void* master, void* slow, int64_t n, double alpha, const cot_lookahead_state* st, int param_dtype,
+                   hipStream_t s);
+
 // ---- grad_clip.hip: the gradients' global norm -> clip coefficient / skip flag in a block in device memory (read by sgd_flat_clip)
 int grad_sumsq(const void* grad, int64_t n, int grad_dtype, float* partials, hipStream_t s);
 int grad_clip_finish(const float* partials, int64_t nparts, float max_norm, void* state, hipStream_t s);

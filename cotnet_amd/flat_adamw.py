@@ -32,12 +32,14 @@ def _as_int(step):
 class FlatAdamW(FlatSGD):
     def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, decoupled=True, bucket_mb=10.0,
                  process_group=None, broadcast_params=True, ema_decay=None, force_collectives=False, grad_dtype=None, device_lr=False,
-                 clip_grad=None, clip_mode="norm", skip_nonfinite=False, agc=None, agc_eps=1e-3):
+                 clip_grad=None, clip_mode="norm", skip_nonfinite=False, agc=None, agc_eps=1e-3, lookahead_k=None, lookahead_alpha=0.5):
         """lr, betas, eps, weight_decay: torch.optim.AdamW's (the reference's optim/adamw.py:36-37); weight decay on the `decay` group
         only, as in FlatSGD.
         decoupled: True: AdamW -- p *= 1 - lr * weight_decay in front of the step (adamw.py:72).  False: torch.optim.Adam's L2 form --
         weight_decay * p joins the gradient (FlatAdam).
-        Every other keyword is FlatSGD's, with FlatSGD's meaning; with device_lr=True the rate is read by `cot_adamw_step` when it runs."""
+        Every other keyword is FlatSGD's, with FlatSGD's meaning; with device_lr=True the rate is read by `cot_adamw_step` when it runs;
+        with lookahead_k the moments are never touched by a sync and the Adam step count runs on (the reference's `lookahead_adam`,
+        `lookahead_adamw`)."""
         name = type(self).__name__
         b1, b2 = (float(b) for b in betas)
         if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
@@ -49,7 +51,7 @@ class FlatAdamW(FlatSGD):
         self.betas, self.eps, self.decoupled = (b1, b2), float(eps), bool(decoupled)
         self._captured_hp = None  # (betas, eps, weight_decay) a HIP-graph capture of step() baked into its launches
         self._setup(model, lr, weight_decay, bucket_mb, process_group, broadcast_params, ema_decay, force_collectives, grad_dtype,
-                    device_lr, clip_grad, clip_mode, skip_nonfinite, agc, agc_eps)
+                    device_lr, clip_grad, clip_mode, skip_nonfinite, agc, agc_eps, lookahead_k, lookahead_alpha)
         self.adam_state = torch.zeros(8, dtype=torch.int32, device=self._device())  # cot_adam_state: step, bc1, sqrt_bc2, refused, 4 reserved
 
     def _bucket_state(self, b):
@@ -99,7 +101,7 @@ class FlatAdamW(FlatSGD):
                 state[i] = {"step": words[0], "exp_avg": m[p].detach().clone(), "exp_avg_sq": v[p].detach().clone()}
         extra = dict(format=self.STATE_FORMAT, device_lr=self.lr_dev is not None, decoupled=self.decoupled, clip_state=self._clip_words(),
                      refused=words[3])
-        return {"state": state, "param_groups": groups, "cotnet_amd": extra}
+        return self._lookahead_saved({"state": state, "param_groups": groups, "cotnet_amd": extra})
 
     def load_state_dict(self, d):
         """the inverse of state_dict(), in place.  Parameters are matched by group and position.  Accepted: `step` as an int or a 0-d
@@ -157,10 +159,12 @@ class FlatAdamW(FlatSGD):
             raise ValueError(f"{name}.load_state_dict(): step() was captured into a HIP graph with (betas, eps, weight_decay) = "
                              f"{self._captured_hp}, which travel by value and stay in its replays; the checkpoint says {new_hp} -- build the "
                              "optimizer with the checkpoint's values before capturing")
+        lookahead = self._lookahead_plan(d)
         self.set_lr(hp["lr"])
         self.betas, self.eps, self.weight_decay = new_hp
         m, v = self._slots("exp_avg"), self._slots("exp_avg_sq")
         with torch.no_grad():
+            self._lookahead_load(lookahead)
             for p, (em, ev) in values.items():
                 m[p].zero_() if em is None else m[p].copy_(em)
                 v[p].zero_() if ev is None else v[p].copy_(ev)

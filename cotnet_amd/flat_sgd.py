@@ -69,7 +69,7 @@ def _agc_unit_table(params, offs, n):
 class FlatSGD:
     def __init__(self, model, lr, momentum=0.9, weight_decay=0.0, nesterov=True, bucket_mb=10.0, process_group=None,
                  broadcast_params=True, ema_decay=None, force_collectives=False, grad_dtype=None, device_lr=False, clip_grad=None,
-                 clip_mode="norm", skip_nonfinite=False, agc=None, agc_eps=1e-3):
+                 clip_mode="norm", skip_nonfinite=False, agc=None, agc_eps=1e-3, lookahead_k=None, lookahead_alpha=0.5):
         """bucket_mb: size of the flat gradient buckets.  10 MiB cuts CoTNet-50's 44 MB of bf16 weight gradients into five
         buckets in the order backward produces them (classifier and stage 4 first, the stem last), so four all-reduces are
         already on the communication stream when backward ends and only the last, small one is exposed; round 2's 48 MiB
@@ -121,10 +121,24 @@ class FlatSGD:
         (cotnet.py:225-226) is a 1-D unit with wn = 0: it is clipped against agc_eps * agc, which is the reference's behaviour and
         is kept.  Not together with clip_grad: the reference runs one mode per step.  `agc_stats()` and `agc_coefficients()` read
         the last step's coefficients.
-        agc_eps: the floor of the weight norm (the reference's eps = 1e-3)."""
+        agc_eps: the floor of the weight norm (the reference's eps = 1e-3).
+        lookahead_k: Lookahead (the reference's `lookahead_` prefix, optim/optim_factory.py:116-118 -> optim/lookahead.py, whose
+        defaults are k = 6 and alpha = 0.5); None (default): off -- nothing is allocated and the launches are the ones of before.
+        An int >= 1: every k-th ACCEPTED step the fp32 weights are pulled back to slow weights, slow += alpha * (fast - slow);
+        fast = slow (lookahead.py:29-39).  The slow weights (`"slow"` in each bucket's state, fp32, the bucket's length) and
+        `self.lookahead_state` (int32[8] = cot_lookahead_state) are allocated here once and keep their addresses.  step() issues one
+        `cot_lookahead_tick` behind the clip launches and the update rule's own tick -- it counts the step in device memory and
+        decides -- and one `cot_lookahead_step` per bucket between the bucket's update kernel and its EMA launch (csrc/lookahead.hip),
+        so the EMA averages the weights after the sync, as the reference's loop does, and one HIP-graph capture serves sync and
+        non-sync steps alike; k and alpha travel by value.  As in the reference the slow weights are created at the FIRST sync as a
+        copy of the fast ones (lookahead.py:34-36): step k moves no weight, step 2k is the first to interpolate.  Momentum and
+        moments are never touched.  A step the non-finite guard skips is not counted (the block's `refused` counts it), as a step
+        the reference's scaler skips never reaches optimizer.step() (train.py:276-277).  `sync_lookahead()` is the reference's
+        end-of-epoch call (train.py:295-296), `lookahead_stats()` reads the block.
+        lookahead_alpha: the slow weights' rate, in [0, 1]."""
         self.momentum, self.nesterov = float(momentum), nesterov
         self._setup(model, lr, weight_decay, bucket_mb, process_group, broadcast_params, ema_decay, force_collectives, grad_dtype,
-                    device_lr, clip_grad, clip_mode, skip_nonfinite, agc, agc_eps)
+                    device_lr, clip_grad, clip_mode, skip_nonfinite, agc, agc_eps, lookahead_k, lookahead_alpha)
 
     def _bucket_state(self, b):
         """what the update rule keeps per bucket next to the master: fp32 arrays of the bucket's length, allocated once"""
@@ -140,10 +154,13 @@ class FlatSGD:
         return self.reducer.buckets[0].pflat.device if self.reducer.buckets else next(self.model.parameters()).device
 
     def _setup(self, model, lr, weight_decay, bucket_mb, process_group, broadcast_params, ema_decay, force_collectives, grad_dtype,
-               device_lr, clip_grad, clip_mode, skip_nonfinite, agc, agc_eps):
+               device_lr, clip_grad, clip_mode, skip_nonfinite, agc, agc_eps, lookahead_k=None, lookahead_alpha=0.5):
         """everything of the constructor that does not depend on the update rule (FlatAdamW, flat_adamw.py, shares it): the keywords'
-        checks, the buckets and masters, the device-resident rate, the clip block, the AGC tables, the averages"""
+        checks, the buckets and masters, the device-resident rate, the clip block, the AGC tables, the averages, Lookahead's slow
+        weights and block"""
         name = type(self).__name__
+        self.lookahead_k, self.lookahead_alpha = self._lookahead_checked(lookahead_k, lookahead_alpha, f"{name}(")
+        self._captured_lookahead = None  # (k, alpha) a HIP-graph capture of step() baked into its lookahead launches
         if clip_mode != "norm":
             raise ValueError(f"{name}(clip_mode={clip_mode!r}): only 'norm' (clipping by the global L2 norm) is a value of clip_mode; "
                              "the reference's other modes 'value' and 'agc' are not values of clip_mode: adaptive clipping is "
@@ -171,7 +188,12 @@ class FlatSGD:
             st = {"master": master, **self._bucket_state(b)}
             if self.ema_decay is not None:
                 st["ema"] = self._weights(b, st).float().clone()
+            if self.lookahead_k is not None:  # zeros, not the weights: the slow weights are born at the first sync (lookahead.py:34-36)
+                st["slow"] = torch.zeros(b.pflat.numel(), dtype=torch.float32, device=b.pflat.device)
             self.state.append(st)
+        self.lookahead_state = None
+        if self.lookahead_k is not None:
+            self.lookahead_state = torch.zeros(8, dtype=torch.int32, device=self._device())  # cot_lookahead_state
         self.lr_dev = None
         if device_lr:
             self.lr_dev = torch.full((1,), self.lr, dtype=torch.float32, device=self._device())
@@ -230,8 +252,11 @@ class FlatSGD:
             L.cot_grad_clip_finish(self._clip_parts.data_ptr(), self._clip_parts.numel(),
                                    self.clip_grad if self.clip_grad is not None else float("inf"), self.clip_state.data_ptr(), stream)
         update = self._bucket_update(L, clipped, stream)
+        sync = self._lookahead_update(L, clipped, stream)
         for b, st in zip(self.reducer.buckets, self.state):
             update(b, st, self.weight_decay if b.key == "decay" else 0.0)
+            if sync is not None:  # in front of the EMA launch: the average follows the weights after the sync
+                sync(b, st)
             if self.ema_decay is not None:
                 src = self._weights(b, st)
                 L.cot_ema_step(st["ema"].data_ptr(), src.data_ptr(), src.numel(),
@@ -261,6 +286,152 @@ class FlatSGD:
                 b.pflat.numel(), *rate, self.momentum, wd, 1.0, 1 if self.nesterov else 0,
                 _lib.dtype_code(b.pflat.dtype), _lib.dtype_code(self.reducer.reduced(b).dtype), stream)
         return update
+
+    # ---- Lookahead (the reference's optim/lookahead.py) on the device: csrc/lookahead.hip
+
+    @staticmethod
+    def _lookahead_checked(k, alpha, where):
+        """(k, alpha) as stored -- (None, alpha) = off; the reference's checks (lookahead.py:14-17)"""
+        alpha = float(alpha)
+        if not 0.0 <= alpha <= 1.0:  # (a NaN fails it too)
+            raise ValueError(f"{where}lookahead_alpha={alpha!r}): the slow update rate must lie in [0, 1]")
+        if k is None:
+            return None, alpha
+        if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+            raise ValueError(f"{where}lookahead_k={k!r}): the number of lookahead steps must be an int >= 1 (None: no Lookahead)")
+        return k, alpha
+
+    def _lookahead_update(self, L, clipped, stream, force=0):
+        """Lookahead's launches: called once per step() behind `_bucket_update` (whose tick, if it has one, is issued first) -- ONE
+        cot_lookahead_tick, which reads the clip block's skip -- and returns sync(bucket, its state) = one cot_lookahead_step, which
+        step() calls per bucket between the update kernel and the bucket's EMA launch.  None with Lookahead off."""
+        if self.lookahead_k is None or not self.reducer.buckets:
+            return None
+        block = self.lookahead_state.data_ptr()
+        k, alpha = self.lookahead_k, self.lookahead_alpha
+        if _lib.capturing():  # k and alpha travel by value: every replay of this capture syncs with them
+            self._captured_lookahead = (k, alpha)
+        L.cot_lookahead_tick(block, self.clip_state.data_ptr() if clipped else None, k, force, stream)
+
+        def sync(b, st):
+            L.cot_lookahead_step(b.pflat.data_ptr(), st["master"].data_ptr() if st["master"] is not None else None, st["slow"].data_ptr(),
+                                 b.pflat.numel(), alpha, block, _lib.dtype_code(b.pflat.dtype), stream)
+        return sync
+
+    def sync_lookahead(self):
+        """the reference's end-of-epoch call (lookahead.py:41-43, train.py:295-296): the slow weights are updated and the fast weights
+        set to them NOW, without counting a step -- one forced cot_lookahead_tick, one cot_lookahead_step per bucket.  Unborn slow
+        weights are adopted and no weight moves, as in the reference.  It finishes no all-reduce, reads no gradient and not the clip
+        block, and leaves momentum, moments and the EMA alone.  Refused while capturing.  Built without lookahead_k it returns at
+        once: the reference guards its call with hasattr, and here the attribute is always there."""
+        if self.lookahead_k is None:
+            return
+        self._not_while_capturing("sync_lookahead()")
+        sync = self._lookahead_update(_lib.api(), False, _lib.stream(), force=1)
+        if sync is None:
+            return
+        for b, st in zip(self.reducer.buckets, self.state):
+            sync(b, st)
+        from . import cot_layer_fused
+        cot_layer_fused.after_optimizer_step(self.reducer.buckets[0].pflat.device)
+
+    def lookahead_stats(self):
+        """ONE host read of the block: dict(step, born, syncs, refused) -- accepted steps, whether the slow weights hold something, the
+        syncs carried out, the steps the guard skipped.  Synchronises with the device; refused while capturing."""
+        if self.lookahead_state is None:
+            raise RuntimeError(f"{type(self).__name__}.lookahead_stats(): built without lookahead_k")
+        self._not_while_capturing("lookahead_stats()")
+        w = self.lookahead_state.cpu().tolist()
+        return dict(step=w[0], born=w[2], syncs=w[3], refused=w[4])
+
+    def _lookahead_saved(self, d):
+        """state_dict()'s `d` with Lookahead's part: the reference's top-level order (lookahead.py:62-66) state, slow_state,
+        param_groups, then cotnet_amd; slow_state[idx] = {'slow_buffer': fp32 clone} once born, {} before; lookahead_alpha, _k and
+        _step in every group (lookahead.py:18-27); the block's eight words under cotnet_amd['lookahead'].  Off: `d` as it is."""
+        if self.lookahead_k is None:
+            return d
+        words = self.lookahead_state.cpu().tolist()
+        slow = self._slots("slow")
+        members = [p for g in self._groups() for _, p in g]
+        slow_state = {i: ({"slow_buffer": slow[p].detach().clone()} if words[2] else {}) for i, p in enumerate(members)}
+        groups = [dict(g, lookahead_alpha=self.lookahead_alpha, lookahead_k=self.lookahead_k, lookahead_step=words[0])
+                  for g in d["param_groups"]]
+        return {"state": d["state"], "slow_state": slow_state, "param_groups": groups, "cotnet_amd": dict(d["cotnet_amd"], lookahead=words)}
+
+    def _lookahead_plan(self, d):
+        """load_state_dict()'s checks of Lookahead's part, all before anything is written: returns what `_lookahead_load` writes.
+        (d['param_groups'] has been checked against this optimizer's groups.)"""
+        name = type(self).__name__
+        extra = d.get("cotnet_amd") or {}
+        if self.lookahead_k is None:
+            if "slow_state" in d or extra.get("lookahead") is not None:
+                raise ValueError(f"{name}.load_state_dict(): the checkpoint carries Lookahead's slow weights and this optimizer was built "
+                                 "without the keyword lookahead_k -- they would be dropped silently; build it with lookahead_k (and "
+                                 "lookahead_alpha) as the checkpoint's groups say")
+            return None
+        theirs = d["param_groups"]
+        said = {}
+        for key in ("lookahead_step", "lookahead_k", "lookahead_alpha"):
+            values = {g[key] for g in theirs if key in g}
+            if len(values) > 1:
+                raise ValueError(f"{name}.load_state_dict(): the groups' {key} are {sorted(values)}; this optimizer keeps ONE count, one k "
+                                 "and one alpha in device memory for all of them")
+            said[key] = values.pop() if values else None
+        k, alpha = self._lookahead_checked(self.lookahead_k if said["lookahead_k"] is None else said["lookahead_k"],
+                                           self.lookahead_alpha if said["lookahead_alpha"] is None else said["lookahead_alpha"],
+                                           f"{name}.load_state_dict(")
+        if self._captured_lookahead is not None and (k, alpha) != self._captured_lookahead:
+            raise ValueError(f"{name}.load_state_dict(): step() was captured into a HIP graph with (lookahead_k, lookahead_alpha) = "
+                             f"{self._captured_lookahead}, which travel by value and stay in its replays; the checkpoint says {(k, alpha)} "
+                             "-- build the optimizer with the checkpoint's values before capturing")
+        step = int(said["lookahead_step"] or 0)
+        if step < 0:
+            raise ValueError(f"{name}.load_state_dict(): negative lookahead_step {step}")
+        buffers = None
+        if "slow_state" in d:
+            slow_state = d["slow_state"]
+            indices = [i for g in theirs for i in g["params"]]
+            if sorted(map(str, slow_state)) != sorted(map(str, indices)):
+                raise ValueError(f"{name}.load_state_dict(): slow_state is keyed by {sorted(map(str, slow_state))[:4]}..., the groups list "
+                                 f"the indices {indices}; a slow_state the reference's Lookahead wrote is keyed by id(tensor) of ITS "
+                                 "process, which cannot be matched to any parameter here -- only a slow_state keyed by the groups' "
+                                 "indices (as state_dict() of this package writes it) is read")
+            buffers = {}
+            for members, g in zip(self._groups(), theirs):
+                for (pname, p), idx in zip(members, g["params"]):
+                    s = slow_state.get(idx)
+                    buf = (s if s is not None else slow_state.get(str(idx)) or {}).get("slow_buffer")
+                    if buf is not None and tuple(buf.shape) != tuple(p.shape):
+                        raise ValueError(f"{name}.load_state_dict(): slow_buffer of index {idx} has shape {tuple(buf.shape)}, parameter "
+                                         f"'{pname}' at that place has {tuple(p.shape)}")
+                    buffers[p] = buf
+            held = [b is not None for b in buffers.values()]
+            if any(held) and not all(held):
+                raise ValueError(f"{name}.load_state_dict(): slow_state holds a slow_buffer for some indices and none for others; this "
+                                 "optimizer's slow weights are born together, at the first sync")
+            if not any(held):
+                buffers = None
+        words = extra.get("lookahead")
+        if words is not None:
+            words = [int(w) for w in words]
+            if len(words) != 8 or bool(words[2]) != (buffers is not None):
+                raise ValueError(f"{name}.load_state_dict(): cotnet_amd['lookahead'] = {words} is not a block of eight words whose `born` "
+                                 f"agrees with slow_state ({'buffers' if buffers is not None else 'no buffers'})")
+        else:
+            words = [step, 0, 1 if buffers is not None else 0, 0, 0, 0, 0, 0]
+        return dict(k=k, alpha=alpha, words=words, buffers=buffers)
+
+    def _lookahead_load(self, plan):
+        """write what `_lookahead_plan` returned, in place (inside torch.no_grad())"""
+        if plan is None:
+            return
+        self.lookahead_k, self.lookahead_alpha = plan["k"], plan["alpha"]
+        slow = self._slots("slow")
+        for st in self.state:
+            st["slow"].zero_()  # (padding, and everything where the checkpoint's slow weights are unborn)
+        for p, buf in (plan["buffers"] or {}).items():
+            slow[p].copy_(buf)
+        self.lookahead_state.copy_(torch.tensor(plan["words"], dtype=torch.int32))
 
     def clip_stats(self):
         """ONE host read of the clip block: dict(total_norm, scale, skip, steps, clipped, skipped) -- the last step's norm, coefficient
@@ -493,7 +664,8 @@ class FlatSGD:
         state[idx] = {'momentum_buffer': fp32 tensor of the parameter's shape}, the hyper-parameters (lr, momentum, dampening 0,
         weight_decay, nesterov) in the groups -- torch.optim.SGD over the same groups of an fp32 twin loads its 'state' and
         'param_groups'.  One more top-level key, 'cotnet_amd', holds what that layout cannot: format, device_lr (whether the rate lives
-        on the device) and clip_state (the eight words of the clip block: last coefficient and norm, the counters; None without one)."""
+        on the device) and clip_state (the eight words of the clip block: last coefficient and norm, the counters; None without one).
+        Built with lookahead_k, Lookahead's part joins in the reference's layout (`_lookahead_saved`)."""
         self._not_while_capturing("state_dict()")
         momentum, groups, state, at = self._slots("mom"), [], {}, 0
         for members, wd in zip(self._groups(), (0.0, self.weight_decay)):
@@ -503,13 +675,15 @@ class FlatSGD:
             for i, (_, p) in zip(idx, members):
                 state[i] = {"momentum_buffer": momentum[p].detach().clone()}
         extra = dict(format=self.STATE_FORMAT, device_lr=self.lr_dev is not None, clip_state=self._clip_words())
-        return {"state": state, "param_groups": groups, "cotnet_amd": extra}
+        return self._lookahead_saved({"state": state, "param_groups": groups, "cotnet_amd": extra})
 
     def load_state_dict(self, d):
         """the inverse of state_dict().  Parameters are matched by group ([no_decay, decay]) and position, their shapes checked, all
         before anything is written.  A dict without 'cotnet_amd' is accepted (a checkpoint the reference wrote): hyper-parameter keys a
         group lacks keep the constructor's values, an index without a momentum_buffer (torch before its first step) gives zero momentum
-        -- with dampening 0 the same next step.  lr goes through set_lr (its rules hold)."""
+        -- with dampening 0 the same next step.  lr goes through set_lr (its rules hold).  Lookahead's part: `_lookahead_plan` -- a
+        dict without slow_state loads unborn at the groups' lookahead_step; slow weights offered to an optimizer built without
+        lookahead_k are refused, not dropped."""
         self._not_while_capturing("load_state_dict()")
         ours, theirs = self._groups(), d["param_groups"]
         if len(theirs) != 2 or [len(g["params"]) for g in theirs] != [len(g) for g in ours]:
@@ -535,10 +709,12 @@ class FlatSGD:
         extra = d.get("cotnet_amd") or {}
         if extra and extra.get("format") != self.STATE_FORMAT:
             raise ValueError(f"FlatSGD.load_state_dict(): 'cotnet_amd' format {extra.get('format')!r}, this build reads {self.STATE_FORMAT}")
+        lookahead = self._lookahead_plan(d)
         self.set_lr(hp["lr"])
         self.momentum, self.weight_decay, self.nesterov = float(hp["momentum"]), float(hp["weight_decay"]), bool(hp["nesterov"])
         mom = self._slots("mom")
         with torch.no_grad():
+            self._lookahead_load(lookahead)
             for p, buf in values.items():
                 mom[p].zero_() if buf is None else mom[p].copy_(buf)
             words = extra.get("clip_state")

@@ -625,6 +625,47 @@ int cot_adamw_step(void* param, void* master, void* exp_avg, void* exp_avg_sq, c
                    const void* adam_state, const void* clip_state, double beta1, double beta2, float eps, float weight_decay,
                    float grad_scale, int decoupled, int param_dtype, int grad_dtype, void* stream);
 
+/* ---- Lookahead's slow weights over a flat parameter bucket (reference: the `lookahead_` prefix of optim/optim_factory.py:116-118 ->
+ * optim/lookahead.py:29-52: a step count per group on the host, and every k-th step a subtraction, an add_ and a copy_ per parameter
+ * tensor).  Here: one launch per bucket, and the step count and the step's decision live in ONE 32-byte block in device memory, so
+ * that a HIP graph that recorded the step serves sync and non-sync steps alike:
+ *   1. cot_lookahead_tick   once per step, behind the clip launches: counts the step and decides 0 nothing / 1 adopt / 2 interpolate
+ *   2. cot_lookahead_step   per bucket, behind the bucket's update kernel: reads the decision when it runs and carries it out
+ *
+ * The block (4-byte aligned, device memory; the caller zeroes it once; cot_lookahead_tick is its only writer on the device,
+ * cot_lookahead_step only reads `action`; successive calls are ordered by the stream). */
+typedef struct cot_lookahead_state {
+    int32_t step;        /* accepted steps: cot_lookahead_tick adds 1 unless the step is skipped or the tick is forced (lookahead.py:49) */
+    int32_t action;      /* the last tick's decision, read by cot_lookahead_step: 0 nothing, 1 adopt, 2 interpolate */
+    int32_t born;        /* 0 or 1: the slow weights hold something (the reference's lazily created slow_buffer, lookahead.py:34-36) */
+    int32_t syncs;       /* how many adopt or interpolate decisions were taken */
+    int32_t refused;     /* ticks that found clip_state->skip != 0 and counted nothing */
+    int32_t reserved[3]; /* never written by a kernel: they stay as the caller left them (0) */
+} cot_lookahead_state;
+
+/* One workgroup, lane 0's plain read-modify-write of the block.  clip_state given (cot_clip_state, as cot_grad_clip_finish left it) and
+ * its skip != 0: refused += 1 and action = 0 (written, so that the last step's decision is never carried out again), nothing else.
+ * Otherwise, force == 0 (a step, lookahead.py:45-52): step += 1, action = step % k != 0 ? 0 : (born ? 2 : 1); force != 0
+ * (sync_lookahead, lookahead.py:41-43): step stays, action = born ? 2 : 1.  Whenever action != 0: born = 1, syncs += 1.  The first
+ * sync therefore only adopts -- the reference creates its slow buffer there as a copy of the fast weights (lookahead.py:34-36), and
+ * the interpolation of equal weights moves nothing.
+ * NULL or misaligned (4 bytes) lookahead_state, misaligned clip_state, k < 1: COT_ERR_INVALID_ARG before any device work. */
+int cot_lookahead_tick(void* lookahead_state, const void* clip_state, int k, int force, void* stream);
+
+/* One bucket's sync.  param / master / param_dtype as for cot_sgd_step (COT_BF16 needs the fp32 `master`, COT_F32 takes
+ * master == NULL); slow is fp32, n elements.  `fast` below is the master, or the fp32 parameters where there is none.  Every lane
+ * reads lookahead_state->action once in front of its loop:
+ *     0   nothing is written
+ *     1   slow = fast; nothing else is written
+ *     2   per element, in fp32 (hipcc may contract the multiply and the add into one FMA; with alpha = 0.5 the product is exact):
+ *             d = fast - slow;  s = slow + alpha * d           alpha = (float) of the double given       (lookahead.py:38)
+ *         slow = s, fast = s, and with a master the working copy = s rounded to param_dtype              (lookahead.py:39)
+ * NULL param / slow / lookahead_state, an array not 16-byte or lookahead_state not 4-byte aligned, n < 1, alpha outside [0, 1] or not
+ * finite: COT_ERR_INVALID_ARG; a dtype / master combination cot_sgd_step does not take: COT_ERR_UNSUPPORTED -- reported through
+ * cot_last_error() before any device work. */
+int cot_lookahead_step(void* param, void* master, void* slow, int64_t n, double alpha, const void* lookahead_state, int param_dtype,
+                       void* stream);
+
 /* ---- exponential moving average of the weights over a flat buffer (replaces the per-tensor
  * `ema = decay*ema + (1-decay)*model` of ModelEmaV2._update, utils/model_ema.py:45-53):  ema fp32 [n], src the fp32
  * master copy / fp32 parameters (COT_F32) or bf16 parameters (COT_BF16). */
