@@ -922,7 +922,7 @@ static int lr_check(const cot_agg_geom* g, int dtype) {
     if (rc) return rc;
     if (dtype != COT_F32 && dtype != COT_BF16) return set_error(COT_ERR_UNSUPPORTED, "local relation: fp32 / bf16 storage only");
     if (!lr_covers(*g))
-        return set_error(COT_ERR_UNSUPPORTED, "local relation: geometry not covered (3x3 / stride 1 / pad 1 / dilation 1, heads 1, "
+        return set_error(COT_ERR_UNSUPPORTED, "local relation: geometry not covered (3x3 pad 1 or 7x7 pad 3, stride 1, dilation 1, heads 1, "
                                               "C %% 8 == 0, wC == C / 8, a tile that fits LDS)");
     return COT_OK;
 }

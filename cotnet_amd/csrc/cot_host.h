@@ -251,6 +251,15 @@ template <typename T>
 int lr_backward(const T* gout, const T* q, const T* k, const T* v, const float* pos, const T* probs, T* gq, T* gk, T* gv, float* gpos,
                 void* workspace, const cot_agg_geom& g, hipStream_t s);
 
+// ---- local_relation7.hip: the 7x7 window of the same operation (lr_covers / lr_workspace_bytes / lr_forward / lr_backward route to it)
+const char* last_kernel_lr7();
+bool lr7_covers(const cot_agg_geom& g);
+int64_t lr7_workspace_bytes(const cot_agg_geom& g, size_t esize);
+template <typename T> int lr7_forward(const T* q, const T* k, const T* v, const float* pos, T* out, T* probs, const cot_agg_geom& g, hipStream_t s);
+template <typename T>
+int lr7_backward(const T* gout, const T* q, const T* k, const T* v, const float* pos, const T* probs, T* gq, T* gk, T* gv, float* gpos,
+                 void* workspace, const cot_agg_geom& g, hipStream_t s);
+
 // ---- mix_loss.hip: mixup / CutMix input pipeline and soft-target cross entropy
 int mix_normalize(const void* x, void* y, const float* mean, const float* stdv, const void* params, int N, int C, int H, int W, int dtype,
                   hipStream_t s);

@@ -18,6 +18,7 @@
 //   lr_gpos_reduce  the partials of each (head, j, t) summed in a fixed order into gpos[C][9].
 //   lr_softmax_bwd  gv and gL for the geometries the LDS-staged softmax aggregation backward (agg_nchw.hip) does not take
 //                   (its 16-byte plane-stride rule); direct loads, one thread per (n, g, pixel).
+// The 7x7 window (K = 7, T = 49, pad 3) has its own plan and kernels in local_relation7.hip; the host functions below route to it.
 #include "cot_common.h"
 #include "cot_host.h"
 
@@ -290,18 +291,25 @@ static inline int lr_vec(int W) { return W % 4 == 0 ? 4 : (W % 2 == 0 ? 2 : 1); 
 static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 bool lr_covers(const cot_agg_geom& g) {
+    if (g.kh == 7 && g.kw == 7) return lr7_covers(g);  // the 7x7 window: local_relation7.hip, its own plan
     return g.kh == 3 && g.kw == 3 && g.sh == 1 && g.sw == 1 && g.ph == 1 && g.pw == 1 && g.dh == 1 && g.dw == 1 && g.heads == 1 &&
            g.C % 8 == 0 && g.wC * 8 == g.C && lr_plan(g.H, g.W, 25).ok && (int64_t)g.N * g.wC * lr_plan(g.H, g.W, 25).tiles < (1LL << 31);
 }
 
 // [glogits: N G 9 HW elements, 256-byte aligned][partials: G N tiles 72 floats]
 int64_t lr_workspace_bytes(const cot_agg_geom& g, size_t esize) {
+    if (g.kh == 7) return lr7_workspace_bytes(g, esize);
     const LrPlan p = lr_plan(g.H, g.W, 25);
     return (int64_t)(align256((size_t)g.N * g.wC * 9 * g.H * g.W * esize) + (size_t)g.wC * g.N * p.tiles * 72 * sizeof(float));
 }
 
 template <typename T>
 int lr_forward(const T* q, const T* k, const T* v, const float* pos, T* out, T* probs, const cot_agg_geom& g, hipStream_t s) {
+    if (g.kh == 7) {
+        const int rc = lr7_forward<T>(q, k, v, pos, out, probs, g, s);
+        g_lr_kernel = last_kernel_lr7();
+        return rc;
+    }
     const LrPlan p = lr_plan(g.H, g.W, 16);
     const int G = g.wC;
     const dim3 grid((unsigned)((int64_t)g.N * G * p.tiles)), block(p.nthreads);
@@ -317,6 +325,11 @@ int lr_forward(const T* q, const T* k, const T* v, const float* pos, T* out, T* 
 template <typename T>
 int lr_backward(const T* gout, const T* q, const T* k, const T* v, const float* pos, const T* probs, T* gq, T* gk, T* gv,
                 float* gpos, void* workspace, const cot_agg_geom& g, hipStream_t s) {
+    if (g.kh == 7) {
+        const int rc = lr7_backward<T>(gout, q, k, v, pos, probs, gq, gk, gv, gpos, workspace, g, s);
+        g_lr_kernel = last_kernel_lr7();
+        return rc;
+    }
     const LrPlan p = lr_plan(g.H, g.W, 25);
     const int G = g.wC;
     const int64_t HW = (int64_t)g.H * g.W;

@@ -5,12 +5,13 @@
 
 with G = C/8 heads of 8 consecutive q/k channels and the weights of channel c taken from head c mod G (:89-96).  `pos` is
 formed here in torch, so pos_h / pos_w stay ordinary differentiable parameters (kept in fp32 by to_mixed_bf16); the fused
-op takes it as fp32 [C][9] and returns its gradient in fp32.
+op takes it as fp32 [C][k k] and returns its gradient in fp32.
 
-Route: the fused autograd Function for CUDA fp32 / bf16 tensors at k = 3 whose geometry the library covers (C % 8 == 0, a tile
-that fits LDS).  Everything else -- CPU tensors, fp64, k != 3 -- takes `local_relation_reference`, the reference's
-composition (unfold, + pos, product, head sum, aggregation_zeropad_softmax).  A CUDA fp32 / bf16 tensor at k = 3 that the
-kernels do not cover is counted as a module fallback (COT_STRICT_DISPATCH=1 makes it an error).
+Route: the fused autograd Function for CUDA fp32 / bf16 tensors at k = 3 (the reference's two builders) or k = 7 (LR-Net's own
+window, csrc/local_relation7.hip) whose geometry the library covers (C % 8 == 0, a tile that fits LDS).  Everything else -- CPU
+tensors, fp64, any other window -- takes `local_relation_reference`, the reference's composition (unfold, + pos, product, head
+sum, aggregation_zeropad_softmax).  A CUDA fp32 / bf16 tensor at k = 3 or 7 that the kernels do not cover is counted as a module
+fallback (COT_STRICT_DISPATCH=1 makes it an error).
 """
 import ctypes
 
@@ -23,39 +24,40 @@ from ._lib import ptr as _ptr, stream as _stream
 from .aggregation_zeropad import _aligned, aggregation_zeropad_softmax
 
 _DT = (torch.float32, torch.bfloat16)
-_WS = _lib.register_cache({})  # (N, C, H, W, dtype) -> workspace bytes (< 0: geometry off the fused kernels)
+_FUSED_WINDOWS = (3, 7)
+_WS = _lib.register_cache({})  # ((N, C, H, W), dtype, window) -> workspace bytes (< 0: geometry off the fused kernels)
 
 
-def _geom(q):
+def _geom(q, kernel_size):
     N, C, H, W = q.shape
-    return _lib.AggGeom(N, C, H, W, 1, C // 8, 3, 3, 1, 1, 1, 1, 1, 1)
+    return _lib.AggGeom(N, C, H, W, 1, C // 8, kernel_size, kernel_size, 1, 1, kernel_size // 2, kernel_size // 2, 1, 1)
 
 
-def _ws_bytes(q):
-    key = (tuple(q.shape), q.dtype)
+def _ws_bytes(q, kernel_size):
+    key = (tuple(q.shape), q.dtype, kernel_size)
     if key not in _WS:
-        _WS[key] = int(_lib.lib().cot_local_relation_workspace_bytes(ctypes.byref(_geom(q)), _lib.dtype_code(q.dtype)))
+        _WS[key] = int(_lib.lib().cot_local_relation_workspace_bytes(ctypes.byref(_geom(q, kernel_size)), _lib.dtype_code(q.dtype)))
     return _WS[key]
 
 
 def _pos(pos_h, pos_w, kernel_size):
-    """pos[c][3i + j] = pos_h[c][i][0] + pos_w[c][0][j]  (:87-88)"""
+    """pos[c][k i + j] = pos_h[c][i][0] + pos_w[c][0][j]  (:87-88)"""
     return (pos_h + pos_w).reshape(pos_h.shape[0], kernel_size * kernel_size)
 
 
 class _LocalRelation(Function):
     @staticmethod
-    def forward(ctx, q, k, v, pos):
+    def forward(ctx, q, k, v, pos, kernel_size):
         q, k, v = (_aligned(t.detach().contiguous()) for t in (q, k, v))
         pos_dtype = pos.dtype
         pos = pos.detach().float().contiguous()
         N, C, H, W = q.shape
-        geom = _geom(q)
+        geom = _geom(q, kernel_size)
         out = torch.empty_like(v)
-        probs = torch.empty((N, 1, C // 8, 9, H, W), dtype=q.dtype, device=q.device)
+        probs = torch.empty((N, 1, C // 8, kernel_size * kernel_size, H, W), dtype=q.dtype, device=q.device)
         _lib.api().cot_local_relation_forward(_ptr(q), _ptr(k), _ptr(v), _ptr(pos), _ptr(out), _ptr(probs),
                                               ctypes.byref(geom), _lib.dtype_code(q.dtype), _stream())
-        ctx.geom, ctx.pos_dtype = geom, pos_dtype
+        ctx.geom, ctx.pos_dtype, ctx.kernel_size = geom, pos_dtype, kernel_size
         ctx.save_for_backward(q, k, v, pos, probs)
         return out
 
@@ -65,11 +67,11 @@ class _LocalRelation(Function):
         gout = _aligned(gout.contiguous())
         gq, gk, gv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
         gpos = torch.empty_like(pos)
-        ws = torch.empty(_ws_bytes(q), dtype=torch.uint8, device=q.device)
+        ws = torch.empty(_ws_bytes(q, ctx.kernel_size), dtype=torch.uint8, device=q.device)
         _lib.api().cot_local_relation_backward(_ptr(gout), _ptr(q), _ptr(k), _ptr(v), _ptr(pos), _ptr(probs), _ptr(gq),
                                                _ptr(gk), _ptr(gv), _ptr(gpos), _ptr(ws), ctypes.byref(ctx.geom),
                                                _lib.dtype_code(q.dtype), _stream())
-        return gq, gk, gv, gpos.to(ctx.pos_dtype)
+        return gq, gk, gv, gpos.to(ctx.pos_dtype), None
 
 
 def local_relation_reference(q, k, v, pos_h, pos_w, kernel_size):
@@ -86,14 +88,15 @@ def local_relation_reference(q, k, v, pos_h, pos_w, kernel_size):
 
 
 def fusable(q, k, v, kernel_size):
-    return (q.is_cuda and kernel_size == 3 and q.dim() == 4 and q.dtype in _DT and k.dtype == q.dtype and v.dtype == q.dtype
-            and k.shape == q.shape and v.shape == q.shape and q.shape[1] % 8 == 0 and _ws_bytes(q) >= 0)
+    return (q.is_cuda and kernel_size in _FUSED_WINDOWS and q.dim() == 4 and q.dtype in _DT and k.dtype == q.dtype
+            and v.dtype == q.dtype and k.shape == q.shape and v.shape == q.shape and q.shape[1] % 8 == 0
+            and _ws_bytes(q, kernel_size) >= 0)
 
 
 def local_relation(q, k, v, pos_h, pos_w, kernel_size):
     """out[n,c,p] = sum_t softmax_t(logit[n, c mod G, :, p]) v[n, c, p + off_t]; see the module docstring"""
     if fusable(q, k, v, kernel_size):
-        return _LocalRelation.apply(q, k, v, _pos(pos_h, pos_w, kernel_size))
-    if q.is_cuda and kernel_size == 3 and q.dtype in _DT:
-        _lib.fallback("local_relation", q, f"C {q.shape[1]}, dtypes {q.dtype} / {k.dtype} / {v.dtype}")
+        return _LocalRelation.apply(q, k, v, _pos(pos_h, pos_w, kernel_size), kernel_size)
+    if q.is_cuda and kernel_size in _FUSED_WINDOWS and q.dtype in _DT:
+        _lib.fallback("local_relation", q, f"window {kernel_size}, C {q.shape[1]}, dtypes {q.dtype} / {k.dtype} / {v.dtype}")
     return local_relation_reference(q, k, v, pos_h, pos_w, kernel_size)

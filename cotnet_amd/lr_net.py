@@ -11,6 +11,9 @@ the same function:
   * the convolutions and BatchNorms run through the package's wrappers (conv1x1, conv3x3, fused_bn_act, pool,
     run_downsample), as cotnet.Bottleneck does.
 
+`Bottleneck_K7` / `lrnet50_k7` are this package's own: the same network at LR-Net's 7x7 window, which the reference's layer takes
+but none of its builders uses.
+
 Unlike CoTNet's Bottleneck, the stride-2 average pool `avd` runs AFTER the attention layer (ref :170-171), so the layer sees
 the stage's input resolution.
 """
@@ -147,6 +150,21 @@ class Bottleneck_Ks3(Bottleneck):
         self.conv2 = SelfAttLayer(width, kernel_size=3, key_ks=3)
 
 
+class Bottleneck_K7(Bottleneck):
+    """the block with LR-Net's own 7x7 window (the layer is parametric in it; the reference builds only 3x3 networks)"""
+    expansion = 4
+
+    def __init__(self, inplanes, planes, stride=1, downsample=None, cardinality=1, base_width=64, reduce_first=1,
+                 dilation=1, first_dilation=None, act_layer=nn.ReLU, norm_layer=nn.BatchNorm2d, attn_layer=None,
+                 aa_layer=None, drop_block=None, drop_path=None):
+        super(Bottleneck_K7, self).__init__(inplanes, planes, stride, downsample, cardinality, base_width, reduce_first,
+                                            dilation, first_dilation, act_layer, norm_layer, attn_layer, aa_layer,
+                                            drop_block, drop_path)
+        # built the way Bottleneck_Ks3 replaces conv2: the parent's layer first, then this one in its place
+        width = int(math.floor(planes * (base_width / 64)) * cardinality)
+        self.conv2 = SelfAttLayer(width, kernel_size=7, key_ks=1)
+
+
 def _create_lrnet(variant, pretrained=False, **kwargs):
     return build_model_with_cfg(ResNet, variant, default_cfg=default_cfgs[variant], pretrained=pretrained, **kwargs)
 
@@ -159,3 +177,11 @@ def lrnet50(pretrained=False, **kwargs):
 @register_model
 def lrnet50_ks3(pretrained=False, **kwargs):
     return _create_lrnet("lrnet_basic", pretrained, block=Bottleneck_Ks3, layers=[3, 4, 6, 3], **kwargs)
+
+
+@register_model
+def lrnet50_k7(pretrained=False, **kwargs):
+    """LR-Net-50 with the 7x7 local relation (SelfAttLayer(width, kernel_size=7, key_ks=1), layers [3, 4, 6, 3]).  NOT a
+    reference entry point: models/lr_net.py builds lrnet50 and lrnet50_ks3 only, so there is no reference state_dict to load
+    and no reference fixture of the whole model; the layer itself is the reference's (tests/golden/lrnet_k7_layer_*)."""
+    return _create_lrnet("lrnet_basic", pretrained, block=Bottleneck_K7, layers=[3, 4, 6, 3], **kwargs)

@@ -107,10 +107,12 @@ int cot_agg_softmax_backward(const void* gout, const void* x, const void* probs,
  *   probs          = softmax over t                                              (:94)
  *   out[n,c,p]     = sum_t probs[n,0,c mod G,t,p] * v[n,c,p + off_t], zero pad   (:95-96: wC = G)
  * A padded tap keeps the logit sum_j q*pos and its probability mass; only v is zero there.
- * q, k, v, out, gq, gk, gv: [N,C,H,W]; probs: [N,1,G,9,H,W] (may be NULL in the forward: inference), all in the storage
- * dtype (COT_F32 / COT_BF16, fp32 accumulation); pos / gpos fp32 [C][9].  The geometry is a cot_agg_geom with kh = kw = 3,
- * stride 1, pad 1, dilation 1, heads 1, wC = C/8, C % 8 == 0; anything else (or a tile that does not fit LDS) returns
- * COT_ERR_UNSUPPORTED and the caller composes unfold + softmax + aggregation.
+ * The same with LR-Net's own 7x7 window: t = 7i + j, pad 3 (local_relation7.hip).  T = kh*kw taps below.
+ * q, k, v, out, gq, gk, gv: [N,C,H,W]; probs: [N,1,G,T,H,W] (may be NULL in the forward: inference), all in the storage
+ * dtype (COT_F32 / COT_BF16, fp32 accumulation); pos / gpos fp32 [C][T].  The geometry is a cot_agg_geom with kh = kw = 3, pad 1
+ * or kh = kw = 7, pad 3; stride 1, dilation 1, heads 1, wC = C/8, C % 8 == 0; anything else -- every other window, 5x5
+ * included, or a tile that does not fit LDS -- returns COT_ERR_UNSUPPORTED and the caller composes unfold + softmax + aggregation.
+ * cot_last_kernel(): lr_fwd / ..+lr_bwd_rel+lr_gpos_reduce at 3x3, lr7_fwd / lr7_bwd_agg+lr7_bwd_rel+lr7_gpos_reduce at 7x7.
  * Backward: gv and glogits as cot_agg_softmax_backward, then gq = sum_t gL (uk + pos), gk[p'] = sum_t gL[p' - off_t] q[p' - off_t]
  * and gpos[c][t] = sum_{n,p} gL[n,c/8,t,p] q[n,c,p] (per-workgroup partials reduced in a fixed order: bit-identical run to run).
  * No allocation and no host synchronisation (graph-capture safe): `workspace` holds
