@@ -13,6 +13,8 @@ Public surface mirrors the reference (JDAI-CV/CoTNet):
     utils.checkpoint_saver / models.helpers.resume_checkpoint -> cotnet_amd.checkpoint (CheckpointSaver, resume_checkpoint)
     optim.optim_factory / optim.adamw / optim.lookahead -> cotnet_amd.optim_factory (create_optimizer -> FlatSGD, FlatAdam, FlatAdamW;
                                             split_opt_name: `lookahead_*` -> the keywords lookahead_k, lookahead_alpha)
+    scheduler (cosine_lr, tanh_lr, step_lr, plateau_lr, scheduler_factory) -> cotnet_amd.lr_schedule (CosineLRSchedule, TanhLRSchedule,
+                                            StepLRSchedule, PlateauLRSchedule, create_scheduler -> (schedule, num_epochs))
     train.py (train_epoch, main) / utils.meters.TrainMeter -> cotnet_amd.trainer (ReplayedStep, TrainMeter, train_epoch, Trainer: the
                                             loop over one replayed step, no host read per step)
 Device code lives in cotnet_amd/csrc (HIP, gfx950) behind the C ABI of include/cotnet_amd.h.
@@ -36,6 +38,8 @@ from .resnet import ResNet  # noqa: F401
 from .checkpoint import CheckpointSaver, resume_checkpoint  # noqa: F401
 from .flat_adamw import FlatAdam, FlatAdamW  # noqa: F401
 from .optim_factory import create_optimizer, split_opt_name  # noqa: F401
+from .lr_schedule import (CosineLRSchedule, CosineSchedule, PlateauLRSchedule, StepLRSchedule, TanhLRSchedule,  # noqa: F401
+                          create_scheduler)
 from .trainer import ReplayedStep, TrainMeter, Trainer, train_epoch  # noqa: F401
 
 __version__ = "0.1.0"

@@ -340,7 +340,9 @@ class Trainer:
     sampler; `train_epoch`; `distribute_bn` where there is a process group and `dist_bn` is 'reduce' or 'broadcast'; `evaler(epoch,
     model)`; where `optimizer.ema_decay` is set, the same inside `optimizer.ema_weights()`, whose top-1 becomes the metric
     (train.py:352-355); `saver.save_recovery(epoch + 1)` when recovery_interval > 0 divides epoch + 1 (0, the reference's default, would divide
-    by zero there: here it means off); with schedule_unit="epoch", `schedule.apply(optimizer, epoch + 1)`; `saver.save_checkpoint(epoch
+    by zero there: here it means off); with schedule_unit="epoch", `schedule.apply(optimizer, epoch + 1)` -- for a schedule whose class says `needs_metric`
+    (PlateauLRSchedule) `schedule.apply(optimizer, epoch + 1, metric)`, the metric that the saver is about to get (DEPARTURE: the
+    reference passes None there, train.py:361, on which its plateau scheduler raises) --; `saver.save_checkpoint(epoch
     + 1, metric=top1)`.  KeyboardInterrupt ends the loop cleanly.  -> `history`, one dict per epoch: epoch, train_loss, updates,
     samples, lr, top1 / top5 / loss of the model, ema_top1 / ema_top5 / ema_loss, best_metric, best_epoch (None where there is nothing
     to report).
@@ -350,6 +352,7 @@ class Trainer:
     Refused at construction, because each would train silently wrong under replay: a schedule with graph=True on a flat optimizer built
     without `device_lr=True` (the capture would freeze the rate); graph=True with a train loader whose mixup is not a DeviceMixup (a
     capture reads the draw from `DeviceMixup.params`; a host-side mixup hands over dense targets that the captured loss cannot take).
+    Refused too: a `needs_metric` schedule without an evaler, or with schedule_unit="update" -- there is no metric to step it with.
     NOT done here: `distribute_bn` of the EMA's averaged buffers (the reference's second call, train.py:353-354)."""
 
     def __init__(self, model, optimizer, loss_fn, train_loader, *, num_epochs, evaler=None, saver=None, schedule=None,
@@ -364,6 +367,13 @@ class Trainer:
             raise ValueError(f"Trainer(schedule=..., graph=True): {type(optimizer).__name__} was built without device_lr=True, so a captured "
                              "step keeps the rate it was captured with and the schedule would not reach the replays -- build the optimizer "
                              "with device_lr=True, or pass graph=False")
+        if getattr(schedule, "needs_metric", False):
+            if evaler is None:
+                raise ValueError(f"Trainer(schedule={type(schedule).__name__}(...)): the schedule is stepped with the epoch's validation metric and "
+                                 "there is no evaler to produce one -- pass evaler=..., or a schedule that needs no metric")
+            if schedule_unit == "update":
+                raise ValueError(f"Trainer(schedule={type(schedule).__name__}(...), schedule_unit='update'): the schedule is stepped with the "
+                                 "epoch's validation metric, and there is none per update -- pass schedule_unit='epoch'")
         mixup = getattr(train_loader, "mixup", getattr(train_loader, "mixup_fn", None))
         if graph and flat and not isinstance(mixup, DeviceMixup) and (mixup is not None or getattr(train_loader, "mixup_enabled", False)):
             raise ValueError(f"Trainer(graph=True): the train loader's mixup is a {type(mixup).__name__}, not a DeviceMixup -- a captured step "
@@ -421,7 +431,10 @@ class Trainer:
                     if self.saver is not None and self.recovery_interval > 0 and (epoch + 1) % self.recovery_interval == 0:
                         self.saver.save_recovery(epoch + 1)
                     if self.schedule is not None and self.schedule_unit == "epoch":
-                        self.schedule.apply(optimizer, epoch + 1)
+                        if getattr(self.schedule, "needs_metric", False):
+                            self.schedule.apply(optimizer, epoch + 1, metric)
+                        else:
+                            self.schedule.apply(optimizer, epoch + 1)
                     if self.saver is not None:
                         self.best_metric, self.best_epoch = self.saver.save_checkpoint(epoch + 1, metric=metric)
                     elif metric is not None and (self.best_metric is None or metric > self.best_metric):
