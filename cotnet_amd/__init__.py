@@ -6,7 +6,7 @@ Public surface mirrors the reference (JDAI-CV/CoTNet):
     models.cotnet                        -> cotnet_amd.cotnet               (CotLayer, CoXtLayer, Bottleneck, cotnet50 ...)
     models.cotnet_hybrid                 -> cotnet_amd.cotnet_hybrid        (CoTLayer, CoTBottleneck, se_cotnetd_* ...)
     models.lr_net                        -> cotnet_amd.lr_net               (SelfAttLayer, Bottleneck, lrnet50, lrnet50_ks3; lrnet50_k7 is this package's own)
-    datasets.mixup (batch mode)          -> cotnet_amd.mixup                (DeviceMixup: host draw, device mixing)
+    datasets.mixup (batch / elem / pair) -> cotnet_amd.mixup                (DeviceMixup, PerSampleMixup, create_mixup: host draw, device mixing)
     loss.cross_entropy                   -> cotnet_amd.loss                 (soft_target_cross_entropy, LabelSmoothingCrossEntropy)
     evaler.evaler / utils.meters         -> cotnet_amd.evaler               (Evaler, DeviceTestMeter, accuracy: scored on the device)
     models.factory / models.registry     -> cotnet_amd.registry             (create_model, register_model)
@@ -31,7 +31,7 @@ from .cotnet_hybrid import (CoTBottleneck, CoTHybridNet, CoTLayer, se_cotnetd_50
 from . import local_relation  # noqa: F401  (the sub-module: import the functions from it, as with aggregation_zeropad)
 from .lr_net import Bottleneck_K7, Bottleneck_Ks3, SelfAttLayer, lrnet50, lrnet50_k7, lrnet50_ks3  # noqa: F401
 from .loss import LabelSmoothingCrossEntropy, MixedSoftTargetCrossEntropy, soft_target_cross_entropy  # noqa: F401
-from .mixup import DeviceMixup  # noqa: F401
+from .mixup import DeviceMixup, PerSampleMixup, create_mixup  # noqa: F401
 from .evaler import DeviceTestMeter, Evaler, accuracy  # noqa: F401
 from .registry import create_model, list_models, load_checkpoint, register_model  # noqa: F401
 from .resnet import ResNet  # noqa: F401

@@ -7,6 +7,10 @@
 // What changes from batch to batch -- mixup or CutMix, lambda, the box -- is NOT a kernel argument: every kernel here reads one 32-byte
 // parameter block in device memory (cot_mix_params, include/cotnet_amd.h) when it RUNS, as cot_sgd_step_lr reads its rate, so a HIP
 // graph that recorded these launches follows the values the block holds at each replay.  The kernels only read the block.
+// The reference's per-sample modes ('elem', 'pair': _mix_elem_collate / _mix_pair_collate, :229-280) are the same kernels reading a
+// TABLE: a header `mode 3, R` followed by R records of the block's layout, record n for sample n and its partner N-1-n.  Header or
+// table is device data too, so the branch is taken inside the kernels (uniform over the grid), not by choosing a kernel on the host;
+// a record is 32 bytes that the lanes of a wave almost always share (one plane is H*W/16 consecutive vectors), served by the cache.
 //
 //   cot_mix_normalize   = cot_input_normalize on  u = mix(x[i], x[N-1-i]):  1 + 1 B read (1 B in mode 0) + sizeof(T) B written per
 //                         element, HBM-bound, 16 pixels per lane (two 16-byte loads, 16-byte stores); the partner is read from the
@@ -25,10 +29,11 @@
 namespace cot {
 
 struct MixParams {  // = cot_mix_params
-    int mode;       // 0 none, 1 mixup, 2 CutMix
+    int mode;       // 0 none, 1 mixup, 2 CutMix; in the header also 3: a table of yl records, one per sample, follows
     float lam, one_minus_lam;
     int yl, yh, xl, xh, reserved;
 };
+constexpr int MIX_TABLE = 3;
 static_assert(sizeof(MixParams) == 32 && sizeof(MixParams) == sizeof(cot_mix_params), "the parameter block is 8 x 32-bit words");
 
 // numpy's `a.astype(float32) * lam + b.astype(float32) * (1 - lam)`, np.rint, .astype(uint8) (mixup.py:296-298): the two products are
@@ -40,14 +45,20 @@ __device__ __forceinline__ uint8_t mix_pixel(uint8_t a, uint8_t b, float lam, fl
     return (uint8_t)(int)rintf(pa + pb);
 }
 
-template <typename T>
-__global__ __launch_bounds__(256) void mix_normalize_kernel(const uint8_t* __restrict__ x, T* __restrict__ y,
-                                                           const float* __restrict__ mean, const float* __restrict__ stdv,
-                                                           const MixParams* __restrict__ pb, int N, int C, int H, int W) {
-    const int mode = pb->mode;
-    const float lam = pb->lam, oml = pb->one_minus_lam;
-    const int yl = pb->yl, yh = pb->yh, xl = pb->xl, xh = pb->xh;
-    const bool mixing = mode == 1 || mode == 2;  // (any other value: as mode 0)
+// the record sample n is mixed by.  Header modes 0-2: the header itself, for every sample.  Table mode: record n of the R that follow the
+// header; a sample past the table is not mixed (mode 0, lam 1).  n < N always, so no word beyond 8 * (1 + min(R, N)) is read
+template <bool TABLE>
+__device__ __forceinline__ MixParams record_of(const MixParams* __restrict__ pb, const MixParams& head, int n) {
+    if (!TABLE) return head;
+    MixParams r = {0, 1.f, 0.f, 0, 0, 0, 0, 0};
+    if (n < head.yl) r = pb[1 + n];  // (head.yl = R)
+    return r;
+}
+
+template <typename T, bool TABLE>
+__device__ __forceinline__ void mix_normalize_body(const uint8_t* __restrict__ x, T* __restrict__ y, const float* __restrict__ mean,
+                                                   const float* __restrict__ stdv, const MixParams* __restrict__ pb,
+                                                   const MixParams& head, int N, int C, int H, int W) {
     const int HW = H * W;
     const int64_t planes = (int64_t)N * C;
     if (HW % 16 == 0) {
@@ -58,18 +69,19 @@ __global__ __launch_bounds__(256) void mix_normalize_kernel(const uint8_t* __res
             const int v = (int)(i - plane * vpp);
             const int n = (int)(plane / C), c = (int)(plane - (int64_t)n * C);
             const float m = mean[c], s = stdv[c];
+            const MixParams r = record_of<TABLE>(pb, head, n);
             Vec<uint8_t, 16> a = ldv<uint8_t, 16>(x + i * 16);
-            if (mixing) {
+            if (r.mode == 1 || r.mode == 2) {  // (any other value: as mode 0)
                 const int64_t j = ((int64_t)(N - 1 - n) * C + c) * vpp + v;  // the same 16 pixels of sample N-1-n
                 const Vec<uint8_t, 16> b = ldv<uint8_t, 16>(x + j * 16);
-                if (mode == 1) {
+                if (r.mode == 1) {
 #pragma unroll
-                    for (int k = 0; k < 16; ++k) a.v[k] = mix_pixel(a.v[k], b.v[k], lam, oml);
+                    for (int k = 0; k < 16; ++k) a.v[k] = mix_pixel(a.v[k], b.v[k], r.lam, r.one_minus_lam);
                 } else {  // a box edge may fall inside the vector, and the vector may run over the end of an image row
                     int yy = (v * 16) / W, xx = v * 16 - yy * W;
 #pragma unroll
                     for (int k = 0; k < 16; ++k) {
-                        if (yy >= yl && yy < yh && xx >= xl && xx < xh) a.v[k] = b.v[k];
+                        if (yy >= r.yl && yy < r.yh && xx >= r.xl && xx < r.xh) a.v[k] = b.v[k];
                         if (++xx == W) { xx = 0; ++yy; }
                     }
                 }
@@ -89,16 +101,27 @@ __global__ __launch_bounds__(256) void mix_normalize_kernel(const uint8_t* __res
             const int64_t plane = i / HW;
             const int p = (int)(i - plane * HW);
             const int n = (int)(plane / C), c = (int)(plane - (int64_t)n * C);
+            const MixParams r = record_of<TABLE>(pb, head, n);
             uint8_t u = x[i];
-            if (mixing) {
+            if (r.mode == 1 || r.mode == 2) {
                 const uint8_t b = x[((int64_t)(N - 1 - n) * C + c) * HW + p];
                 const int yy = p / W, xx = p - yy * W;
-                if (mode == 1) u = mix_pixel(u, b, lam, oml);
-                else if (yy >= yl && yy < yh && xx >= xl && xx < xh) u = b;
+                if (r.mode == 1) u = mix_pixel(u, b, r.lam, r.one_minus_lam);
+                else if (yy >= r.yl && yy < r.yh && xx >= r.xl && xx < r.xh) u = b;
             }
             y[i] = norm_one<T>(u, mean[c], stdv[c]);
         }
     }
+}
+
+// header or table is device data: one kernel, the branch is taken on the header's mode when it runs (uniform over the grid)
+template <typename T>
+__global__ __launch_bounds__(256) void mix_normalize_kernel(const uint8_t* __restrict__ x, T* __restrict__ y,
+                                                           const float* __restrict__ mean, const float* __restrict__ stdv,
+                                                           const MixParams* __restrict__ pb, int N, int C, int H, int W) {
+    const MixParams head = *pb;
+    if (head.mode == MIX_TABLE) mix_normalize_body<T, true>(x, y, mean, stdv, pb, head, N, C, H, W);
+    else mix_normalize_body<T, false>(x, y, mean, stdv, pb, head, N, C, H, W);
 }
 
 int mix_normalize(const void* x, void* y, const float* mean, const float* stdv, const void* params, int N, int C, int H, int W,
@@ -150,8 +173,16 @@ __device__ __forceinline__ RowTarget row_target(const long long* __restrict__ la
     t.y2 = labels[N - 1 - n];
     t.on = on;
     t.off = off;
-    t.lam = pb->lam;
-    t.oml = pb->one_minus_lam;
+    if (pb->mode != MIX_TABLE) {
+        t.lam = pb->lam;
+        t.oml = pb->one_minus_lam;
+    } else if (n < pb->yl) {  // table mode: row n's own record; n < N, so nothing behind record min(R, N) - 1 is read
+        t.lam = pb[1 + n].lam;
+        t.oml = pb[1 + n].one_minus_lam;
+    } else {  // a row past the table: the hard label
+        t.lam = 1.f;
+        t.oml = 0.f;
+    }
     return t;
 }
 

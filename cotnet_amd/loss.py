@@ -62,8 +62,9 @@ def soft_target_cross_entropy(logits, labels, mix, smoothing=0.1):
     if _lib.DEVICE_ONLY and not logits.is_cuda:
         raise RuntimeError("soft_target_cross_entropy: cotnet_amd has no CPU path (logits must be on the GPU)")
     block = _block_of(mix)
-    if block.dtype != torch.int32 or block.numel() != 8 or block.device != logits.device:
-        raise ValueError("soft_target_cross_entropy: the parameter block is int32[8] on the logits' device")
+    if block.dtype != torch.int32 or block.numel() < 8 or block.numel() % 8 or block.device != logits.device:
+        raise ValueError("soft_target_cross_entropy: the parameter block is int32[8] (a PerSampleMixup's: int32[8 * (1 + capacity)]) on the "
+                         "logits' device")
     return _SoftTargetCE.apply(logits.contiguous(), labels.contiguous(), block, float(smoothing))
 
 

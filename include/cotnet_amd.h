@@ -693,9 +693,16 @@ int cot_input_normalize(const void* x_u8, void* y, const float* mean, const floa
  * its writes to the block on the stream, as for cot_sgd_step_lr's rate.
  *   lam = float32(lambda), one_minus_lam = float32(1.0 - lambda) with the subtraction in double -- the reference forms both from the
  *   double (mixup.py:27, :296); 1 - lam in fp32 would not match.  The box [yl, yh) x [xl, xh) is only ever compared with pixel
- *   coordinates, never used as an address. */
+ *   coordinates, never used as an address.
+ * A block whose first word is 3 is the HEADER OF A TABLE (the reference's mode='elem' / 'pair', mixup.py:229-280: a draw per sample):
+ *   {mode = 3, lam, one_minus_lam (both unused), yl = R, 0, 0, 0, 0} followed by R records of this same layout, 8*(1 + R) words in
+ *   all.  Record n (its own mode 0, 1 or 2; any other value: as 0) mixes sample n < min(R, N) with its partner N-1-n; a sample
+ *   n >= R is not mixed (mode 0, lam = 1, one_minus_lam = 0).  With record N-1-n = record n the pair is mixed symmetrically
+ *   ('pair').  In these modes the reference keeps lambda as float32, so the caller stores one_minus_lam = 1.0f - lam subtracted in
+ *   fp32.  No word beyond 8*(1 + min(R, N)) is read, and R, like the boxes, is only compared, never used as an address.
+ * Header or table is decided by the kernels when they run: one recorded launch serves both kinds of block. */
 typedef struct cot_mix_params {
-    int32_t mode; /* 0 none, 1 mixup, 2 CutMix (any other value: as 0) */
+    int32_t mode; /* 0 none, 1 mixup, 2 CutMix; in a block's first word also 3: a table follows (any other value: as 0) */
     float lam, one_minus_lam;
     int32_t yl, yh, xl, xh, reserved;
 } cot_mix_params;
@@ -704,6 +711,7 @@ typedef struct cot_mix_params {
  * j = N-1-i, read from the unmodified input (y must not overlap x):
  *     mode 1: u = rint(float(x_i)*lam + float(x_j)*one_minus_lam)   two fp32 products rounded separately, then added; half to even
  *     mode 2: u = x_j inside the box, x_i outside;   mode 0: u = x_i
+ *     mode 3 (header only): sample i by record i of the table as above, a sample past the table as mode 0
  *     y = (u - mean[c]) / std[c]  exactly as cot_input_normalize (COT_F32 / COT_F16 / COT_BF16)
  * N must be even (the reference asserts, mixup.py:303): odd N is COT_ERR_INVALID_ARG before any launch.  x and y are 16-byte aligned
  * when H*W is a multiple of 16 (16 pixels per lane); otherwise the kernel works element by element and y only needs its element's
@@ -712,7 +720,8 @@ int cot_mix_normalize(const void* x_u8, void* y, const float* mean, const float*
                       int dtype, void* stream);
 
 /* Soft-target cross entropy against targets that are never materialised: logits [N, K] row-major (COT_F32 or COT_BF16), labels
- * int64 [N], `params` the block above (only lam / one_minus_lam are read):
+ * int64 [N], `params` the block above (only lam / one_minus_lam are read; under a table header row n takes them from record n, a
+ * row n >= R takes (1, 0)):
  *     t[n,j] = lam*oh(j, y_n) + one_minus_lam*oh(j, y_{N-1-n}),  oh(j, y) = on if j == y else off,
  *     off = smoothing/K, on = 1 - smoothing + off (formed in double, rounded to fp32 once); everything else in fp32.
  * Labels are only compared with the column index: an out-of-range label matches no column and reads nothing.
