@@ -4,6 +4,7 @@ This is the only place the shared library is opened.  There is NO fallback: if t
 or a call fails, a RuntimeError is raised (the product path must fail loudly, never silently compute
 on the CPU).  The reference's equivalent is cupy_layers/utils.py:14-18 (`load_kernel`).
 """
+import contextlib
 import ctypes
 import functools
 import os
@@ -78,6 +79,9 @@ SYMBOLS = {
     "cot_aggmix_backward_input": (_I, [_P, _P, _P, _P, _G, _I, _I, _I, _I, _P]),
     "cot_aggmix_backward_weight": (_I, [_P, _P, _P, _P, _G, _I, _I, _I, _P]),
     "cot_set_tuning": (_I, [_I, _I]),
+    "cot_get_tuning": (_I, [_I, ctypes.POINTER(_I)]),
+    "cot_reset_tuning": (_I, []),
+    "cot_tuning_name": (ctypes.c_char_p, [_I]),
     "cot_xchg_mode": (_I, []),
     "cot_launch_log": (_I, [ctypes.c_char_p, _I]),
     "cot_radix_gap": (_I, [_P, _P, _P, ctypes.c_int64, _I, _I, _P]),
@@ -252,20 +256,101 @@ def lib():
         L = bind(ctypes.CDLL(LIB_PATH), lenient=bool(os.environ.get("COT_LIB_PATH")))
         if L.cot_abi_version() != 1:
             raise RuntimeError(f"libcotnet_hip.so ABI version {L.cot_abi_version()} != 1")
-        raw_set_tuning = L.cot_set_tuning
-
-        def cot_set_tuning(key, value):  # every caller (tests, bench.py --tune, COT_TUNING) goes through this wrapper
-            for d in _SHAPE_CACHES:
-                d.clear()
-            return raw_set_tuning(key, value)
-        L.cot_set_tuning = cot_set_tuning
-        # developer knobs: COT_TUNING="12=1,9=0" -> cot_set_tuning(12, 1), cot_set_tuning(9, 0)  (include/cotnet_amd.h)
-        for item in filter(None, os.environ.get("COT_TUNING", "").split(",")):
-            k, v = item.split("=")
-            if L.cot_set_tuning(int(k), int(v)) != 0:
+        def clearing(raw):  # every caller (tests, bench.py --tune, COT_TUNING) changes a key through these wrappers
+            def fn(*args):
+                for d in _SHAPE_CACHES:
+                    d.clear()
+                return raw(*args)
+            return fn
+        L.cot_set_tuning = clearing(L.cot_set_tuning)
+        if hasattr(L, "cot_reset_tuning"):
+            L.cot_reset_tuning = clearing(L.cot_reset_tuning)
+        # developer knobs: COT_TUNING="12=1,bn_chan=0" -> cot_set_tuning(12, 1), cot_set_tuning(21, 0)  (include/cotnet_amd.h)
+        for k, v in parse_tuning(os.environ.get("COT_TUNING", ""), L):
+            if L.cot_set_tuning(k, v) != 0:
                 raise RuntimeError(f"COT_TUNING: {L.cot_last_error().decode()}")
         _lib = L
     return _lib
+
+
+# The tuning keys by name (enum cot_tuning_key in include/cotnet_amd.h).  Every helper takes the handle it steers: lib(), or a host
+# build of the kernels bound with bind(ctypes.CDLL(...)) (the tests' emulator).
+def tuning_keys(L):
+    """{"BN_FOLD": 12, ...}: what cot_tuning_name tells of the handle's library"""
+    names = ((k, L.cot_tuning_name(k)) for k in range(64))
+    return {n.decode().upper(): k for k, n in names if n}
+
+
+class Tune:
+    """Tune(L).BN_FOLD == 12: the keys of a handle as attributes, asked for on first use (no handle: lib())"""
+
+    def __init__(self, L=None):
+        self._L = L
+
+    def __getattr__(self, name):
+        if name.startswith("_"):
+            raise AttributeError(name)
+        self.__dict__.update(tuning_keys(self._L or lib()))
+        try:
+            return self.__dict__[name]
+        except KeyError:
+            raise AttributeError(f"no tuning key {name}") from None
+
+
+TUNE = Tune()
+
+
+def _clear_caches():
+    for d in _SHAPE_CACHES:
+        d.clear()
+
+
+def _set_tuning(L, key, value):
+    _clear_caches()  # (lib()'s own cot_set_tuning does it too; an emulator handle's does not)
+    if L.cot_set_tuning(key, value) != 0:
+        raise RuntimeError(L.cot_last_error().decode())
+
+
+def get_tuning(L, key):
+    v = ctypes.c_int()
+    if L.cot_get_tuning(key, ctypes.byref(v)) != 0:
+        raise RuntimeError(L.cot_last_error().decode())
+    return v.value
+
+
+def reset_tuning(L):
+    """every key back to the value the library starts with"""
+    _clear_caches()
+    L.cot_reset_tuning()
+
+
+@contextlib.contextmanager
+def tuned(L, **knobs):
+    """with tuned(L, BN_FOLD=0, BN_CHAN=0): ... -- the keys set in the order given, the values they had put back in reverse order on
+    the way out, whatever way that is.  Nests."""
+    keys = tuning_keys(L)
+    unknown = [n for n in knobs if n not in keys]
+    if unknown:
+        raise KeyError(f"no tuning key {unknown} (include/cotnet_amd.h: enum cot_tuning_key)")
+    old = []
+    try:
+        for name, value in knobs.items():
+            old.append((keys[name], get_tuning(L, keys[name])))
+            _set_tuning(L, keys[name], value)
+        yield
+    finally:
+        for key, value in reversed(old):
+            _set_tuning(L, key, value)
+
+
+def parse_tuning(text, L=None):
+    """"12=1,bn_chan=0" -> [(12, 1), (21, 0)]: a key is its number or its name in either case (L: the handle the names are asked of,
+    lib() by default and only when a name occurs)"""
+    out = []
+    for item in filter(None, (t.strip() for t in text.split(","))):
+        k, v = item.split("=")
+        out.append((int(k) if k.strip().lstrip("-").isdigit() else tuning_keys(L or lib())[k.strip().upper()], int(v)))
+    return out
 
 
 class CotError(RuntimeError):  # an entry point returned a cot_status other than COT_OK: .entry is its name, .status the code

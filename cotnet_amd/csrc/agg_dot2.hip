@@ -381,12 +381,7 @@ __global__ __launch_bounds__(NW * 64) void agg_bwd_nchw_k3_dot2(const bf16_t* __
 // key 33: SAFE operand masking (1 default; 0 = a non-finite gO may reach the next-nearest column of gX as well); key 34: double-
 // buffered slabs (1 default: phase p+1 is copied while phase p is computed; 0 = copy, wait, compute)
 // ------------------------------------------------------------------------------------------------
-static int g_dot2[6] = {1, 0, -1, 0, 1, 1};
-int set_tuning_dot2(int key, int value) {
-    if (key < 0 || key > 5) return -1;
-    g_dot2[key] = value;
-    return 0;
-}
+int g_dot2[6] = {1, 0, -1, 0, 1, 1};
 
 template <int W, int P, int GS, int JP, int NW>
 static int launch_dot2_nw(const bf16_t* gout, const bf16_t* x, const bf16_t* w, bf16_t* gx, bf16_t* gw, const cot_agg_geom& g,

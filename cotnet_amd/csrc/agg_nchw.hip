@@ -925,7 +925,7 @@ __global__ __launch_bounds__(512) void agg_bwd_nchw_k3_lds(const T* __restrict__
 static const char* g_last_kernel = "";  // diagnostic only (written by whichever thread launched last)
 const char* last_kernel_nchw() { return g_last_kernel; }
 
-// run-time tuning knobs (cot_set_tuning): 0 = kernel version (0 auto, 1 force v1, 2 force v2),
+// run-time tuning knobs (cot_set_tuning keys 0..8): 0 = kernel version (0 auto, 1 force v1, 2 force v2),
 // 1 = max P forward, 2 = max P backward, 3 = lane-exchange primitive (-1 auto/probe, 0 DPP, 1 ds_bpermute),
 // 4 = v3 fused backward: channel groups staged in LDS per phase (0 = default 4),
 // 5 = v3 waves per workgroup (4 or 8), 6 = v3 extra dynamic LDS per workgroup in KiB (occupancy shaping: fewer
@@ -934,15 +934,10 @@ const char* last_kernel_nchw() { return g_last_kernel; }
 //     and a gW launch (0 fused, 1 split; A/B on the MI355X: the split form is slower, fused stays the default)
 // defaults from the on-device A/B (profiles/r01_agg_variants.log, N80xC64x56x56 bf16): forward P=4 (v3 22.0 us vs 26.0 at P=8),
 // fused backward P=2 with 4 channel groups per LDS phase (v3 45.4 us; 27.3 vs 31.8 us at 28x28)
-static int g_tune[9] = {0, 4, 2, -1, 0, 4, 0, -1, 0};
+int g_tune[9] = {0, 4, 2, -1, 0, 4, 0, -1, 0};
 // XCD-aware tile order (key 7): -1 = automatic -- on for planes up to 28 x 28 (round-2 A/B on the MI355X: 28 x 28 forward
 // 15.7 -> 14.7 us, backward 23.6 -> 22.5 us; 56 x 56 is 2 % slower with it), 0 off, 1 on
 static inline int xcd_order(int H, int W) { return g_tune[7] < 0 ? (H * W <= 28 * 28 ? 1 : 0) : g_tune[7]; }
-int set_tuning_nchw(int key, int value) {
-    if (key < 0 || key > 8) return -1;
-    g_tune[key] = value;
-    return 0;
-}
 
 // One-time device probe: does v_mov_b32_dpp wave_shr:1 / wave_shl:1 move data the way the v2 kernels assume?
 int xchg_mode() {

@@ -7,6 +7,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <mutex>
 #include <vector>
@@ -256,72 +257,114 @@ const char* cot_status_string(int status) {
 
 int cot_agg_out_size(int in, int k, int s, int p, int d) { return out_size(in, k, s, p, d); }
 
-// cot_set_tuning: one row per key -- where the value goes, how it is normalised, and what it is in a line (the full account is at the
-// global's definition).  Keys 0-8 go to set_tuning_nchw, 29-34 to set_tuning_dot2; 35 is unused.
+// The tuning keys (enum cot_tuning_key in the header tells what each one does): one row per key -- its name, where the value lives
+// and how it is normalised.  A key's default is what its target holds before the first write: every target is a constant-initialised
+// int, and tuning_defaults() copies them all on the first use of a tuning entry point.
 static int tn_raw(int v) { return v; }
 static int tn_bool(int v) { return v ? 1 : 0; }
 static int tn_012(int v) { return v == 2 ? 2 : (v ? 1 : 0); }
 static int tn_nonneg(int v) { return v > 0 ? v : 0; }
 struct TuneRow {
     int key;
+    const char* name;
     int* target;
     int (*norm)(int);
-    const char* what;
 };
 static const TuneRow kTuning[] = {
-    {9, &g_conv1x1_tune[0], tn_raw, "first-generation 1x1: XCD remap"},
-    {10, &g_conv1x1_tune[1], tn_raw, "first-generation 1x1: MT override (0 = auto)"},
-    {11, &g_conv1x1_tune[2], tn_raw, "first-generation 1x1 weight gradient: target waves"},
-    {12, &g_bn_fold, tn_bool, "BatchNorm: statistics merged in the apply kernel's prologue"},
-    {13, &g_bn_grid_cap, [](int v) { return v > 0 ? v : 4096; }, "BatchNorm: most workgroups of a flat apply kernel"},
-    {14, &g_conv1x1_tune[3], tn_raw, "first-generation 1x1: waves from which the ring depth is 1"},
-    {15, &g_conv_lds_tune[0], tn_raw, "LDS kernels on / off"},
-    {16, &g_conv_lds_tune[1], tn_raw, "LDS kernels: images per FLAT tile (0 = by plane size)"},
-    {17, &g_conv_lds_tune[2], tn_raw, "LDS kernels: A/B bits (bit 2 weight gradient off, bit 5 transposed weight copy)"},
-    {18, &g_bn_small_m, tn_nonneg, "BatchNorm: samples per channel up to which the fp64 path is taken"},
-    {19, &g_wgrad_cap_pct, tn_nonneg, "weight gradient: partial-sum cap in percent of the input bytes"},
-    {20, &g_wgrad_lds_cap_pct, tn_nonneg, "LDS weight gradient: the same cap"},
-    {21, &g_bn_chan, tn_nonneg, "channel-resident BatchNorm: 0 off, 1 on, 256 / 512 / 1024 on with that workgroup size"},
-    {22, &g_conv_tiny, tn_bool, "one-image 1x1 kernels"},
-    {23, &g_conv_lds2_tune, tn_raw, "third-generation 1x1: A/B bits"},
-    {24, &g_conv_ablate, tn_raw, "DIAGNOSTIC: timing ablations of the third-generation 1x1 kernel (results become wrong)"},
-    {25, &g_wgrad2_tune, tn_raw, "third-generation weight gradient: A/B bits"},
-    {26, &g_dry_run, tn_bool, "dry run: record launches instead of issuing them (see cot_launch_log)"},
-    {27, &g_pool_tile, tn_bool, "row-block pooling kernels"},
-    {28, &g_bn_split_target, [](int v) { return v > 0 ? v : 1024; }, "streaming BatchNorm: workgroups aimed for"},
-    {36, &g_grouped_tuned, tn_bool, "grouped 1x1 convolutions group by group on the tuned kernels"},
-    {37, &g_conv3x3_merge, tn_bool, "merged-groups 3x3 weight gradient"},
-    {38, &g_conv3x3_ring, [](int v) { return v >= 5 ? 5 : 3; }, "3x3 per-step ring depth"},
-    {39, &g_conv3x3_res, tn_012, "chunk-resident 3x3: 0 off, 1 groups of >= 24 channels, 2 also 16-channel groups"},
-    {40, &g_bn_chan7, tn_bool, "channel-resident BatchNorm: 7-element accesses"},
-    {41, &g_stem_lds, tn_bool, "7x7 stem: input rows staged in LDS"},
-    {42, &g_conv3x3_wsingle, tn_012, "chunk-resident 3x3: one weight buffer"},
-    {43, &g_conv_flat_ns3, tn_012, "third-generation 1x1: three-stage FLAT tiles"},
-    {44, &g_conv3x3_cols, tn_012, "chunk-resident 3x3: 512- or 256-column tiles"},
-    {45, &g_conv3x3_perm, tn_012, "chunk-resident 3x3: K order inside a chunk"},
-    {46, &g_conv_big_fill, tn_nonneg, "third-generation 1x1: workgroups below which BIG tiles take narrower channel blocks"},
-    {47, &g_bn_chan_rr, tn_bool, "channel-resident BatchNorm: short-round instances"},
-    {48, &g_conv_big_xswz, [](int v) { return v & 7; }, "third-generation 1x1: LDS permutation bits"},
-    {49, &g_gn9_pack, tn_bool, "GroupNorm-9: several (image, group) pairs per wave on small planes"},
-    {50, &g_radix_pack7, tn_bool, "radix tail: 8 planes of 7 x 7 per wave"},
-    {51, &g_mix_tune[0], tn_bool, "mixed aggregation: generic kernels only"},
-    {52, &g_mix_tune[1], [](int v) { return v >= 64 ? v : 256; }, "mixed aggregation: lanes a workgroup aims for"},
-    {53, &g_mix_tune[2], [](int v) { return v == 1 || v == 2 || v == 4 ? v : 0; }, "mixed aggregation: pixels per lane"},
-    {54, &g_conv_k_tail, tn_bool, "third-generation 1x1: reduction depths off the 32-channel grid"},
+    {COT_TUNE_AGG_VERSION, "agg_version", &g_tune[0], tn_raw},
+    {COT_TUNE_AGG_PPL_FWD, "agg_ppl_fwd", &g_tune[1], tn_raw},
+    {COT_TUNE_AGG_PPL_BWD, "agg_ppl_bwd", &g_tune[2], tn_raw},
+    {COT_TUNE_AGG_XCHG, "agg_xchg", &g_tune[3], tn_raw},
+    {COT_TUNE_AGG_V3_GROUPS, "agg_v3_groups", &g_tune[4], tn_raw},
+    {COT_TUNE_AGG_V3_WAVES, "agg_v3_waves", &g_tune[5], tn_raw},
+    {COT_TUNE_AGG_V3_LDS_KIB, "agg_v3_lds_kib", &g_tune[6], tn_raw},
+    {COT_TUNE_AGG_V3_XCD, "agg_v3_xcd", &g_tune[7], tn_raw},
+    {COT_TUNE_AGG_BWD_SPLIT, "agg_bwd_split", &g_tune[8], tn_raw},
+    {COT_TUNE_C1_XCD, "c1_xcd", &g_conv1x1_tune[0], tn_raw},
+    {COT_TUNE_C1_ROWS_PER_WAVE, "c1_rows_per_wave", &g_conv1x1_tune[1], tn_raw},
+    {COT_TUNE_C1_WGRAD_WAVES, "c1_wgrad_waves", &g_conv1x1_tune[2], tn_raw},
+    {COT_TUNE_BN_FOLD, "bn_fold", &g_bn_fold, tn_bool},
+    {COT_TUNE_BN_GRID_CAP, "bn_grid_cap", &g_bn_grid_cap, [](int v) { return v > 0 ? v : 4096; }},
+    {COT_TUNE_C1_SHALLOW_RING_WAVES, "c1_shallow_ring_waves", &g_conv1x1_tune[3], tn_raw},
+    {COT_TUNE_CONV_LDS, "conv_lds", &g_conv_lds_tune[0], tn_raw},
+    {COT_TUNE_CONV_LDS_FLAT_IMAGES, "conv_lds_flat_images", &g_conv_lds_tune[1], tn_raw},
+    {COT_TUNE_CONV_LDS_BITS, "conv_lds_bits", &g_conv_lds_tune[2], tn_raw},
+    {COT_TUNE_BN_SMALL_M, "bn_small_m", &g_bn_small_m, tn_nonneg},
+    {COT_TUNE_WGRAD_CAP_PCT, "wgrad_cap_pct", &g_wgrad_cap_pct, tn_nonneg},
+    {COT_TUNE_WGRAD_LDS_CAP_PCT, "wgrad_lds_cap_pct", &g_wgrad_lds_cap_pct, tn_nonneg},
+    {COT_TUNE_BN_CHAN, "bn_chan", &g_bn_chan, tn_nonneg},
+    {COT_TUNE_CONV_TINY, "conv_tiny", &g_conv_tiny, tn_bool},
+    {COT_TUNE_CONV_LDS2_BITS, "conv_lds2_bits", &g_conv_lds2_tune, tn_raw},
+    {COT_TUNE_CONV_ABLATE, "conv_ablate", &g_conv_ablate, tn_raw},
+    {COT_TUNE_WGRAD2_BITS, "wgrad2_bits", &g_wgrad2_tune, tn_raw},
+    {COT_TUNE_DRY_RUN, "dry_run", &g_dry_run, tn_bool},
+    {COT_TUNE_POOL_TILE, "pool_tile", &g_pool_tile, tn_bool},
+    {COT_TUNE_BN_SPLIT_TARGET, "bn_split_target", &g_bn_split_target, [](int v) { return v > 0 ? v : 1024; }},
+    {COT_TUNE_DOT2, "dot2", &g_dot2[0], tn_raw},
+    {COT_TUNE_DOT2_GROUPS, "dot2_groups", &g_dot2[1], tn_raw},
+    {COT_TUNE_DOT2_XCD, "dot2_xcd", &g_dot2[2], tn_raw},
+    {COT_TUNE_DOT2_WAVES, "dot2_waves", &g_dot2[3], tn_raw},
+    {COT_TUNE_DOT2_SAFE, "dot2_safe", &g_dot2[4], tn_raw},
+    {COT_TUNE_DOT2_DOUBLE_BUFFER, "dot2_double_buffer", &g_dot2[5], tn_raw},
+    {COT_TUNE_GROUPED_TUNED, "grouped_tuned", &g_grouped_tuned, tn_bool},
+    {COT_TUNE_CONV3X3_MERGE, "conv3x3_merge", &g_conv3x3_merge, tn_bool},
+    {COT_TUNE_CONV3X3_RING, "conv3x3_ring", &g_conv3x3_ring, [](int v) { return v >= 5 ? 5 : 3; }},
+    {COT_TUNE_CONV3X3_RES, "conv3x3_res", &g_conv3x3_res, tn_012},
+    {COT_TUNE_BN_CHAN7, "bn_chan7", &g_bn_chan7, tn_bool},
+    {COT_TUNE_STEM_LDS, "stem_lds", &g_stem_lds, tn_bool},
+    {COT_TUNE_CONV3X3_WSINGLE, "conv3x3_wsingle", &g_conv3x3_wsingle, tn_012},
+    {COT_TUNE_CONV_FLAT_NS3, "conv_flat_ns3", &g_conv_flat_ns3, tn_012},
+    {COT_TUNE_CONV3X3_COLS, "conv3x3_cols", &g_conv3x3_cols, tn_012},
+    {COT_TUNE_CONV3X3_PERM, "conv3x3_perm", &g_conv3x3_perm, tn_012},
+    {COT_TUNE_CONV_BIG_FILL, "conv_big_fill", &g_conv_big_fill, tn_nonneg},
+    {COT_TUNE_BN_CHAN_RR, "bn_chan_rr", &g_bn_chan_rr, tn_bool},
+    {COT_TUNE_CONV_BIG_XSWZ, "conv_big_xswz", &g_conv_big_xswz, [](int v) { return v & 7; }},
+    {COT_TUNE_GN9_PACK, "gn9_pack", &g_gn9_pack, tn_bool},
+    {COT_TUNE_RADIX_PACK7, "radix_pack7", &g_radix_pack7, tn_bool},
+    {COT_TUNE_MIX_GENERIC, "mix_generic", &g_mix_tune[0], tn_bool},
+    {COT_TUNE_MIX_LANES, "mix_lanes", &g_mix_tune[1], [](int v) { return v >= 64 ? v : 256; }},
+    {COT_TUNE_MIX_PPL, "mix_ppl", &g_mix_tune[2], [](int v) { return v == 1 || v == 2 || v == 4 ? v : 0; }},
+    {COT_TUNE_CONV_K_TAIL, "conv_k_tail", &g_conv_k_tail, tn_bool},
 };
+constexpr int kTuningRows = (int)(sizeof(kTuning) / sizeof(kTuning[0]));
+static const std::array<int, kTuningRows>& tuning_defaults() {
+    static const std::array<int, kTuningRows> snapshot = [] {
+        std::array<int, kTuningRows> d;
+        for (int i = 0; i < kTuningRows; ++i) d[i] = *kTuning[i].target;
+        return d;
+    }();
+    return snapshot;
+}
+static const TuneRow* tuning_row(int key) {
+    tuning_defaults();
+    for (const TuneRow& r : kTuning)
+        if (r.key == key) return &r;
+    set_error(COT_ERR_INVALID_ARG, "unknown tuning key %d", key);
+    return nullptr;
+}
 
 int cot_set_tuning(int key, int value) {
-    for (const TuneRow& r : kTuning)
-        if (r.key == key) {
-            *r.target = r.norm(value);
-            return COT_OK;
-        }
-    if (key >= 29 && key <= 34) {
-        set_tuning_dot2(key - 29, value);
-        return COT_OK;
-    }
-    if (set_tuning_nchw(key, value) != 0) return set_error(COT_ERR_INVALID_ARG, "unknown tuning key %d", key);
+    const TuneRow* r = tuning_row(key);
+    if (!r) return COT_ERR_INVALID_ARG;
+    *r->target = r->norm(value);
     return COT_OK;
+}
+int cot_get_tuning(int key, int* value) {
+    const TuneRow* r = tuning_row(key);
+    if (!r) return COT_ERR_INVALID_ARG;
+    if (!value) return set_error(COT_ERR_INVALID_ARG, "NULL value");
+    *value = *r->target;
+    return COT_OK;
+}
+int cot_reset_tuning(void) {
+    const auto& d = tuning_defaults();
+    for (int i = 0; i < kTuningRows; ++i) *kTuning[i].target = d[i];
+    return COT_OK;
+}
+const char* cot_tuning_name(int key) {
+    for (const TuneRow& r : kTuning)
+        if (r.key == key) return r.name;
+    return nullptr;
 }
 int cot_xchg_mode(void) { return g_dry_run ? 0 : xchg_mode(); }
 int cot_launch_log(char* buf, int cap) {

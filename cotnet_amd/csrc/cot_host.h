@@ -12,7 +12,7 @@ extern unsigned long long* g_debug_stamps;  // DIAGNOSTIC: see cot_debug_stamps
 
 // ---- agg_nchw.hip: aggregation, NCHW (fused softmax / GroupNorm-9 / row-statistics forms included)
 const char* last_kernel_nchw();
-int set_tuning_nchw(int key, int value);
+extern int g_tune[9];
 int xchg_mode();
 template <typename T> int agg_forward_nchw(const T* x, const T* w, T* out, const cot_agg_geom& g, int Ho, int Wo, hipStream_t s, const char* tname);
 template <typename T>
@@ -27,7 +27,7 @@ int agg_softmax_backward_nchw(const T* gout, const T* x, const T* probs, T* gx, 
 
 // ---- agg_dot2.hip: packed-bf16 dot-product backward of the 3x3 aggregation; -1 = geometry not covered
 int agg_backward_nchw_dot2(const bf16_t* gout, const bf16_t* x, const bf16_t* w, bf16_t* gx, bf16_t* gw, const cot_agg_geom& g, hipStream_t s);
-int set_tuning_dot2(int key, int value);
+extern int g_dot2[6];
 int agg_gn9_backward_nchw_dot2(const bf16_t* gout, const bf16_t* x, const bf16_t* logits, const float* mean, const float* rstd, const bf16_t* gamma,
                                const bf16_t* beta, int gimg, bf16_t* gx, bf16_t* gw, const cot_agg_geom& g, hipStream_t s);
 

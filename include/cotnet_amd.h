@@ -144,86 +144,140 @@ const char* cot_status_string(int status);
  * (e.g. "agg_fwd_nchw_k3<bf16,P8>"); used by tests to prove the fast path ran. */
 const char* cot_last_kernel(void);
 
-/* Developer knobs for A/B benchmarking (process-global, not part of the drop-in contract):
- *   key 0: 3x3 fast-path kernel version (0 auto, 1 = v1 scalar-halo, 2 = v2 wave-aligned, 3 = v3 LDS-staged kernels)
- *   key 1: max pixels per lane, forward   key 2: max pixels per lane, fused backward
- *   key 3: lane-exchange primitive (-1 probe on first use, 0 = DPP wave shift, 1 = ds_bpermute)
- *   key 4: v3 backward channel groups per LDS phase   key 5: v3 waves per workgroup (4|8)
- *   key 6: v3 extra LDS KiB per workgroup             key 7: v3 XCD-aware tile order (0|1)
- *   key 8: issue the fused backward as separate gX and gW launches (0|1)
- *   key 9: 1x1-convolution kernels XCD-aware wave order (0|1)   key 10: 16-row tiles per wave, forward (0 auto|2|4)
- *   key 11: weight-gradient target wave count (sizes the split of the reduction AND therefore cot_*_workspace: query the
- *           workspace after setting it); negative = force -value splits
- *   key 12: BatchNorm: fold the per-channel finalize step into the apply kernels (1 default | 0; one launch less each way)
- *   key 13: BatchNorm: most workgroups of the flat (grid-stride) apply kernels (default 4096; <= 0 restores it)
- *   key 14: convolutions: launches of at least this many waves use the shallow register ring (default 8192;
- *           a huge value = deep rings everywhere, 1 = shallow everywhere; <= 0 restores the default)
- *   key 15: LDS-pipelined convolution kernels (conv_lds.hip) on (1, default) / off (0: first-generation kernels)
- *   key 16: conv_lds FLAT mode: images per workgroup (0 = auto)
- *   key 17: conv_lds bit field -- bit 0 (retired: four-wave workgroups), bit 1 2-byte gathers instead of transposing LDS reads, bit 2 LDS
- *           weight gradient off, bit 3 general LDS weight gradient everywhere, bit 4 its deep-layer rule off, bit 5 data
- *           gradient on a transposed weight copy instead of reading the weight in place, bits 8..: 7 x 7 stage channel-block
- *           rule (0 default, 1 off, n > 1 workgroup-count threshold)
- *   key 18: BatchNorm: per-channel sample count up to which the fp64 one-wave-per-channel path is taken (default 256)
- *   key 19: weight gradients (register kernels): partial-sum bytes allowed as a percentage of the input bytes (default 50)
- *   key 20: the same for the LDS weight gradient (default 25 aligned planes / 100 general form)
- *   key 21: BatchNorm channel-resident kernels (1 default, 0 off, 256 / 512 / 1024 = forced workgroup size)
- *   key 22: one-image 1x1 convolutions on the staging-free kernels of conv_tiny.hip (1 default, 0 off)
- *   key 23: third-generation 1x1 forward / data-gradient kernel (conv_lds2.hip) bit field -- bit 0 off (second generation
- *           instead), bit 1 no fragment prefetch in the small-image (FLAT) kernels, bit 2 fragment prefetch in the BIG kernels
- *   key 24: DIAGNOSTIC timing ablations of the third-generation 1x1 kernel (results become wrong; 0 = off)
- *   key 25: third-generation 1x1 weight gradient (conv_wgrad2.hip) bit field -- bit 0 off, bit 1 the plain K loop (no fragment
- *           prefetch, 32-pixel stages), bit 2 old LDS chunk permutation of the 32-pixel forms, bit 4 general reduce kernel only,
- *           bit 6 32-pixel stages for every plane, bit 7 64-pixel stages + loader waves for every plane (default: planes of more
- *           than 64 pixels), bits 8..15 partial-sum cap in % of the input bytes (0 = 100), bits 16..23 target workgroups per
- *           CU x 4 (0 = 4), bits 24..30 forced slice count (tests)
- *   key 26: dry run (1): no kernel is launched, no HIP call is made; launches are recorded for cot_launch_log()
- *   key 27: 3x3 / stride-2 poolings: 1 (default) = row blocks (a lane owns a group of windows), 0 = one lane per pixel
- *   key 28: streaming BatchNorm kernels: workgroups aimed for (channels x batch chunks; default 1024).  Changes
- *           cot_bn_act_workspace: query it after setting the key
- *   key 29: bf16 fused aggregation backward on the packed dot-product kernel (agg_dot2.hip; 1 default, 0 = the fp32-unpacked
- *           LDS kernel)   key 30: its channel groups per LDS phase (0 = by width; 2 | 4 | 8)   key 31: its XCD-aware tile order
- *           (-1 automatic, 0 off, 1 on)   key 32: its waves per workgroup (0 = by width; 2 | 4 | 5 | 7)
- *   key 33: 1 (default) = operand halves outside an output's window are cleared, so Inf / NaN in gO reach exactly the gX
- *           elements the reference puts them in; 0 = they may also reach the next-nearest column (12 instructions per channel less)
- *   key 34: 1 (default) = its slabs are double-buffered (phase p+1 copied while phase p is computed), 0 = copy, wait, compute
- *   key 36: grouped 1x1 convolutions (cot_conv1x1g_*) group by group on the tuned LDS-pipelined kernels where a group's depth is a
- *           multiple of 32 (1 default), 0 = general kernels everywhere
- *   key 37: grouped 3x3 weight gradient with group widths off the 8-channel grid (12 per group): neighbouring groups merged, the
- *           wider convolution's gradient taken on the tuned kernels and its diagonal blocks copied out (1 default), 0 = general kernel
- *   key 38: (A/B builds only) weight-tile ring of the per-step form of the LDS-staged 3x3 kernel
- *   key 46: 1x1 forward / data gradient on 128-pixel tiles (planes of more than 256 pixels, i.e. also the channel-major rows of the
- *           deep stages): output-channel blocks of 64 / 32 instead of 128 while the launch has fewer workgroups than `value` (200 default, 0 = off)
- *   key 47: channel-resident BatchNorm: instances unrolled for 2 / 4 rounds where they cover the channel (1 default), 0 = always the
- *           full-capacity instance
- *   key 48: LDS layouts of the 1x1 forward / data-gradient kernel against bank conflicts (7 default; results identical either way):
- *           bit 0 = the X stage of 128-pixel tiles with its 16-byte chunks XOR-permuted per channel row, bit 1 / bit 2 = the weight
- *           tile's / transposed weight tile's chunk permutation in the form that is conflict-free under the hardware's lane groups
- *   key 49: GroupNorm of the attention logits on planes of at most 128 pixels (7 x 7, 10 x 10): several (image, group) pairs per
- *           wave (1 default), 0 = one workgroup each
- *   key 50: radix-2 tail kernels with channel-major descriptors on 7 x 7 bf16 planes: eight planes per wave, 7 lanes x 7 elements
- *           each (1 default), 0 = one wave per plane
- *   key 51: aggregation_zeropad_mix: 1 = the one-lane-per-element kernels for every call (A/B; default 0 = LDS-tiled kernels where
- *           the geometry is stride 1, padding 1 / 2);  key 52: lanes a tiled workgroup aims for (default 256);  key 53: pixels per lane
- *           (0 = the planner's choice per direction, else 1 / 2 / 4)
- *   key 54: 1x1 convolutions whose reduction depth is a multiple of 8 but not of 32 (CoXtLayer's groups of 24 / 48 / 216 / 432 channels)
- *           on the LDS-pipelined kernels with a partial last K step (1 default), 0 = first-generation / general kernels
- *   key 39: LDS-staged 3x3 forward / data gradient: 1 (default) = the chunk-resident form (all nine taps' weights of a 32-channel
- *           chunk in LDS, one barrier per chunk) for groups of >= 24 channels, 2 = also for 16-channel groups, 0 = the per-step
- *           ring everywhere
- *   key 40: channel-resident BatchNorm on odd planes that are multiples of 7 (7 x 7): 1 (default) = 7 elements per access,
- *           0 = element by element
- *   key 41: stem 7x7 forward: 1 (default) = input patch staged in LDS, 0 = operand gathered from global memory
- *   key 42: chunk-resident 3x3 form: 1 (default) = one weight buffer where that makes room for a second workgroup per CU, 0 = always two
- *   key 43: 1x1 forward / data gradient on whole small images (H*W <= 256), 128-row tiles: 1 (default) = three LDS stages instead of
- *           six when the launch has more than one workgroup per CU (two then share a CU), 0 = always six
- *   key 44: chunk-resident 3x3 form, groups of <= 32 channels on planes > 256 pixels: 1 (default) = 512- or 256-column tiles by
- *           rounds of workgroups, 0 = 512-column tiles wherever they fill the chip
- *   key 45: chunk-resident 3x3 form, order of the 32 channels of a chunk along K: 1 (default) = blocked or interleaved by LDS bank
- *           windows of the staged rows, 0 = always blocked, 2 = always interleaved
+/* Developer knobs for A/B benchmarking (process-global, not part of the drop-in contract).  The numbers are the interface of
+ * `bench.py --tune KEY=VALUE`, COT_TUNING and the logs under profiles/: they never change; 35 is unused.
  * Keys 11, 15, 17 (bits 2-4), 19, 20, 25 change split counts / kernel choice: query cot_*_workspace after setting them. */
+enum cot_tuning_key {
+    /* 3x3 fast-path kernel version (0 auto, 1 = v1 scalar-halo, 2 = v2 wave-aligned, 3 = v3 LDS-staged kernels) */
+    COT_TUNE_AGG_VERSION = 0,
+    COT_TUNE_AGG_PPL_FWD = 1, /* max pixels per lane, forward */
+    COT_TUNE_AGG_PPL_BWD = 2, /* max pixels per lane, fused backward */
+    COT_TUNE_AGG_XCHG = 3,    /* lane-exchange primitive (-1 probe on first use, 0 = DPP wave shift, 1 = ds_bpermute) */
+    COT_TUNE_AGG_V3_GROUPS = 4,  /* v3 backward channel groups per LDS phase */
+    COT_TUNE_AGG_V3_WAVES = 5,   /* v3 waves per workgroup (4|8) */
+    COT_TUNE_AGG_V3_LDS_KIB = 6, /* v3 extra LDS KiB per workgroup */
+    COT_TUNE_AGG_V3_XCD = 7,     /* v3 XCD-aware tile order (0|1) */
+    COT_TUNE_AGG_BWD_SPLIT = 8,  /* issue the fused backward as separate gX and gW launches (0|1) */
+    COT_TUNE_C1_XCD = 9,         /* 1x1-convolution kernels XCD-aware wave order (0|1) */
+    COT_TUNE_C1_ROWS_PER_WAVE = 10, /* 16-row tiles per wave, forward (0 auto|2|4) */
+    /* weight-gradient target wave count (sizes the split of the reduction AND therefore cot_*_workspace: query the
+     * workspace after setting it); negative = force -value splits */
+    COT_TUNE_C1_WGRAD_WAVES = 11,
+    /* BatchNorm: fold the per-channel finalize step into the apply kernels (1 default | 0; one launch less each way) */
+    COT_TUNE_BN_FOLD = 12,
+    /* BatchNorm: most workgroups of the flat (grid-stride) apply kernels (default 4096; <= 0 restores it) */
+    COT_TUNE_BN_GRID_CAP = 13,
+    /* convolutions: launches of at least this many waves use the shallow register ring (default 8192;
+     * a huge value = deep rings everywhere, 1 = shallow everywhere; <= 0 restores the default) */
+    COT_TUNE_C1_SHALLOW_RING_WAVES = 14,
+    /* LDS-pipelined convolution kernels (conv_lds.hip) on (1, default) / off (0: first-generation kernels) */
+    COT_TUNE_CONV_LDS = 15,
+    COT_TUNE_CONV_LDS_FLAT_IMAGES = 16, /* conv_lds FLAT mode: images per workgroup (0 = auto) */
+    /* conv_lds bit field -- bit 0 (retired: four-wave workgroups), bit 1 2-byte gathers instead of transposing LDS reads, bit 2 LDS
+     * weight gradient off, bit 3 general LDS weight gradient everywhere, bit 4 its deep-layer rule off, bit 5 data
+     * gradient on a transposed weight copy instead of reading the weight in place, bits 8..: 7 x 7 stage channel-block
+     * rule (0 default, 1 off, n > 1 workgroup-count threshold) */
+    COT_TUNE_CONV_LDS_BITS = 17,
+    /* BatchNorm: per-channel sample count up to which the fp64 one-wave-per-channel path is taken (default 256) */
+    COT_TUNE_BN_SMALL_M = 18,
+    /* weight gradients (register kernels): partial-sum bytes allowed as a percentage of the input bytes (default 50) */
+    COT_TUNE_WGRAD_CAP_PCT = 19,
+    /* the same for the LDS weight gradient (default 25 aligned planes / 100 general form) */
+    COT_TUNE_WGRAD_LDS_CAP_PCT = 20,
+    /* BatchNorm channel-resident kernels (1 default, 0 off, 256 / 512 / 1024 = forced workgroup size) */
+    COT_TUNE_BN_CHAN = 21,
+    /* one-image 1x1 convolutions on the staging-free kernels of conv_tiny.hip (1 default, 0 off) */
+    COT_TUNE_CONV_TINY = 22,
+    /* third-generation 1x1 forward / data-gradient kernel (conv_lds2.hip) bit field -- bit 0 off (second generation
+     * instead), bit 1 no fragment prefetch in the small-image (FLAT) kernels, bit 2 fragment prefetch in the BIG kernels */
+    COT_TUNE_CONV_LDS2_BITS = 23,
+    /* DIAGNOSTIC timing ablations of the third-generation 1x1 kernel (results become wrong; 0 = off) */
+    COT_TUNE_CONV_ABLATE = 24,
+    /* third-generation 1x1 weight gradient (conv_wgrad2.hip) bit field -- bit 0 off, bit 1 the plain K loop (no fragment
+     * prefetch, 32-pixel stages), bit 2 old LDS chunk permutation of the 32-pixel forms, bit 4 general reduce kernel only,
+     * bit 6 32-pixel stages for every plane, bit 7 64-pixel stages + loader waves for every plane (default: planes of more
+     * than 64 pixels), bits 8..15 partial-sum cap in % of the input bytes (0 = 100), bits 16..23 target workgroups per
+     * CU x 4 (0 = 4), bits 24..30 forced slice count (tests) */
+    COT_TUNE_WGRAD2_BITS = 25,
+    /* dry run (1): no kernel is launched, no HIP call is made; launches are recorded for cot_launch_log() */
+    COT_TUNE_DRY_RUN = 26,
+    /* 3x3 / stride-2 poolings: 1 (default) = row blocks (a lane owns a group of windows), 0 = one lane per pixel */
+    COT_TUNE_POOL_TILE = 27,
+    /* streaming BatchNorm kernels: workgroups aimed for (channels x batch chunks; default 1024).  Changes
+     * cot_bn_act_workspace: query it after setting the key */
+    COT_TUNE_BN_SPLIT_TARGET = 28,
+    /* bf16 fused aggregation backward on the packed dot-product kernel (agg_dot2.hip; 1 default, 0 = the fp32-unpacked
+     * LDS kernel) */
+    COT_TUNE_DOT2 = 29,
+    COT_TUNE_DOT2_GROUPS = 30, /* its channel groups per LDS phase (0 = by width; 2 | 4 | 8) */
+    COT_TUNE_DOT2_XCD = 31,    /* its XCD-aware tile order (-1 automatic, 0 off, 1 on) */
+    COT_TUNE_DOT2_WAVES = 32,  /* its waves per workgroup (0 = by width; 2 | 4 | 5 | 7) */
+    /* 1 (default) = operand halves outside an output's window are cleared, so Inf / NaN in gO reach exactly the gX
+     * elements the reference puts them in; 0 = they may also reach the next-nearest column (12 instructions per channel less) */
+    COT_TUNE_DOT2_SAFE = 33,
+    /* 1 (default) = its slabs are double-buffered (phase p+1 copied while phase p is computed), 0 = copy, wait, compute */
+    COT_TUNE_DOT2_DOUBLE_BUFFER = 34,
+    /* grouped 1x1 convolutions (cot_conv1x1g_*) group by group on the tuned LDS-pipelined kernels where a group's depth is a
+     * multiple of 32 (1 default), 0 = general kernels everywhere */
+    COT_TUNE_GROUPED_TUNED = 36,
+    /* grouped 3x3 weight gradient with group widths off the 8-channel grid (12 per group): neighbouring groups merged, the
+     * wider convolution's gradient taken on the tuned kernels and its diagonal blocks copied out (1 default), 0 = general kernel */
+    COT_TUNE_CONV3X3_MERGE = 37,
+    /* (A/B builds only) weight-tile ring of the per-step form of the LDS-staged 3x3 kernel */
+    COT_TUNE_CONV3X3_RING = 38,
+    /* LDS-staged 3x3 forward / data gradient: 1 (default) = the chunk-resident form (all nine taps' weights of a 32-channel
+     * chunk in LDS, one barrier per chunk) for groups of >= 24 channels, 2 = also for 16-channel groups, 0 = the per-step
+     * ring everywhere */
+    COT_TUNE_CONV3X3_RES = 39,
+    /* channel-resident BatchNorm on odd planes that are multiples of 7 (7 x 7): 1 (default) = 7 elements per access,
+     * 0 = element by element */
+    COT_TUNE_BN_CHAN7 = 40,
+    /* stem 7x7 forward: 1 (default) = input patch staged in LDS, 0 = operand gathered from global memory */
+    COT_TUNE_STEM_LDS = 41,
+    /* chunk-resident 3x3 form: 1 (default) = one weight buffer where that makes room for a second workgroup per CU, 0 = always two */
+    COT_TUNE_CONV3X3_WSINGLE = 42,
+    /* 1x1 forward / data gradient on whole small images (H*W <= 256), 128-row tiles: 1 (default) = three LDS stages instead of
+     * six when the launch has more than one workgroup per CU (two then share a CU), 0 = always six */
+    COT_TUNE_CONV_FLAT_NS3 = 43,
+    /* chunk-resident 3x3 form, groups of <= 32 channels on planes > 256 pixels: 1 (default) = 512- or 256-column tiles by
+     * rounds of workgroups, 0 = 512-column tiles wherever they fill the chip */
+    COT_TUNE_CONV3X3_COLS = 44,
+    /* chunk-resident 3x3 form, order of the 32 channels of a chunk along K: 1 (default) = blocked or interleaved by LDS bank
+     * windows of the staged rows, 0 = always blocked, 2 = always interleaved */
+    COT_TUNE_CONV3X3_PERM = 45,
+    /* 1x1 forward / data gradient on 128-pixel tiles (planes of more than 256 pixels, i.e. also the channel-major rows of the
+     * deep stages): output-channel blocks of 64 / 32 instead of 128 while the launch has fewer workgroups than `value` (200 default, 0 = off) */
+    COT_TUNE_CONV_BIG_FILL = 46,
+    /* channel-resident BatchNorm: instances unrolled for 2 / 4 rounds where they cover the channel (1 default), 0 = always the
+     * full-capacity instance */
+    COT_TUNE_BN_CHAN_RR = 47,
+    /* LDS layouts of the 1x1 forward / data-gradient kernel against bank conflicts (7 default; results identical either way):
+     * bit 0 = the X stage of 128-pixel tiles with its 16-byte chunks XOR-permuted per channel row, bit 1 / bit 2 = the weight
+     * tile's / transposed weight tile's chunk permutation in the form that is conflict-free under the hardware's lane groups */
+    COT_TUNE_CONV_BIG_XSWZ = 48,
+    /* GroupNorm of the attention logits on planes of at most 128 pixels (7 x 7, 10 x 10): several (image, group) pairs per
+     * wave (1 default), 0 = one workgroup each */
+    COT_TUNE_GN9_PACK = 49,
+    /* radix-2 tail kernels with channel-major descriptors on 7 x 7 bf16 planes: eight planes per wave, 7 lanes x 7 elements
+     * each (1 default), 0 = one wave per plane */
+    COT_TUNE_RADIX_PACK7 = 50,
+    /* aggregation_zeropad_mix: 1 = the one-lane-per-element kernels for every call (A/B; default 0 = LDS-tiled kernels where
+     * the geometry is stride 1, padding 1 / 2) */
+    COT_TUNE_MIX_GENERIC = 51,
+    COT_TUNE_MIX_LANES = 52, /* aggregation_zeropad_mix: lanes a tiled workgroup aims for (default 256) */
+    COT_TUNE_MIX_PPL = 53,   /* aggregation_zeropad_mix: pixels per lane (0 = the planner's choice per direction, else 1 / 2 / 4) */
+    /* 1x1 convolutions whose reduction depth is a multiple of 8 but not of 32 (CoXtLayer's groups of 24 / 48 / 216 / 432 channels)
+     * on the LDS-pipelined kernels with a partial last K step (1 default), 0 = first-generation / general kernels */
+    COT_TUNE_CONV_K_TAIL = 54
+};
+/* Set a knob (`key`: a cot_tuning_key; the value is normalised as the key's account says), read it back (the stored, normalised
+ * value), put every knob -- the dry-run key included -- back to the value the library starts with, and a key's name: the enumerator
+ * without its prefix, in lower case ("bn_fold"); NULL for a number that is no key. */
 int cot_set_tuning(int key, int value);
-/* Dry-run log of the calling thread (cot_set_tuning(26, 1)): one line per launch the library WOULD have issued --
+int cot_get_tuning(int key, int* value);
+int cot_reset_tuning(void);
+const char* cot_tuning_name(int key);
+/* Dry-run log of the calling thread (cot_set_tuning(COT_TUNE_DRY_RUN, 1)): one line per launch the library WOULD have issued --
  * "kernel | launcher instantiation | grid | block | lds".  Copies up to cap-1 bytes into buf (NUL-terminated), clears the log
  * and returns the bytes copied; buf == NULL returns the pending size.  Used to pin the dispatch table without a GPU. */
 int cot_launch_log(char* buf, int cap);

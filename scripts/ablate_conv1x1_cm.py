@@ -21,8 +21,8 @@ SHAPES = [("s3 conv1 1024->256", 1024, 256, 15680), ("s3 embed0 512->128", 512, 
 ABL = [0, 1, 31, 32, 63, 64]
 if len(sys.argv) > 1:
     ABL = [int(v) for v in sys.argv[1].split(',')]
-for kv in (sys.argv[2].split(',') if len(sys.argv) > 2 else []):  # further tuning keys: KEY=VALUE,...
-    assert L.cot_set_tuning(int(kv.split('=')[0]), int(kv.split('=')[1])) == 0
+for key, value in _lib.parse_tuning(sys.argv[2] if len(sys.argv) > 2 else ""):  # further tuning keys: KEY=VALUE,...
+    assert L.cot_set_tuning(key, value) == 0
 
 
 def timeit(fn, n=20):
@@ -50,15 +50,13 @@ for name, Ci, Co, HW in SHAPES:
     ws = torch.empty(int(L.cot_conv1x1_workspace(N, Ci, Co, HW, 0)), dtype=torch.uint8, device=dev)
     res = []
     for a in ABL:
-        assert L.cot_set_tuning(24, a) == 0
+        with _lib.tuned(L, CONV_ABLATE=a):
+            def fwd(i):
+                x, gy, y, gx = sets[i % nset]
+                assert L.cot_conv1x1_forward(P(x), None, Ci, P(w), None, P(y), N, Ci, Co, HW, BF, None) == 0, L.cot_last_error()
 
-        def fwd(i):
-            x, gy, y, gx = sets[i % nset]
-            assert L.cot_conv1x1_forward(P(x), None, Ci, P(w), None, P(y), N, Ci, Co, HW, BF, None) == 0, L.cot_last_error()
-
-        def dgr(i):
-            x, gy, y, gx = sets[i % nset]
-            assert L.cot_conv1x1_backward_data(P(gy), P(w), P(gx), None, Ci, 0, P(ws), N, Ci, Co, HW, BF, None) == 0, L.cot_last_error()
-        res.append((timeit(fwd), timeit(dgr)))
-    L.cot_set_tuning(24, 0)
+            def dgr(i):
+                x, gy, y, gx = sets[i % nset]
+                assert L.cot_conv1x1_backward_data(P(gy), P(w), P(gx), None, Ci, 0, P(ws), N, Ci, Co, HW, BF, None) == 0, L.cot_last_error()
+            res.append((timeit(fwd), timeit(dgr)))
     print(f"{name:34s} " + " ".join(f"{f:4.1f}/{d:4.1f}" for f, d in res))

@@ -5,6 +5,7 @@ Interleaved rounds over the variants (cot_set_tuning), HIP events on the launch 
 exceed the 256 MiB Infinity Cache ("cold") or one set ("hot").  Prints median-of-rounds per variant.
 """
 import argparse
+import contextlib
 import ctypes
 import json
 import os
@@ -39,35 +40,35 @@ def main():
     stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     print("xchg probe mode:", L.cot_xchg_mode(), flush=True)
     VAR = {
-        "v1": [(0, 1)], "v2dpp": [(0, 2), (3, 0)], "v2shfl": [(0, 2), (3, 1)],
-        "v2dpp_fP4": [(0, 2), (3, 0), (1, 4)], "v2dpp_bP2": [(0, 2), (3, 0), (2, 2)],
-        "v2dpp_fP2": [(0, 2), (3, 0), (1, 2)],
-        "v2": [(0, 2), (1, 4)], "v2_fP8": [(0, 2), (1, 8)],
-        "v3": [(0, 3), (1, 4), (4, 4)], "v3_fP8": [(0, 3), (1, 8), (4, 4)], "v3_jp2": [(0, 3), (1, 4), (4, 2)],
-        "v3_jp8": [(0, 3), (1, 8), (4, 8)], "v3_bP2": [(0, 3), (1, 4), (2, 2), (4, 4)],
-        "v3d": [(0, 3)], "v3d_nw8": [(0, 3), (5, 8)], "v3d_pad16": [(0, 3), (6, 16)], "v3d_pad32": [(0, 3), (6, 32)],
-        "v3d_pad56": [(0, 3), (6, 56)], "v3d_nw8_pad32": [(0, 3), (5, 8), (6, 32)], "v3d_bP4": [(0, 3), (2, 4)],
-        "v3d_bP4_pad32": [(0, 3), (2, 4), (6, 32)],
-        "v3d_xcd": [(0, 3), (7, 1)], "v3d_split": [(0, 3), (8, 1)], "v3d_xcd_split": [(0, 3), (7, 1), (8, 1)],
-        "v3d_jp8": [(0, 3), (4, 8)], "v3d_jp2": [(0, 3), (4, 2)],
+        "v1": dict(AGG_VERSION=1), "v2dpp": dict(AGG_VERSION=2, AGG_XCHG=0), "v2shfl": dict(AGG_VERSION=2, AGG_XCHG=1),
+        "v2dpp_fP4": dict(AGG_VERSION=2, AGG_XCHG=0, AGG_PPL_FWD=4), "v2dpp_bP2": dict(AGG_VERSION=2, AGG_XCHG=0, AGG_PPL_BWD=2),
+        "v2dpp_fP2": dict(AGG_VERSION=2, AGG_XCHG=0, AGG_PPL_FWD=2),
+        "v2": dict(AGG_VERSION=2, AGG_PPL_FWD=4), "v2_fP8": dict(AGG_VERSION=2, AGG_PPL_FWD=8),
+        "v3": dict(AGG_VERSION=3, AGG_PPL_FWD=4, AGG_V3_GROUPS=4), "v3_fP8": dict(AGG_VERSION=3, AGG_PPL_FWD=8, AGG_V3_GROUPS=4), "v3_jp2": dict(AGG_VERSION=3, AGG_PPL_FWD=4, AGG_V3_GROUPS=2),
+        "v3_jp8": dict(AGG_VERSION=3, AGG_PPL_FWD=8, AGG_V3_GROUPS=8), "v3_bP2": dict(AGG_VERSION=3, AGG_PPL_FWD=4, AGG_PPL_BWD=2, AGG_V3_GROUPS=4),
+        "v3d": dict(AGG_VERSION=3), "v3d_nw8": dict(AGG_VERSION=3, AGG_V3_WAVES=8), "v3d_pad16": dict(AGG_VERSION=3, AGG_V3_LDS_KIB=16), "v3d_pad32": dict(AGG_VERSION=3, AGG_V3_LDS_KIB=32),
+        "v3d_pad56": dict(AGG_VERSION=3, AGG_V3_LDS_KIB=56), "v3d_nw8_pad32": dict(AGG_VERSION=3, AGG_V3_WAVES=8, AGG_V3_LDS_KIB=32), "v3d_bP4": dict(AGG_VERSION=3, AGG_PPL_BWD=4),
+        "v3d_bP4_pad32": dict(AGG_VERSION=3, AGG_PPL_BWD=4, AGG_V3_LDS_KIB=32),
+        "v3d_xcd": dict(AGG_VERSION=3, AGG_V3_XCD=1), "v3d_split": dict(AGG_VERSION=3, AGG_BWD_SPLIT=1), "v3d_xcd_split": dict(AGG_VERSION=3, AGG_V3_XCD=1, AGG_BWD_SPLIT=1),
+        "v3d_jp8": dict(AGG_VERSION=3, AGG_V3_GROUPS=8), "v3d_jp2": dict(AGG_VERSION=3, AGG_V3_GROUPS=2),
         # automatic dispatch (key 0 = 0): bf16 fused backward on the packed dot-product kernel (agg_dot2.hip); keys 30 / 32 / 33 =
         # channel groups per LDS phase, waves per workgroup, SAFE operand masking; "lds" = the same dispatch with it off
-        "lds": [(29, 0)], "dot2": [],
+        "lds": dict(DOT2=0), "dot2": dict(),
         # automatic dispatch with the forward's pixels per lane / waves per workgroup changed (round 6 re-check of the small planes)
-        "fP2": [(1, 2)], "fP8": [(1, 8)], "nw8": [(5, 8)], "fP2_nw8": [(1, 2), (5, 8)], "fP1": [(1, 1)],
+        "fP2": dict(AGG_PPL_FWD=2), "fP8": dict(AGG_PPL_FWD=8), "nw8": dict(AGG_V3_WAVES=8), "fP2_nw8": dict(AGG_PPL_FWD=2, AGG_V3_WAVES=8), "fP1": dict(AGG_PPL_FWD=1),
     }
     for jp in (2, 4, 8):
         for nw in (2, 4, 7):
             for safe in (0, 1):
-                VAR[f"d2_jp{jp}_nw{nw}_s{safe}"] = [(30, jp), (32, nw), (33, safe)]
-                VAR[f"d2_jp{jp}_nw{nw}_s{safe}_sb"] = [(30, jp), (32, nw), (33, safe), (34, 0)]
-                VAR[f"d2_jp{jp}_nw{nw}_s{safe}_xcd"] = [(30, jp), (32, nw), (33, safe), (31, 1)]
+                VAR[f"d2_jp{jp}_nw{nw}_s{safe}"] = dict(DOT2_GROUPS=jp, DOT2_WAVES=nw, DOT2_SAFE=safe)
+                VAR[f"d2_jp{jp}_nw{nw}_s{safe}_sb"] = dict(DOT2_GROUPS=jp, DOT2_WAVES=nw, DOT2_SAFE=safe, DOT2_DOUBLE_BUFFER=0)
+                VAR[f"d2_jp{jp}_nw{nw}_s{safe}_xcd"] = dict(DOT2_GROUPS=jp, DOT2_WAVES=nw, DOT2_SAFE=safe, DOT2_XCD=1)
+
+    variant = contextlib.ExitStack()
 
     def set_variant(name):
-        for k, v in ((0, 0), (1, 4), (2, 2), (3, -1), (4, 0), (5, 4), (6, 0), (7, -1), (8, 0), (29, 1), (30, 0), (31, -1), (32, 0), (33, 1), (34, 1)):
-            L.cot_set_tuning(k, v)
-        for k, v in VAR[name]:
-            L.cot_set_tuning(k, v)
+        variant.close()  # (the keys of the variant before: back to what they were)
+        variant.enter_context(_lib.tuned(L, **VAR[name]))
 
     rows = []
     for dname in args.dtypes.split(","):
@@ -142,8 +143,7 @@ def main():
                 print(msg, flush=True)
             del sets
             torch.cuda.empty_cache()
-    for k, v in ((0, 0), (1, 4), (2, 2), (3, -1), (4, 0), (5, 4), (6, 0), (7, -1), (8, 0), (29, 1), (30, 0), (31, -1), (32, 0), (33, 1), (34, 1)):
-        L.cot_set_tuning(k, v)
+    variant.close()
     if args.out:
         json.dump(rows, open(args.out, "w"), indent=1)
 

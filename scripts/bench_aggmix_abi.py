@@ -38,7 +38,7 @@ def algorithmic_bytes(N, esize):
             "backward_weight": esize * N * hw * (2 * C + C + 34 * WC)}
 
 
-def measure(batch=64, dtype=torch.bfloat16, iters=20, rounds=5, cold=True, tuning=()):
+def measure(batch=64, dtype=torch.bfloat16, iters=20, rounds=5, cold=True, tuning={}):
     """-> {direction: {"us": median over rounds of the mean launch time, "GBps", "frac", "kernel"}}"""
     L = _lib.lib()
     dev = torch.device("cuda:0")
@@ -55,9 +55,7 @@ def measure(batch=64, dtype=torch.bfloat16, iters=20, rounds=5, cold=True, tunin
         sets.append((x, w1, w2, gout, torch.empty_like(gout), torch.empty_like(x), torch.empty_like(w1), torch.empty_like(w2)))
     geo = _lib.AggGeom(batch, C, H, W, HEADS, WC, 3, 3, 1, 1, 1, 1, 1, 1)
     dt = _lib.dtype_code(dtype)
-    for k, v in tuning:
-        L.cot_set_tuning(k, v)
-    try:
+    with _lib.tuned(L, **tuning):
         calls = {
             "forward": lambda s: L.cot_aggmix_forward(P(s[0]), P(s[1]), P(s[2]), P(s[4]), ctypes.byref(geo), 2, 2, dt, stream),
             "backward_input": lambda s: L.cot_aggmix_backward_input(P(s[3]), P(s[1]), P(s[2]), P(s[5]), ctypes.byref(geo), 2, 2, 0, dt, stream),
@@ -84,9 +82,6 @@ def measure(batch=64, dtype=torch.bfloat16, iters=20, rounds=5, cold=True, tunin
             out[name] = {"us": round(us, 2), "GBps": round(gbs, 1), "frac": round(gbs / PEAK_GBS, 4), "kernel": kernel,
                          "algorithmic_bytes": alg[name]}
         return out
-    finally:
-        for k, _ in tuning:
-            L.cot_set_tuning(k, {51: 0, 52: 256, 53: 0}.get(k, 0))
 
 
 def main():
@@ -96,18 +91,18 @@ def main():
     ap.add_argument("--lanes", default="256")
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--generic", action="store_true", help="also time the one-lane-per-element kernels (cot_set_tuning(51, 1))")
+    ap.add_argument("--generic", action="store_true", help="also time the one-lane-per-element kernels (MIX_GENERIC=1)")
     ap.add_argument("--hot", action="store_true")
-    ap.add_argument("--ppl", default="0", help="pixels per lane to try (cot_set_tuning(53, .)); 0 = the planner's choice")
+    ap.add_argument("--ppl", default="0", help="pixels per lane to try (MIX_PPL); 0 = the planner's choice")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     res = {}
     for dn in args.dtypes.split(","):
         dtype = {"bf16": torch.bfloat16, "fp32": torch.float32, "fp16": torch.float16}[dn]
-        variants = [(f"tile_lanes{l}" + (f"_P{pp}" if pp else ""), ((52, int(l)), (53, int(pp))))
+        variants = [(f"tile_lanes{l}" + (f"_P{pp}" if pp else ""), dict(MIX_LANES=int(l), MIX_PPL=int(pp)))
                     for l in args.lanes.split(",") for pp in args.ppl.split(",")]
         if args.generic:
-            variants.append(("generic", ((51, 1),)))
+            variants.append(("generic", dict(MIX_GENERIC=1)))
         for vn, tuning in variants:
             r = measure(args.batch, dtype, args.iters, args.rounds, not args.hot, tuning)
             res[f"{dn}|{vn}"] = r

@@ -25,9 +25,8 @@ def main():
     ap.add_argument("--no-check", action="store_true")
     args = ap.parse_args()
     L = _lib.lib()
-    for kv in filter(None, args.tune.split(",")):
-        k, v = kv.split("=")
-        assert L.cot_set_tuning(int(k), int(v)) == 0
+    for k, v in _lib.parse_tuning(args.tune):
+        assert L.cot_set_tuning(k, v) == 0
     dev = torch.device("cuda:0")
     st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     P = lambda t: ctypes.c_void_p(t.data_ptr())

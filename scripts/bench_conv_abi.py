@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Device time of the 1x1-convolution entry points straight through the C ABI (no autograd, no allocator in the loop):
 forward / data gradient / weight gradient at every 1x1 shape of CoTNet-50 (B = 80, bf16), first-generation kernels
-(cot_set_tuning(15, 0)) against the LDS-pipelined ones (15, 1).  HIP events around `iters` back-to-back launches on
+(CONV_LDS=0) against the LDS-pipelined ones (CONV_LDS=1).  HIP events around `iters` back-to-back launches on
 rotating buffer sets (cold) -- per-launch time, fraction of the 8 TB/s HBM roofline for the algorithmic bytes
 2*N*HW*(Ci+Co) (+ weights), and MFMA TFLOP/s.
 
@@ -59,9 +59,8 @@ def main():
     ap.add_argument("--tune", default="", help="KEY=VALUE[,KEY=VALUE...] for cot_set_tuning (A/B)")
     args = ap.parse_args()
     L = _lib.lib()
-    for kv in filter(None, args.tune.split(",")):
-        key, value = kv.split("=")
-        assert L.cot_set_tuning(int(key), int(value)) == 0
+    for key, value in _lib.parse_tuning(args.tune):
+        assert L.cot_set_tuning(key, value) == 0
     dev = torch.device("cuda:0")
     st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     BF = _lib.COT_BF16
@@ -116,22 +115,22 @@ def main():
 
         outs = {}
         for gen in [int(m) for m in args.modes.split(",")]:
-            assert L.cot_set_tuning(15, gen) == 0
-            tf, td, tw = timed(fwd), timed(dgrad), timed(wgrad)
-            outs[gen] = sets[0][2].float().clone()
-            pf, pd, pw = (100 * act_bytes / (t * 1e-6) / 8e12 for t in (tf, td, tw))
-            print(f"{name:26s} {gen:3d} {tf:8.1f} {pf:6.1f} {flops / (tf * 1e-6) / 1e12:6.0f} | {td:8.1f} {pd:6.1f} | {tw:8.1f} {pw:6.1f}",
-                  flush=True)
-            rows.append({"shape": name.strip(), "gen": gen, "fwd_us": round(tf, 2), "dgrad_us": round(td, 2),
-                         "wgrad_us": round(tw, 2), "fwd_frac_hbm": round(pf / 100, 4), "dgrad_frac_hbm": round(pd / 100, 4),
-                         "wgrad_frac_hbm": round(pw / 100, 4), "fwd_tflops": round(flops / (tf * 1e-6) / 1e12, 1)})
+            with _lib.tuned(L, CONV_LDS=gen):
+                tf, td, tw = timed(fwd), timed(dgrad), timed(wgrad)
+                outs[gen] = sets[0][2].float().clone()
+                pf, pd, pw = (100 * act_bytes / (t * 1e-6) / 8e12 for t in (tf, td, tw))
+                print(f"{name:26s} {gen:3d} {tf:8.1f} {pf:6.1f} {flops / (tf * 1e-6) / 1e12:6.0f} | {td:8.1f} {pd:6.1f} | {tw:8.1f} {pw:6.1f}",
+                      flush=True)
+                rows.append({"shape": name.strip(), "gen": gen, "fwd_us": round(tf, 2), "dgrad_us": round(td, 2),
+                             "wgrad_us": round(tw, 2), "fwd_frac_hbm": round(pf / 100, 4), "dgrad_frac_hbm": round(pd / 100, 4),
+                             "wgrad_frac_hbm": round(pw / 100, 4), "fwd_tflops": round(flops / (tf * 1e-6) / 1e12, 1)})
         if len(outs) == 2:  # both generations on the last buffer set: same result up to summation order
             fwd(0)
             torch.cuda.synchronize()
             d = (outs[0] - outs[1]).abs().max().item()
             if d > 0.05 * outs[0].abs().max().item() + 1e-3:
                 print(f"   !! generations disagree: max|diff| {d:.3e}")
-        L.cot_set_tuning(15, 1)
+        L.cot_set_tuning(_lib.TUNE.CONV_LDS, 1)
     # ---- grouped 3x3 key-embed convolutions (CoTNet-50: groups 4)
     print(f"\n{'grouped 3x3':26s} {'gen':3s} {'fwd us':>8s} {'%HBM':>6s} {'TF/s':>6s} | {'dgrad us':>8s} {'%HBM':>6s} | {'wgrad us':>8s} {'%HBM':>6s}")
     for C, H in ((64, 56), (128, 28), (256, 14), (512, 7)):
@@ -174,15 +173,14 @@ def main():
             assert L.cot_conv3x3g_backward_weight(P(gy), P(x), P(gw3), P(masks), P(ws3), N, C, C, G, H, H, BF, st) == 0
 
         for gen in [int(m) for m in args.modes.split(",")]:
-            assert L.cot_set_tuning(15, gen) == 0
-            tf, td, tw = timed3(f3), timed3(d3), timed3(w3g)
-            pf, pd, pw = (100 * act_bytes / (t * 1e-6) / 8e12 for t in (tf, td, tw))
-            name = f"C{C} g4 {H}x{H}"
-            print(f"{name:26s} {gen:3d} {tf:8.1f} {pf:6.1f} {flops / (tf * 1e-6) / 1e12:6.0f} | {td:8.1f} {pd:6.1f} | {tw:8.1f} {pw:6.1f}", flush=True)
-            rows.append({"shape": "conv3x3g " + name, "gen": gen, "fwd_us": round(tf, 2), "dgrad_us": round(td, 2),
-                         "wgrad_us": round(tw, 2), "fwd_frac_hbm": round(pf / 100, 4), "dgrad_frac_hbm": round(pd / 100, 4),
-                         "wgrad_frac_hbm": round(pw / 100, 4), "fwd_tflops": round(flops / (tf * 1e-6) / 1e12, 1)})
-        L.cot_set_tuning(15, 1)
+            with _lib.tuned(L, CONV_LDS=gen):
+                tf, td, tw = timed3(f3), timed3(d3), timed3(w3g)
+                pf, pd, pw = (100 * act_bytes / (t * 1e-6) / 8e12 for t in (tf, td, tw))
+                name = f"C{C} g4 {H}x{H}"
+                print(f"{name:26s} {gen:3d} {tf:8.1f} {pf:6.1f} {flops / (tf * 1e-6) / 1e12:6.0f} | {td:8.1f} {pd:6.1f} | {tw:8.1f} {pw:6.1f}", flush=True)
+                rows.append({"shape": "conv3x3g " + name, "gen": gen, "fwd_us": round(tf, 2), "dgrad_us": round(td, 2),
+                             "wgrad_us": round(tw, 2), "fwd_frac_hbm": round(pf / 100, 4), "dgrad_frac_hbm": round(pd / 100, 4),
+                             "wgrad_frac_hbm": round(pw / 100, 4), "fwd_tflops": round(flops / (tf * 1e-6) / 1e12, 1)})
     if args.json:
         json.dump(rows, open(args.json, "w"), indent=1)
 

@@ -44,8 +44,8 @@ for G, HW in ((8, 3136), (16, 784), (32, 196), (64, 49)):
     dg, db = torch.empty(C, device="cuda").bfloat16(), torch.empty(C, device="cuda").bfloat16()
     ws = torch.empty(2 * B * C, device="cuda")
     for tune in TUNES:
-        if tune:
-            assert L.cot_set_tuning(int(tune.split("=")[0]), int(tune.split("=")[1])) == 0
+        for key, value in _lib.parse_tuning(tune):
+            assert L.cot_set_tuning(key, value) == 0
 
         def f(i):
             x, dy, y, dx = sets[i % 4]

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
-"""3x3 / stride-2 poolings of a CoTNet-50 step through the C ABI (B = 80, bf16): plane-tile form (cot_set_tuning(27, 1), default)
-against one lane per pixel (27, 0); time per launch and % of the 8 TB/s roofline for the bytes the op must move.
+"""3x3 / stride-2 poolings of a CoTNet-50 step through the C ABI (B = 80, bf16): plane-tile form (POOL_TILE=1, default)
+against one lane per pixel (POOL_TILE=0); time per launch and % of the 8 TB/s roofline for the bytes the op must move.
 
     python scripts/bench_pool.py"""
 import ctypes
@@ -64,17 +64,16 @@ def main():
         for tag, fn, nb, outs in ((" fwd", fwd, fb, lambda: (y.clone(), taps.clone())), (" bwd", bwd, bb, lambda: (gx.clone(),))):
             res, t = [], []
             for tile in (0, 1):
-                assert L.cot_set_tuning(27, tile) == 0
-                it[0] = 0
-                if tag == " bwd" and name.startswith("max"):
-                    L.cot_maxpool3x3s2_forward_taps(P(xs[1]), P(y), P(taps), N * C, H, H, BF, st)
-                fn()
-                torch.cuda.synchronize()
-                res.append(outs())
-                t.append(timed(fn))
+                with _lib.tuned(L, POOL_TILE=tile):
+                    it[0] = 0
+                    if tag == " bwd" and name.startswith("max"):
+                        L.cot_maxpool3x3s2_forward_taps(P(xs[1]), P(y), P(taps), N * C, H, H, BF, st)
+                    fn()
+                    torch.cuda.synchronize()
+                    res.append(outs())
+                    t.append(timed(fn))
             same = all(torch.equal(a, b) for a, b in zip(*res))
             print(f"{name + tag:34s} {t[0]:13.1f} {t[1]:14.1f} {nb / (t[1] * 1e-6) / 8e12 * 100:6.1f}  {same}", flush=True)
-    L.cot_set_tuning(27, 1)
 
 
 if __name__ == "__main__":

@@ -42,8 +42,8 @@ for C, HW in ((64, 3136), (128, 784), (256, 196), (512, 49)):
     logT, glogT = torch.randn(2 * C, B, device="cuda").bfloat16(), torch.empty(2 * C, B, device="cuda").bfloat16()
     attn, ggapT = torch.empty(B * C * 2, device="cuda").bfloat16(), torch.randn(C, B, device="cuda").bfloat16()
     for tune in TUNES:
-        if tune:
-            assert L.cot_set_tuning(int(tune.split("=")[0]), int(tune.split("=")[1])) == 0
+        for key, value in _lib.parse_tuning(tune):
+            assert L.cot_set_tuning(key, value) == 0
 
         def f1(i):
             y, k, g, o1, o2 = sets[i % 4]

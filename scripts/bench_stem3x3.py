@@ -28,9 +28,8 @@ def timeit(fn, iters=10, warm=3):
 def main():
     dev = "cuda"
     from cotnet_amd import _lib
-    for kv in filter(None, os.environ.get("COT_TUNE", "").split(",")):  # e.g. COT_TUNE=15:0,39:0
-        k, v = kv.split(":")
-        _lib.lib().cot_set_tuning(int(k), int(v))
+    for k, v in _lib.parse_tuning(os.environ.get("COT_TUNE", "").replace(":", "=")):  # e.g. COT_TUNE=15:0,39:0
+        _lib.lib().cot_set_tuning(k, v)
     N = int(sys.argv[1]) if len(sys.argv) > 1 else 64
     torch.manual_seed(0)
     cases = [("3->64 s2 @320", nn.Conv2d(3, 64, 3, 2, 1, bias=False), (N, 3, 320, 320), False),

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""1x1 forward and data gradient through the C ABI under cot_set_tuning(23, value) against fp32 matmuls on the same bf16 operands
+"""1x1 forward and data gradient through the C ABI under cot_set_tuning(_lib.TUNE.CONV_LDS2_BITS, value) against fp32 matmuls on the same bf16 operands
 (device check for kernel forms that are not the default).   python scripts/check_fwd_variant.py 8"""
 import ctypes
 import os
@@ -12,7 +12,7 @@ from cotnet_amd import _lib  # noqa: E402
 
 tune = int(sys.argv[1]) if len(sys.argv) > 1 else 0
 L = _lib.lib()
-assert L.cot_set_tuning(23, tune) == 0
+assert L.cot_set_tuning(_lib.TUNE.CONV_LDS2_BITS, tune) == 0
 dev = torch.device("cuda:0")
 st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 P = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Weight gradient of the 1x1 convolution through the C ABI under a given cot_set_tuning(25, ...) value against an fp32
+"""Weight gradient of the 1x1 convolution through the C ABI under a given cot_set_tuning(_lib.TUNE.WGRAD2_BITS, ...) value against an fp32
 einsum on the same bf16 operands, at CoTNet-50's deep shapes (device check for A/B variants that are not the default).
 
     python scripts/check_wgrad_variant.py 128"""
@@ -16,7 +16,7 @@ from cotnet_amd import _lib  # noqa: E402
 def main():
     tune = int(sys.argv[1]) if len(sys.argv) > 1 else 0
     L = _lib.lib()
-    assert L.cot_set_tuning(25, tune) == 0
+    assert L.cot_set_tuning(_lib.TUNE.WGRAD2_BITS, tune) == 0
     dev = torch.device("cuda:0")
     st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     P = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Streaming BatchNorm+ReLU kernels through the C ABI (B = 80, bf16) as a function of the number of workgroups they aim for
-(cot_set_tuning(28, target): channels x batch chunks), next to the channel-resident kernels where those exist.  Cold buffers.
+(BN_SPLIT_TARGET=target: channels x batch chunks), next to the channel-resident kernels where those exist.  Cold buffers.
 
     python scripts/ubench_bn_split.py"""
 import ctypes
@@ -37,31 +37,29 @@ def main():
         mean, rstd, dg, db = (torch.empty(C, device=dev) for _ in range(4))
         res = {}
         for mode, target in [(1, 1024)] + [(0, t) for t in TARGETS]:
-            assert L.cot_set_tuning(21, mode) == 0 and L.cot_set_tuning(28, target) == 0
-            ws = torch.empty(int(L.cot_bn_act_workspace(N, C)), device=dev)
+            with _lib.tuned(L, BN_CHAN=mode, BN_SPLIT_TARGET=target):  # (sizes the workspace)
+                ws = torch.empty(int(L.cot_bn_act_workspace(N, C)), device=dev)
 
-            def fwd(i):
-                x, y, dy = sets[i % nset]
-                assert L.cot_bn_act_forward(P(x), None, P(y), P(gamma), P(beta), P(mean), P(rstd), None, None, None, P(ws), N, C, HW,
-                                            1e-5, 0.1, 1, BF, st) == 0, L.cot_last_error()
+                def fwd(i):
+                    x, y, dy = sets[i % nset]
+                    assert L.cot_bn_act_forward(P(x), None, P(y), P(gamma), P(beta), P(mean), P(rstd), None, None, None, P(ws), N, C, HW,
+                                                1e-5, 0.1, 1, BF, st) == 0, L.cot_last_error()
 
-            def bwd(i):
-                x, y, dy = sets[i % nset]
-                assert L.cot_bn_act_backward(P(dy), P(x), None, P(dx), None, P(gamma), P(beta), P(mean), P(rstd), P(dg), P(db), P(ws),
-                                             N, C, HW, 1, BF, st) == 0, L.cot_last_error()
-            for fn in (fwd, bwd):
-                for i in range(3):
-                    fn(i)
-                torch.cuda.synchronize()
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                for i in range(12):
-                    fn(i)
-                e1.record()
-                torch.cuda.synchronize()
-                res[(mode, target, fn.__name__)] = e0.elapsed_time(e1) / 12 * 1e3
-        L.cot_set_tuning(21, 1)
-        L.cot_set_tuning(28, 1024)
+                def bwd(i):
+                    x, y, dy = sets[i % nset]
+                    assert L.cot_bn_act_backward(P(dy), P(x), None, P(dx), None, P(gamma), P(beta), P(mean), P(rstd), P(dg), P(db), P(ws),
+                                                 N, C, HW, 1, BF, st) == 0, L.cot_last_error()
+                for fn in (fwd, bwd):
+                    for i in range(3):
+                        fn(i)
+                    torch.cuda.synchronize()
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    for i in range(12):
+                        fn(i)
+                    e1.record()
+                    torch.cuda.synchronize()
+                    res[(mode, target, fn.__name__)] = e0.elapsed_time(e1) / 12 * 1e3
         keys = [(1, 1024)] + [(0, t) for t in TARGETS]
         print(f"{C:4d} x {H:3d}^2 {nbytes / 1e6:6.1f} | " + " ".join(f"{res[k + ('fwd',)]:7.1f}" for k in keys) + " | " +
               " ".join(f"{res[k + ('bwd',)]:7.1f}" for k in keys), flush=True)

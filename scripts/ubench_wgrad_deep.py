@@ -14,9 +14,8 @@ from cotnet_amd import _lib  # noqa: E402
 SHAPES = [("s3 conv1 1024->256@14", 1024, 256, 14), ("s3 embed0 512->128@14", 512, 128, 14), ("s3 conv1x1 256->256@14", 256, 256, 14),
           ("s3 conv3 256->1024@14", 256, 1024, 14), ("s4 conv1 2048->512@7", 2048, 512, 7), ("s4 embed0 1024->256@7", 1024, 256, 7),
           ("s4 conv1x1 512->512@7", 512, 512, 7), ("s4 conv3 512->2048@7", 512, 2048, 7)]
-CONFIGS = [("reg auto", {}), ("reg S=2", {11: -2}), ("reg S=4", {11: -4}), ("reg S=8", {11: -8}), ("reg S=16", {11: -16}),
-           ("reg S=32", {11: -32}), ("lds 25%", {17: 8, 20: 25}), ("lds 100%", {17: 8, 20: 100}), ("lds 400%", {17: 8, 20: 400}),
-           ("lds 1600%", {17: 8, 20: 1600})]
+CONFIGS = [("reg auto", {})] + [(f"reg S={s}", dict(C1_WGRAD_WAVES=-s)) for s in (2, 4, 8, 16, 32)] + \
+          [(f"lds {pct}%", dict(CONV_LDS_BITS=8, WGRAD_LDS_CAP_PCT=pct)) for pct in (25, 100, 400, 1600)]
 
 
 def P(t):
@@ -38,32 +37,28 @@ def main():
         ref = None
         out = []
         for cname, keys in CONFIGS:
-            for k, v in keys.items():
-                assert L.cot_set_tuning(k, v) == 0
-
-            def run(i):
-                x, gy = sets[i % nset]
-                rc = L.cot_conv1x1_backward_weight(P(gy), P(x), None, Ci, P(gw), None, P(ws), N, Ci, Co, HW, BF, st)
-                assert rc == 0, L.cot_last_error()
-            for i in range(3):
-                run(i)
-            torch.cuda.synchronize()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for i in range(16):
-                run(i)
-            e1.record()
-            torch.cuda.synchronize()
-            out.append(e0.elapsed_time(e1) / 16 * 1e3)
-            run(0)
-            torch.cuda.synchronize()
-            g = gw.float().clone()
-            if ref is None:
-                ref = g
-            elif (g - ref).abs().max() > 0.03 * ref.abs().max():
-                out[-1] = -out[-1]  # flagged: result differs from the first configuration
-            for k in keys:
-                L.cot_set_tuning(k, 2048 if k == 11 else 0)
+            with _lib.tuned(L, **keys):
+                def run(i):
+                    x, gy = sets[i % nset]
+                    rc = L.cot_conv1x1_backward_weight(P(gy), P(x), None, Ci, P(gw), None, P(ws), N, Ci, Co, HW, BF, st)
+                    assert rc == 0, L.cot_last_error()
+                for i in range(3):
+                    run(i)
+                torch.cuda.synchronize()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for i in range(16):
+                    run(i)
+                e1.record()
+                torch.cuda.synchronize()
+                out.append(e0.elapsed_time(e1) / 16 * 1e3)
+                run(0)
+                torch.cuda.synchronize()
+                g = gw.float().clone()
+                if ref is None:
+                    ref = g
+                elif (g - ref).abs().max() > 0.03 * ref.abs().max():
+                    out[-1] = -out[-1]  # flagged: result differs from the first configuration
         print(f"{name:26s} " + " ".join(f"{t:10.1f}" for t in out), flush=True)
 
 

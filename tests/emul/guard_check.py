@@ -126,20 +126,19 @@ def aggregation(N, C, H, W, dtype):
     assert E.cot_agg_backward(P(g), P(x), P(w), P(gx), P(gw), ct.byref(geom), dt, 0, None) == 0
 
 
-def bn_act(N, C, H, W, dtype, fold):
-    assert E.cot_set_tuning(12, fold) == 0
-    HW = H * W
-    x, res, dy = (guarded(torch.randn(N, C, H, W).to(dtype)) for _ in range(3))
-    y, dx, dres = (guarded(torch.empty(N, C, H, W).to(dtype)) for _ in range(3))
-    ga, be, mean, rstd, rm, rv, dg, db = (guarded(torch.ones(C)) for _ in range(8))
-    nbt = torch.zeros((), dtype=torch.int64)
-    ws = torch.empty(E.cot_bn_act_workspace(N, C))
-    dt = _lib.dtype_code(dtype)
-    assert E.cot_bn_act_forward(P(x), P(res), P(y), P(ga), P(be), P(mean), P(rstd), P(rm), P(rv), P(nbt), P(ws), N, C, HW,
-                                1e-5, 0.1, 1, dt, None) == 0
-    assert E.cot_bn_act_backward(P(dy), P(x), P(y), P(dx), P(dres), P(ga), P(be), P(mean), P(rstd), P(dg), P(db), P(ws), N,
-                                 C, HW, 1, dt, None) == 0
-    assert E.cot_set_tuning(12, 0) == 0
+def bn_act(N, C, H, W, dtype, fold, chan):
+    with _lib.tuned(E, BN_FOLD=fold, BN_CHAN=chan):
+        HW = H * W
+        x, res, dy = (guarded(torch.randn(N, C, H, W).to(dtype)) for _ in range(3))
+        y, dx, dres = (guarded(torch.empty(N, C, H, W).to(dtype)) for _ in range(3))
+        ga, be, mean, rstd, rm, rv, dg, db = (guarded(torch.ones(C)) for _ in range(8))
+        nbt = torch.zeros((), dtype=torch.int64)
+        ws = torch.empty(E.cot_bn_act_workspace(N, C))
+        dt = _lib.dtype_code(dtype)
+        assert E.cot_bn_act_forward(P(x), P(res), P(y), P(ga), P(be), P(mean), P(rstd), P(rm), P(rv), P(nbt), P(ws), N, C, HW,
+                                    1e-5, 0.1, 1, dt, None) == 0
+        assert E.cot_bn_act_backward(P(dy), P(x), P(y), P(dx), P(dres), P(ga), P(be), P(mean), P(rstd), P(dg), P(db), P(ws), N,
+                                     C, HW, 1, dt, None) == 0
 
 
 def radix(N, C, H, W, dtype):
@@ -193,10 +192,9 @@ def stem(N, H, W):
 
 if __name__ == "__main__":
     torch.manual_seed(0)
-    E.cot_set_tuning(17, 8)  # also the general LDS weight-gradient kernel (2-byte-aligned DMA sources, tensor-end path)
-    for shape in [(8, 16, 80, 7, 7, 0), (3, 64, 72, 14, 14, 32), (2, 40, 24, 6, 6, 0)]:
-        conv1x1(*shape)
-    E.cot_set_tuning(17, 0)
+    with _lib.tuned(E, CONV_LDS_BITS=8):  # also the general LDS weight-gradient kernel (2-byte-aligned DMA sources, tensor-end path)
+        for shape in [(8, 16, 80, 7, 7, 0), (3, 64, 72, 14, 14, 32), (2, 40, 24, 6, 6, 0)]:
+            conv1x1(*shape)
     # tensors whose byte size is a multiple of 16 keep the 16-byte base alignment the ABI asks for
     for shape in [(2, 64, 32, 8, 16, 0), (1, 40, 72, 12, 12, 0), (2, 32, 24, 14, 14, 0), (8, 16, 80, 7, 7, 0),
                   (2, 48, 40, 8, 8, 16), (8, 24, 16, 7, 7, 8), (8, 8, 8, 1, 1, 0),
@@ -233,8 +231,7 @@ if __name__ == "__main__":
         for shape in [(8, 8, 7, 7), (4, 16, 14, 14), (2, 8, 8, 8), (8, 8, 1, 1)]:
             for fold in (0, 1):
                 for chan in (0, 1):  # streaming kernels, then the channel-resident ones
-                    E.cot_set_tuning(21, chan)
-                    bn_act(*shape, dtype, fold)
+                    bn_act(*shape, dtype, fold, chan)
             radix(*shape, dtype)
         for shape in [(2, 4, 8, 8), (1, 8, 7, 7), (2, 4, 5, 9), (8, 2, 1, 1)]:
             pooling(*shape, dtype)

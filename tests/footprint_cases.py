@@ -163,7 +163,7 @@ class Recording:
         if sym is not None and sym[0] is ctypes.c_int and name not in _lib.NOT_STATUS:
             if not (soft and rc == _lib.COT_ERR_UNSUPPORTED):
                 assert rc == 0, (name, rc, self._L.cot_last_error())
-            if self._arena is not None and name != "cot_set_tuning":
+            if self._arena is not None and not name.endswith("_tuning"):
                 self._arena.kernels.append((name, rc, self._L.cot_last_kernel() if rc == 0 else b""))
         return rc
 
@@ -195,22 +195,6 @@ def run_case(L, case, args=(), base=0, names=None):
     return arena
 
 
-class tuned:
-    """cot_set_tuning(key, value) for the block, the default restored afterwards (workspaces are sized inside the block)"""
-    DEFAULTS = {10: 0, 11: 2048, 12: 1, 18: 256, 21: 1, 25: 0, 27: 1, 29: 1, 41: 1, 49: 1, 50: 1, 8: 0}
-
-    def __init__(self, L, **keys):
-        self.L, self.keys = L, {int(k[1:]): v for k, v in keys.items()}
-
-    def __enter__(self):
-        for k, v in self.keys.items():
-            self.L.cot_set_tuning(k, v)
-
-    def __exit__(self, *exc):
-        for k in self.keys:
-            self.L.cot_set_tuning(k, self.DEFAULTS[k])
-
-
 def _gen(*seed):
     return torch.Generator().manual_seed(sum((i + 1) * int(s) for i, s in enumerate(seed)) + 1)
 
@@ -239,11 +223,11 @@ def case_agg(L, A, N, C, H, W, dtype):
     L.cot_agg_backward_weight(P(go), P(x), P(gw), G, d, 0, None)
     for want_gx, want_gw, split in ((1, 1, 0), (1, 0, 0), (0, 1, 0), (1, 1, 1)):  # (split: tuning key 8, two launches)
         gx, gw = A.o(x.shape, dtype) if want_gx else None, A.o(w.shape, dtype) if want_gw else None
-        with tuned(L, k8=split):
+        with _lib.tuned(L, AGG_BWD_SPLIT=split):
             L.cot_agg_backward(P(go), P(x), P(w), P(gx), P(gw), G, d, 0, None)
     if dtype == BF16:  # (the fp32-unpacked LDS kernel behind the packed dot-product one)
         gx, gw = A.o(x.shape, dtype), A.o(w.shape, dtype)
-        with tuned(L, k29=0):
+        with _lib.tuned(L, DOT2=0):
             L.cot_agg_backward(P(go), P(x), P(w), P(gx), P(gw), G, d, 0, None)
     if (H, W) == (3, 10):  # (no LDS tile plan for this plane: refused before any launch, the caller composes softmax + cot_agg_forward)
         out, probs = A.i(_rn(g, N, C, H, W, dtype=dtype)), A.i(_rn(g, N, 1, wC, 9, H, W, dtype=dtype))  # (must stay as they are)
@@ -320,8 +304,7 @@ def case_aggmix(L, A, N, C, wC, H, W, heads, dtype):
     geo = _geom(N, C, H, W, heads, wC)
     G = ctypes.byref(geo)
     for flat in (0, 1):
-        L.cot_set_tuning(51, flat)
-        try:
+        with _lib.tuned(L, MIX_GENERIC=flat):
             out = A.o(go.shape, dtype)
             L.cot_aggmix_forward(P(x), P(w1), P(w2), P(out), G, 2, 2, d, None)
             for all_heads in (0, 1):
@@ -329,8 +312,6 @@ def case_aggmix(L, A, N, C, wC, H, W, heads, dtype):
                 L.cot_aggmix_backward_input(P(go), P(w1), P(w2), P(gx), G, 2, 2, all_heads, d, None)
             gw1, gw2 = A.o(w1.shape, dtype), A.o(w2.shape, dtype)
             L.cot_aggmix_backward_weight(P(go), P(x), P(gw1), P(gw2), G, 2, 2, d, None)
-        finally:
-            L.cot_set_tuning(51, 0)
 
 
 # ---------------------------------------------------------------------------------------------------------------- 1x1 convolutions
@@ -348,7 +329,7 @@ def case_conv1x1(L, A, N, Ci, Co, H, W, c1, dtype=BF16):
     gy = A.i(_rn(g, N, Co, H, W, dtype=dtype))
     for bias, rows in ((1, 0), (0, 2), (0, 4)):
         y = A.o((N, Co, H, W), dtype)
-        with tuned(L, k10=rows):
+        with _lib.tuned(L, C1_ROWS_PER_WAVE=rows):
             L.cot_conv1x1_forward(P(x1), P(x2), cc1, P(w), P(b) if bias else None, P(y), N, Ci, Co, HW, d, None)
     general = dtype == F32
     size = (lambda bias: L.cot_convg_workspace(N, Ci, Co, 1, HW, 1, 1)) if general else (lambda bias: L.cot_conv1x1_workspace(N, Ci, Co, HW, bias))
@@ -360,7 +341,7 @@ def case_conv1x1(L, A, N, Ci, Co, H, W, c1, dtype=BF16):
             gx2 = A.io(_rn(g, N, Ci - cc1, H, W, dtype=dtype)) if acc & 2 else A.o((N, Ci - cc1, H, W), dtype)
         L.cot_conv1x1_backward_data(P(gy), P(w), P(gx1), P(gx2), cc1, acc, P(ws), N, Ci, Co, HW, d, None)
     for bias, k11, k25 in ((1, 2048, 0), (0, -2, 0), (1, -3, 0), (0, 2048, 3 << 24), (1, 2048, 7 << 24)):
-        with tuned(L, k11=k11, k25=k25):
+        with _lib.tuned(L, C1_WGRAD_WAVES=k11, WGRAD2_BITS=k25):
             ws = A.w(size(bias))
             gw, gb = A.o((Co, Ci), dtype), A.o(Co, bdt) if bias else None
             L.cot_conv1x1_backward_weight(P(gy), P(x1), P(x2), cc1, P(gw), P(gb), P(ws), N, Ci, Co, HW, d, None)
@@ -424,7 +405,7 @@ def case_conv1x1g(L, A, N, Ci, Co, G, H, W, dtype):
         gx = A.io(_rn(g, N, Ci, H, W, dtype=dtype)) if acc else A.o(x.shape, dtype)
         L.cot_conv1x1g_backward_data(P(gy), P(w), P(gx), acc, N, Ci, Co, G, HW, d, None)
     for bias, k11 in ((1, 2048), (0, -2)):
-        with tuned(L, k11=k11):
+        with _lib.tuned(L, C1_WGRAD_WAVES=k11):
             ws = A.w(L.cot_convg_workspace(N, Ci, Co, G, HW, 1, 1))
             gw, gb = A.o(w.shape, dtype), A.o(Co, dtype) if bias else None
             L.cot_conv1x1g_backward_weight(P(gy), P(x), P(gw), P(gb), P(ws), N, Ci, Co, G, HW, d, None)
@@ -451,7 +432,7 @@ def case_conv3x3(L, A, N, C, G, H, W, dtype=BF16):
         gx = A.io(_rn(g, N, C, H, W, dtype=dtype)) if acc else A.o(x.shape, dtype)
         L.cot_conv3x3g_backward_data(P(gy), P(w), P(gx), acc, P(mk), P(ws), *geo, d, None)
     for k11, k25 in ((2048, 0), (-2, 0), (2048, 2 << 24), (2048, 7 << 24)):
-        with tuned(L, k11=k11, k25=k25):
+        with _lib.tuned(L, C1_WGRAD_WAVES=k11, WGRAD2_BITS=k25):
             ws, gw = A.w(size()), A.o(w.shape, dtype)
             L.cot_conv3x3g_backward_weight(P(gy), P(x), P(gw), P(mk), P(ws), *geo, d, None)
             for guard in (W + 1, 0):
@@ -482,7 +463,7 @@ def case_stem7(L, A, N, H, W, dtype):
     x, w = A.i(_rn(g, N, 3, H, W, dtype=dtype)), A.i(_rn(g, 64, 3, 7, 7, dtype=dtype, scale=1 / 12))
     gy = A.i(_rn(g, N, 64, Ho, Wo, dtype=dtype))
     for lds in (1, 0):
-        with tuned(L, k41=lds):
+        with _lib.tuned(L, STEM_LDS=lds):
             y = A.o(gy.shape, dtype)
             L.cot_stem7x7s2_forward(P(x), P(w), P(y), N, H, W, d, None)
     ws, gw = A.w(L.cot_stem7x7s2_workspace(N, H, W)), A.o(w.shape, dtype)
@@ -517,7 +498,7 @@ def case_pools(L, A, N, C, H, W, dtype):
     x = A.i(torch.relu(_rn(g, N, C, H, W)).to(dtype))  # (post-ReLU: ties at zero)
     gy = A.i(_rn(g, N, C, Ho, Wo, dtype=dtype))
     for blk in (1, 0):
-        with tuned(L, k27=blk):
+        with _lib.tuned(L, POOL_TILE=blk):
             y, gx = A.o(gy.shape, dtype), A.o(x.shape, dtype)
             L.cot_maxpool3x3s2_forward(P(x), P(y), planes, H, W, d, None)
             L.cot_maxpool3x3s2_backward(P(gy), P(x), P(gx), planes, H, W, d, None)
@@ -583,7 +564,7 @@ def case_tail_lay(L, A, N, C, H, W, k50):
     ain = A.i(torch.softmax(torch.randn(N, C, 2, generator=g), 2).bfloat16())
     both = lambda t: (A.i(t), A.i(_cm(t)))  # noqa: E731
     y, k, go = both(hy), both(hk), both(hg)
-    with tuned(L, k50=k50):
+    with _lib.tuned(L, RADIX_PACK7=k50):
         for b0, b1, b2 in itertools.product((0, 1), repeat=3):
             lay = b0 | (b1 << 1) | (b2 << 2)
             if not b2:
@@ -646,7 +627,7 @@ def case_gn9(L, A, N, G, H, W, dtype, k49=1):
     hx, hdy = _rn(g, N, C, H, W, dtype=dtype, scale=1.5, shift=0.3), _rn(g, N, C, H, W, dtype=dtype)
     x, dy = A.i(hx), A.i(hdy)
     gamma, beta = A.i(_rn(g, C, dtype=dtype, scale=0.3, shift=1.0)), A.i(_rn(g, C, dtype=dtype, scale=0.2))
-    with tuned(L, k49=k49):
+    with _lib.tuned(L, GN9_PACK=k49):
         y, mean, rstd = A.o(x.shape, dtype), A.o(N * G, F32), A.o(N * G, F32)
         L.cot_group_norm9_forward(P(x), P(gamma), P(beta), P(y), P(mean), P(rstd), N, C, HW, 1e-5, d, None)
         m_in, r_in = A.i(mean.clone()), A.i(rstd.clone())
@@ -681,7 +662,7 @@ def case_bn(L, A, N, C, H, W, dtype, k21, k12):
     gamma, beta = A.i(torch.rand(C, generator=g) + 0.5), A.i(0.2 * torch.randn(C, generator=g))
     ps = A.i((torch.rand(N, generator=g) < 0.7).float() / 0.7)
     run_m, run_v = A.i(0.3 * torch.randn(C, generator=g)), A.i(torch.rand(C, generator=g) + 0.5)
-    with tuned(L, k21=k21, k12=k12):
+    with _lib.tuned(L, BN_CHAN=k21, BN_FOLD=k12):
         nws = 4 * max(int(L.cot_bn_act_workspace(N, C)), 1)
         nb = int(L.cot_bn_relu_mask_bytes(N, C, HW, d))
 
@@ -871,7 +852,7 @@ EXEMPT = {
     "cot_conv3x3g_workspace": _QUERY, "cot_conv3x3g_packed_bytes": _QUERY, "cot_convg_workspace": _QUERY, "cot_conv1x1_lds_covers": _QUERY,
     "cot_bn_act_workspace": _QUERY, "cot_bn_relu_mask_bytes": _QUERY, "cot_conv1x1_stats_covers": _QUERY, "cot_bn_act_lay_covers": _QUERY,
     "cot_agg_rowstats_floats": _QUERY, "cot_agg_out_size": _QUERY,
-    "cot_set_tuning": _DEV, "cot_xchg_mode": _DEV + " (a 64-thread probe on library-owned memory)", "cot_launch_log": _DEV,
+    "cot_set_tuning": _DEV, "cot_get_tuning": _DEV, "cot_reset_tuning": _DEV, "cot_tuning_name": _DEV, "cot_xchg_mode": _DEV + " (a 64-thread probe on library-owned memory)", "cot_launch_log": _DEV,
     "cot_profile_begin": _DEV, "cot_profile_end": _DEV,
     "cot_local_relation_forward": "operands and outputs inside NaN margins, output margins checked: tests/test_fuzz_emulated.py case_local_relation (tests/test_fuzz_gpu.py on the device)",
     "cot_local_relation_backward": "operands and outputs inside NaN margins, output margins checked: tests/test_fuzz_emulated.py case_local_relation (tests/test_fuzz_gpu.py on the device)",

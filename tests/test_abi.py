@@ -127,13 +127,127 @@ sys.exit(1 if bad else 0)
 """
 
 
+def _child(script):
+    import subprocess
+    import sys
+    r = subprocess.run([sys.executable, "-c", script], cwd=ROOT, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+
+
 def test_tuning_keys():
     """cot_set_tuning takes every key in {0-34, 36-54} with the values 0 and 1 and refuses -1, 35 and 55 as unknown -- in a child
     process, so that the knobs it turns reach no other test"""
-    import subprocess
-    import sys
-    r = subprocess.run([sys.executable, "-c", _TUNING_KEYS_CHILD], cwd=ROOT, capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stdout + r.stderr
+    _child(_TUNING_KEYS_CHILD)
+
+
+def header_tuning_enum():
+    src = open(os.path.join(ROOT, "include", "cotnet_amd.h")).read()
+    body = re.search(r"enum cot_tuning_key \{(.*?)\};", re.sub(r"/\*.*?\*/", "", src, flags=re.S), flags=re.S).group(1)
+    return [(n, int(v)) for n, v in re.findall(r"\bCOT_TUNE_([A-Z0-9_]+)\s*=\s*(\d+)", body)]
+
+
+def test_tuning_names_match_the_header():
+    """every enumerator of enum cot_tuning_key is cot_tuning_name(value) in upper case behind the prefix; names and values are unique;
+    35 and 55 are no keys (nothing is set here: no child process needed)"""
+    L = _lib.lib()
+    enum = header_tuning_enum()
+    assert sorted(v for _, v in enum) == list(range(0, 35)) + list(range(36, 55))
+    assert len({n for n, _ in enum}) == len(enum)
+    for name, value in enum:
+        assert L.cot_tuning_name(value) == name.lower().encode(), (name, value)
+    assert L.cot_tuning_name(35) is None and L.cot_tuning_name(55) is None and L.cot_tuning_name(-1) is None
+    assert _lib.tuning_keys(L) == dict(enum)
+    assert _lib.TUNE.BN_FOLD == 12 and _lib.Tune(L).CONV_BIG_XSWZ == 48
+    assert _lib.parse_tuning("12=1,bn_chan=0, MIX_LANES=128") == [(12, 1), (21, 0), (52, 128)]
+
+
+_TUNING_RESET_CHILD = r"""
+import sys
+from cotnet_amd import _lib
+L = _lib.lib()
+KEYS = list(range(0, 35)) + list(range(36, 55))
+fresh = {k: _lib.get_tuning(L, k) for k in KEYS}
+bad = []
+for k, want in ((12, 1), (13, 4096), (18, 256), (21, 1), (48, 7), (52, 256)):  # the globals' initialisers, by name in the assertion
+    if fresh[k] != want:
+        bad.append(("default", L.cot_tuning_name(k), fresh[k], want))
+
+
+def idempotent(what):  # cot_set_tuning(k, cot_get_tuning(k)) changes nothing: what tuned()'s restore relies on
+    for k in KEYS:
+        v = _lib.get_tuning(L, k)
+        assert L.cot_set_tuning(k, v) == 0
+        if _lib.get_tuning(L, k) != v:
+            bad.append(("set(get)", what, L.cot_tuning_name(k), v, _lib.get_tuning(L, k)))
+
+
+idempotent("defaults")
+for value in (0, 1, 5, 300, -2):
+    for k in KEYS:
+        assert L.cot_set_tuning(k, value) == 0
+    idempotent(value)
+for value in (0, 1, 7):
+    for k in KEYS:
+        assert L.cot_set_tuning(k, value) == 0
+assert L.cot_reset_tuning() == 0
+for k in KEYS:
+    if _lib.get_tuning(L, k) != fresh[k]:
+        bad.append(("reset", L.cot_tuning_name(k), _lib.get_tuning(L, k), fresh[k]))
+print("BAD", bad)
+sys.exit(1 if bad else 0)
+"""
+
+
+def test_tuning_reset_and_idempotence():
+    """in a fresh process: keys 12, 13, 18, 21, 48, 52 read 1, 4096, 256, 1, 7, 256; cot_set_tuning(k, cot_get_tuning(k)) leaves every
+    key as it is, for the defaults and after every key was set to 0, 1, 5, 300, -2; after every key was set to 0, 1 and 7,
+    cot_reset_tuning puts each back to what the fresh process read"""
+    _child(_TUNING_RESET_CHILD)
+
+
+_TUNED_CHILD = r"""
+from cotnet_amd import _lib
+L = _lib.lib()
+T = _lib.TUNE
+get = lambda k: _lib.get_tuning(L, k)
+cache = _lib.register_cache({})
+assert (get(T.BN_FOLD), get(T.BN_CHAN), get(T.C1_WGRAD_WAVES)) == (1, 1, 2048)
+cache["shape"] = 1
+with _lib.tuned(L, BN_FOLD=0, C1_WGRAD_WAVES=-3):
+    assert not cache, "emptied on entry"
+    assert (get(T.BN_FOLD), get(T.C1_WGRAD_WAVES)) == (0, -3)
+    with _lib.tuned(L, BN_FOLD=1, BN_CHAN=512):  # nests
+        assert (get(T.BN_FOLD), get(T.BN_CHAN), get(T.C1_WGRAD_WAVES)) == (1, 512, -3)
+    assert (get(T.BN_FOLD), get(T.BN_CHAN), get(T.C1_WGRAD_WAVES)) == (0, 1, -3)
+    cache["shape"] = 2
+assert not cache, "emptied on exit"
+assert (get(T.BN_FOLD), get(T.C1_WGRAD_WAVES)) == (1, 2048)
+try:
+    with _lib.tuned(L, BN_SMALL_M=0, MIX_LANES=128):
+        cache["shape"] = 3
+        raise ZeroDivisionError
+except ZeroDivisionError:
+    pass
+assert not cache and (get(T.BN_SMALL_M), get(T.MIX_LANES)) == (256, 256), "restored on an exception"
+try:
+    with _lib.tuned(L, BN_FOLD=0, NO_SUCH_KEY=1):
+        raise SystemExit("entered with an unknown key")
+except KeyError:
+    pass
+assert get(T.BN_FOLD) == 1
+L.cot_set_tuning(T.BN_FOLD, 0)
+cache["shape"] = 4
+_lib.reset_tuning(L)
+assert not cache and get(T.BN_FOLD) == 1
+cache["shape"] = 5
+L.cot_reset_tuning()  # (lib()'s handle: wrapped as cot_set_tuning is)
+assert not cache
+"""
+
+
+def test_tuned_context_manager():
+    """_lib.tuned nests, restores on an exception, and empties a register_cache dictionary on entry and on exit; so does reset_tuning"""
+    _child(_TUNED_CHILD)
 
 
 def test_product_has_no_cpu_fallback():

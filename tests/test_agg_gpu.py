@@ -320,11 +320,8 @@ def test_mix_tile_kernels_equal_the_generic_kernels():
     contracts multiply-adds differently in the two loop shapes; integer-valued data is bit-exact for both, test above)"""
     x, w1, w2, gout = _mix_config5_inputs(torch.float32, N=8)
     tile = _mix_gpu(x, w1, w2, gout)
-    _lib.lib().cot_set_tuning(51, 1)
-    try:
+    with _lib.tuned(_lib.lib(), MIX_GENERIC=1):
         gen = _mix_gpu(x, w1, w2, gout)
-    finally:
-        _lib.lib().cot_set_tuning(51, 0)
     assert tile[4] == "aggmix_fwd_tile" and gen[4] == "aggmix_fwd"
     for a, b in zip(tile[:4], gen[:4]):
         assert (a - b).abs().max() <= 2e-6 * (1 + b.abs().max())

@@ -64,7 +64,7 @@ def test_any_trouble_with_the_child_keeps_round1(monkeypatch):
 
 def test_kernel_sets_apply_the_documented_switches(monkeypatch):
     from cotnet_amd import _lib, conv1x1 as c1, conv3x3g as c3, cot_layer_fused as clf, group_norm9 as g9
-    calls = []
+    calls, BN_FOLD = [], _lib.TUNE.BN_FOLD
 
     class Fake:
         def cot_set_tuning(self, k, v):
@@ -75,9 +75,9 @@ def test_kernel_sets_apply_the_documented_switches(monkeypatch):
     for mod, attr in ((clf, "ENABLED"), (c1, "MODE"), (c3, "MODE"), (g9, "MODE"), (p3, "MODE"), (hf, "MODE"), (s7, "MODE")):
         monkeypatch.setattr(mod, attr, getattr(mod, attr))  # restored after the test
     bench.apply_kernel_set("new")
-    assert clf.ENABLED and c1.MODE == c3.MODE == g9.MODE == "hip" and calls[-1] == (12, 1)
+    assert clf.ENABLED and c1.MODE == c3.MODE == g9.MODE == "hip" and calls[-1] == (BN_FOLD, 1)
     bench.apply_kernel_set("round1")
-    assert not clf.ENABLED and c1.MODE == c3.MODE == g9.MODE == "" and calls[-1] == (12, 0)
+    assert not clf.ENABLED and c1.MODE == c3.MODE == g9.MODE == "" and calls[-1] == (BN_FOLD, 0)
 
 
 def test_probe_child_body_on_emulated_kernels(monkeypatch, capsys):
@@ -129,7 +129,7 @@ def _emulated_probe(monkeypatch, lib_wrapper=None):
     try:
         return bench.probe_child(args, dev=torch.device("cpu"), warm=1, timed=1, make_model=make_model)
     finally:
-        tke._EMUL.cot_set_tuning(12, 0)
+        _lib.reset_tuning(tke._EMUL)  # (the kernel sets turn BN_FOLD)
         for cache in caches:
             cache.clear()
 

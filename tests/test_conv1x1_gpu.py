@@ -156,7 +156,7 @@ def test_other_inputs_keep_the_module_path(monkeypatch):
 @pytest.mark.parametrize("N,Ci,Co,H", [(6, 512, 2048, 7), (6, 2048, 512, 7), (5, 256, 1024, 14)])
 def test_deep_layers_with_both_channel_block_sizes(N, Ci, Co, H, monkeypatch):
     """the 7 x 7 / 14 x 14 layers run 64-channel blocks when a launch has few workgroups (the small batches of these tests
-    always do) and 128-channel blocks otherwise (B = 80): both forms (cot_set_tuning(17) bits 8..) against the fp32
+    always do) and 128-channel blocks otherwise (B = 80): both forms (cot_set_tuning(CONV_LDS_BITS) bits 8..) against the fp32
     reference (the two walk K from different staggered starting steps, so they agree to rounding, not bit for bit)"""
     from cotnet_amd import _lib
     monkeypatch.setattr(c1, "MODE", "hip")
@@ -165,16 +165,13 @@ def test_deep_layers_with_both_channel_block_sizes(N, Ci, Co, H, monkeypatch):
     x = torch.randn(N, Ci, H, H, device=DEV).bfloat16()
     gy = torch.randn(N, Co, H, H, device=DEV).bfloat16()
     outs = []
-    try:
-        for key in (0, 256):
-            _lib.check(_lib.lib().cot_set_tuning(17, key), "cot_set_tuning")
+    for key in (0, 256):
+        with _lib.tuned(_lib.lib(), CONV_LDS_BITS=key):
             xi = x.clone().requires_grad_(True)
             conv.zero_grad()
             y = c1.conv1x1(conv, xi)
             y.backward(gy)
             outs.append((y.detach().clone(), xi.grad.clone(), conv.weight.grad.clone()))
-    finally:
-        _lib.check(_lib.lib().cot_set_tuning(17, 0), "cot_set_tuning")
     yr, gxr, gwr, _ = _ref([x], conv.weight, None, gy)
     for y, gx, gw in outs:
         assert _close(y, yr, 1e-2) and _close(gx, gxr[0], 1e-2) and _close(gw, gwr, 1e-2)
@@ -185,7 +182,7 @@ def test_deep_layers_with_both_channel_block_sizes(N, Ci, Co, H, monkeypatch):
 def test_one_image_convolutions_of_the_se_branch(Ci, Co, NB, monkeypatch):
     """the `se` branch's two 1x1 convolutions as the single-node layers issue them: ONE image whose pixels are the batch
     (csrc/conv_tiny.hip: a wave per 16 x 16 output tile, no LDS), against the fp32 reference, and the tiled kernels next to
-    them (cot_set_tuning(22, 0))"""
+    them (cot_set_tuning(_lib.TUNE.CONV_TINY, 0))"""
     from cotnet_amd import _lib
     monkeypatch.setattr(c1, "MODE", "hip")
     torch.manual_seed(Ci + Co)
@@ -193,9 +190,8 @@ def test_one_image_convolutions_of_the_se_branch(Ci, Co, NB, monkeypatch):
     x = torch.randn(1, Ci, 1, NB, device=DEV).bfloat16()
     gy = torch.randn(1, Co, 1, NB, device=DEV).bfloat16()
     yr, gxr, gwr, gbr = _ref([x], conv.weight, conv.bias, gy)
-    try:
-        for key in (1, 0):
-            _lib.check(_lib.lib().cot_set_tuning(22, key), "cot_set_tuning")
+    for key in (1, 0):
+        with _lib.tuned(_lib.lib(), CONV_TINY=key):
             xi = x.clone().requires_grad_(True)
             conv.zero_grad()
             y = c1.conv1x1(conv, xi)
@@ -203,8 +199,6 @@ def test_one_image_convolutions_of_the_se_branch(Ci, Co, NB, monkeypatch):
             torch.cuda.synchronize()
             assert _close(y, yr, 1e-2) and _close(xi.grad, gxr[0], 1e-2)
             assert _close(conv.weight.grad, gwr, 1e-2) and _close(conv.bias.grad, gbr, 1e-2)
-    finally:
-        _lib.check(_lib.lib().cot_set_tuning(22, 1), "cot_set_tuning")
 
 
 @pytest.mark.parametrize("N,Ci,Co,H", [(64, 48, 48, 56), (64, 96, 24, 56), (64, 96, 48, 28), (64, 96, 216, 14), (64, 192, 432, 7),
@@ -235,17 +229,14 @@ def test_partial_last_k_step_on_the_lds_kernels(N, Ci, Co, H):
     init = torch.randn(N, Ci, H, H, device=DEV).bfloat16()
     st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     outs = {}
-    try:
-        for k54 in (1, 0):
-            assert L.cot_set_tuning(54, k54) == 0
+    for k54 in (1, 0):
+        with _lib.tuned(L, CONV_K_TAIL=k54):
             y, gx, ga = torch.full_like(gy, float("nan")), torch.full_like(x, float("nan")), init.clone()
             assert L.cot_conv1x1_forward(P(x), None, Ci, P(w), None, P(y), N, Ci, Co, HW, dt, st) == 0, L.cot_last_error()
             assert L.cot_conv1x1_backward_data(P(gy), P(w), P(gx), None, Ci, 0, P(ws), N, Ci, Co, HW, dt, st) == 0, L.cot_last_error()
             assert L.cot_conv1x1_backward_data(P(gy), P(w), P(ga), None, Ci, 1, P(ws), N, Ci, Co, HW, dt, st) == 0, L.cot_last_error()
             torch.cuda.synchronize()
             outs[k54] = (y, gx, ga)
-    finally:
-        L.cot_set_tuning(54, 1)
     assert L.cot_conv1x1_lds_covers(Ci, Ci, 0, HW) == 1 and L.cot_conv1x1_lds_covers(Co, Co, 0, HW) == 1
     y, gx, ga = outs[1]
     assert _close(y, yr, 2e-2) and _close(gx, gr, 2e-2) and _close(ga, gr + init.float(), 3e-2)

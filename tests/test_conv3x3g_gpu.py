@@ -101,13 +101,10 @@ def test_weight_gradient_lds_staged_kernel(N, C, G, H):
         assert rc == 0, L.cot_last_error()
         torch.cuda.synchronize()
         outs.append(gw)
-    try:  # which kernels the call takes: a dry run (nothing is launched) fills the launch log
-        assert L.cot_set_tuning(26, 1) == 0
+    with _lib.tuned(L, DRY_RUN=1):  # which kernels the call takes: a dry run (nothing is launched) fills the launch log
         assert L.cot_conv3x3g_backward_weight_guarded(P(gy), P(x), P(gw), P(masks), P(ws), N, C, C, G, H, H, _lib.COT_BF16, lead, st) == 0
         buf = ctypes.create_string_buffer(4096)
         L.cot_launch_log(buf, 4096)
-    finally:
-        assert L.cot_set_tuning(26, 0) == 0
     assert b"conv1x1_wgrad_lds2<9, 1" in buf.value and b"block 832" in buf.value, buf.value
     assert torch.equal(outs[0], outs[1])
     scale = wf.grad.abs().max().item()

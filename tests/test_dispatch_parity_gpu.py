@@ -90,12 +90,9 @@ class _Pinned:
         L = self.L
         buf = ctypes.create_string_buffer(1 << 14)
         L.cot_launch_log(buf, len(buf))  # (drain)
-        assert L.cot_set_tuning(26, 1) == 0
-        try:
+        with _lib.tuned(L, DRY_RUN=1):
             rc = fn()
             L.cot_launch_log(buf, len(buf))
-        finally:
-            assert L.cot_set_tuning(26, 0) == 0
         assert rc == 0, L.cot_last_error().decode()
         got = [_short(ln) for ln in buf.value.decode().splitlines() if ln]
         assert got == TABLE[self.key], (self.key, got, TABLE[self.key])
@@ -107,10 +104,8 @@ class _Pinned:
 @pytest.fixture(autouse=True)
 def _bench_tuning():
     """the state bench.py's `new` set runs in (KERNEL_SETS: BatchNorm finalize folded into the apply kernels)"""
-    L = _lib.lib()
-    assert L.cot_set_tuning(12, 1) == 0
-    yield
-    assert L.cot_set_tuning(12, 1) == 0
+    with _lib.tuned(_lib.lib(), BN_FOLD=1):
+        yield
 
 
 def _conv1x1g(key, shp, what):

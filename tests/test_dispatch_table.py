@@ -4,7 +4,7 @@ The library picks its kernels by shape through a stack of rules (tile shapes, im
 behind 26 tuning keys).  Every rule is a place for a shape to fall onto a variant nobody measured or tested, so the table
 is pinned: the models of BASELINE.json's configs 2-5 are walked on the `meta` device (shapes only), every convolution /
 BatchNorm / GroupNorm / aggregation / pooling call they would make is issued against the REAL library in dry-run mode
-(cot_set_tuning(26, 1): no launch, no HIP call -- works in the GPU-less container), and the recorded launches are compared
+(cot_set_tuning(COT_TUNE_DRY_RUN, 1): no launch, no HIP call -- works in the GPU-less container), and the recorded launches are compared
 with tests/golden/dispatch_table.json.  A deliberate change of a rule = regenerate the fixture and look at the diff:
 
     python tests/test_dispatch_table.py --write
@@ -96,99 +96,98 @@ def build_table():
     BF = _lib.COT_BF16
     buf = ctypes.create_string_buffer(1 << 16)
     table = {}
-    assert L.cot_set_tuning(26, 1) == 0
-    try:
-        def rec(key, rc):
-            n = L.cot_launch_log(buf, len(buf))
-            lines = [ln for ln in buf.value.decode().splitlines() if ln]
-            table[key] = [_short(ln) for ln in lines] if rc == 0 else [f"rc={rc}: {L.cot_last_error().decode()}"]
-            assert n < len(buf) - 1
-        for cfg, (model, batch, size) in CONFIGS.items():
-            for kind, shp in sorted(_shapes(model, batch, size)):
-                tag = f"{cfg} {kind} {'x'.join(map(str, shp))}"
-                if kind == "conv1x1":
-                    N, Ci, Co, g, H, W, s, bias = shp
-                    if s != 1:
-                        H, W = (H - 1) // s + 1, (W - 1) // s + 1  # (strided projection = the stride-1 kernel on every s-th pixel)
-                    HW = H * W
-                    if g == 1:
-                        rec(tag + " fwd", L.cot_conv1x1_forward(PTR, None, Ci, PTR, PTR if bias else None, PTR, N, Ci, Co, HW, BF, None))
-                        rec(tag + " dgrad", L.cot_conv1x1_backward_data(PTR, PTR, PTR, None, Ci, 0, PTR, N, Ci, Co, HW, BF, None))
-                        rec(tag + " wgrad", L.cot_conv1x1_backward_weight(PTR, PTR, None, Ci, PTR, PTR if bias else None, PTR, N, Ci, Co,
-                                                                          HW, BF, None))
-                        if Ci % 2 == 0 and (Ci // 2) % 32 == 0 and not bias:  # embed[0] reads [x | k] as two slabs
-                            rec(tag + " fwd(two slabs)", L.cot_conv1x1_forward(PTR, PTR, Ci // 2, PTR, None, PTR, N, Ci, Co, HW, BF, None))
-                    else:
-                        rec(tag + " fwd", L.cot_conv1x1g_forward(PTR, PTR, PTR if bias else None, PTR, N, Ci, Co, g, HW, BF, None))
-                        rec(tag + " dgrad", L.cot_conv1x1g_backward_data(PTR, PTR, PTR, 0, N, Ci, Co, g, HW, BF, None))
-                        rec(tag + " wgrad", L.cot_conv1x1g_backward_weight(PTR, PTR, PTR, PTR if bias else None, PTR, N, Ci, Co, g, HW, BF,
-                                                                           None))
-                elif kind == "conv3x3":
-                    N, Ci, Co, g, H, W, s, bias = shp
-                    if s == 2 and Ci == 3 and g == 1 and not bias:  # a deep stem's first convolution: csrc/stem3x3.hip
-                        rec(tag + " fwd", L.cot_stem3x3s2_forward(PTR, PTR, PTR, N, H, W, Co, BF, None))
-                        rec(tag + " wgrad", L.cot_stem3x3s2_backward_weight(PTR, PTR, PTR, PTR, N, H, W, Co, BF, None))
-                        continue
-                    if s != 1 or bias:
-                        table[tag] = ["module (MIOpen): strided / biased 3x3 convolutions are outside the library"]
-                        continue
-                    # (groups of 12 channels -- CoXtLayer(96).key_embed: the nodes launch pairs of groups as one group of 24 with a
-                    # block-diagonal weight, cot_layer_fused._conv3x3_fwd / _dgrad)
-                    from cotnet_amd import cot_layer_fused as clf
-                    gl = clf._conv3x3_ws_groups(Ci, g) if Ci == Co else g
-                    rec(tag + " fwd", L.cot_conv3x3g_forward(PTR, PTR, PTR, PTR, PTR, N, Ci, Co, gl, H, W, BF, None))
-                    rec(tag + " dgrad", L.cot_conv3x3g_backward_data(PTR, PTR, PTR, 0, PTR, PTR, N, Ci, Co, gl, H, W, BF, None))
-                    rec(tag + " wgrad", L.cot_conv3x3g_backward_weight(PTR, PTR, PTR, PTR, PTR, N, Ci, Co, g, H, W, BF, None))
-                    # (the single-node Bottleneck allocates the CoT layer's input with margins: cot_layer_fused._new_guarded)
-                    rec(tag + " wgrad(guarded)", L.cot_conv3x3g_backward_weight_guarded(PTR, PTR, PTR, PTR, PTR, N, Ci, Co, g, H, W, BF,
-                                                                                        (W + 8) // 8 * 8, None))
-                elif kind == "bn":
-                    N, C, HW = shp
-                    rec(tag + " fwd", L.cot_bn_act_forward(PTR, None, PTR, PTR, PTR, PTR, PTR, PTR, PTR, PTR, PTR, N, C, HW, 1e-5, 0.1, 1,
-                                                           BF, None))
-                    rec(tag + " bwd", L.cot_bn_act_backward(PTR, PTR, None, PTR, None, PTR, PTR, PTR, PTR, PTR, PTR, PTR, N, C, HW, 1, BF,
-                                                            None))
-                elif kind == "gn":
-                    N, C, HW, G = shp
-                    if G * 9 == C:
-                        rec(tag + " fwd", L.cot_group_norm9_forward(PTR, PTR, PTR, PTR, PTR, PTR, N, C, HW, 1e-5, BF, None))
-                        rec(tag + " bwd", L.cot_group_norm9_backward(PTR, PTR, PTR, PTR, PTR, PTR, PTR, PTR, PTR, N, C, HW, BF, None))
-                elif kind == "agg":
-                    N, C, H, W, wC = shp
-                    g = _lib.AggGeom(N, C, H, W, 1, wC, 3, 3, 1, 1, 1, 1, 1, 1)
-                    rec(tag + " fwd", L.cot_agg_forward(PTR, PTR, PTR, ctypes.byref(g), BF, 0, None))
-                    rec(tag + " bwd", L.cot_agg_backward(PTR, PTR, PTR, PTR, PTR, ctypes.byref(g), BF, 0, None))
-                elif kind in ("AvgPool2d", "MaxPool2d"):
-                    N, C, H, W = shp
-                    fn = L.cot_avgpool3x3s2_forward if kind == "AvgPool2d" else L.cot_maxpool3x3s2_forward
-                    rec(tag + " fwd", fn(PTR, PTR, N * C, H, W, BF, None))
-                # ---- the channel-major forms of the deep stages' identity Bottlenecks (cot_layer_fused._BottleneckCMNode):
-                # the same 1x1 / BatchNorm entry points on channel rows (N = 1, HW' = N*HW) and the per-tensor-layout BatchNorm
-                if cfg == "cotnet50_b80_224" and kind == "conv1x1" and shp[3] == 1 and shp[6] == 1 and shp[4] * shp[5] in (196, 49):
-                    N, Ci, Co, g, H, W, s, bias = shp
-                    M = N * H * W
-                    cmt = f"{cfg} conv1x1cm {'x'.join(map(str, shp))}"
-                    rec(cmt + " fwd", L.cot_conv1x1_forward(PTR, None, Ci, PTR, PTR if bias else None, PTR, 1, Ci, Co, M, BF, None))
-                    rec(cmt + " dgrad", L.cot_conv1x1_backward_data(PTR, PTR, PTR, None, Ci, 0, PTR, 1, Ci, Co, M, BF, None))
-                    rec(cmt + " wgrad", L.cot_conv1x1_backward_weight(PTR, PTR, None, Ci, PTR, PTR if bias else None, PTR, 1, Ci, Co, M, BF,
-                                                                      None))
-                    if Ci % 2 == 0 and (Ci // 2) % 32 == 0 and not bias:
-                        rec(cmt + " fwd(two slabs)", L.cot_conv1x1_forward(PTR, PTR, Ci // 2, PTR, None, PTR, 1, Ci, Co, M, BF, None))
-                if cfg == "cotnet50_b80_224" and kind == "bn" and shp[2] in (196, 49):
-                    N, C, HW = shp
-                    cmt = f"{cfg} bncm {'x'.join(map(str, shp))}"
-                    rec(cmt + " fwd", L.cot_bn_act_forward(PTR, None, PTR, PTR, PTR, PTR, PTR, PTR, PTR, PTR, PTR, 1, C, N * HW, 1e-5, 0.1, 1,
-                                                           BF, None))
-                    rec(cmt + " bwd", L.cot_bn_act_backward(PTR, PTR, None, PTR, None, PTR, PTR, PTR, PTR, PTR, PTR, PTR, 1, C, N * HW, 1, BF,
-                                                            None))
-                    lyt = f"{cfg} bnlay {'x'.join(map(str, shp))}"
-                    rec(lyt + " fwd", L.cot_bn_act_forward_lay(PTR, None, PTR, PTR, PTR, PTR, PTR, PTR, PTR, PTR, PTR, None, N, C, HW, 1e-5, 0.1,
-                                                               1, 1 | 8, BF, None))
-                    rec(lyt + " bwd", L.cot_bn_act_backward_lay(PTR, PTR, PTR, None, PTR, None, PTR, PTR, PTR, PTR, PTR, PTR, None, N, C, HW, 1,
-                                                                1 | 4 | 16, BF, None))
-    finally:
-        L.cot_launch_log(buf, len(buf))
-        assert L.cot_set_tuning(26, 0) == 0
+    with _lib.tuned(L, DRY_RUN=1):
+        try:
+            def rec(key, rc):
+                n = L.cot_launch_log(buf, len(buf))
+                lines = [ln for ln in buf.value.decode().splitlines() if ln]
+                table[key] = [_short(ln) for ln in lines] if rc == 0 else [f"rc={rc}: {L.cot_last_error().decode()}"]
+                assert n < len(buf) - 1
+            for cfg, (model, batch, size) in CONFIGS.items():
+                for kind, shp in sorted(_shapes(model, batch, size)):
+                    tag = f"{cfg} {kind} {'x'.join(map(str, shp))}"
+                    if kind == "conv1x1":
+                        N, Ci, Co, g, H, W, s, bias = shp
+                        if s != 1:
+                            H, W = (H - 1) // s + 1, (W - 1) // s + 1  # (strided projection = the stride-1 kernel on every s-th pixel)
+                        HW = H * W
+                        if g == 1:
+                            rec(tag + " fwd", L.cot_conv1x1_forward(PTR, None, Ci, PTR, PTR if bias else None, PTR, N, Ci, Co, HW, BF, None))
+                            rec(tag + " dgrad", L.cot_conv1x1_backward_data(PTR, PTR, PTR, None, Ci, 0, PTR, N, Ci, Co, HW, BF, None))
+                            rec(tag + " wgrad", L.cot_conv1x1_backward_weight(PTR, PTR, None, Ci, PTR, PTR if bias else None, PTR, N, Ci, Co,
+                                                                              HW, BF, None))
+                            if Ci % 2 == 0 and (Ci // 2) % 32 == 0 and not bias:  # embed[0] reads [x | k] as two slabs
+                                rec(tag + " fwd(two slabs)", L.cot_conv1x1_forward(PTR, PTR, Ci // 2, PTR, None, PTR, N, Ci, Co, HW, BF, None))
+                        else:
+                            rec(tag + " fwd", L.cot_conv1x1g_forward(PTR, PTR, PTR if bias else None, PTR, N, Ci, Co, g, HW, BF, None))
+                            rec(tag + " dgrad", L.cot_conv1x1g_backward_data(PTR, PTR, PTR, 0, N, Ci, Co, g, HW, BF, None))
+                            rec(tag + " wgrad", L.cot_conv1x1g_backward_weight(PTR, PTR, PTR, PTR if bias else None, PTR, N, Ci, Co, g, HW, BF,
+                                                                               None))
+                    elif kind == "conv3x3":
+                        N, Ci, Co, g, H, W, s, bias = shp
+                        if s == 2 and Ci == 3 and g == 1 and not bias:  # a deep stem's first convolution: csrc/stem3x3.hip
+                            rec(tag + " fwd", L.cot_stem3x3s2_forward(PTR, PTR, PTR, N, H, W, Co, BF, None))
+                            rec(tag + " wgrad", L.cot_stem3x3s2_backward_weight(PTR, PTR, PTR, PTR, N, H, W, Co, BF, None))
+                            continue
+                        if s != 1 or bias:
+                            table[tag] = ["module (MIOpen): strided / biased 3x3 convolutions are outside the library"]
+                            continue
+                        # (groups of 12 channels -- CoXtLayer(96).key_embed: the nodes launch pairs of groups as one group of 24 with a
+                        # block-diagonal weight, cot_layer_fused._conv3x3_fwd / _dgrad)
+                        from cotnet_amd import cot_layer_fused as clf
+                        gl = clf._conv3x3_ws_groups(Ci, g) if Ci == Co else g
+                        rec(tag + " fwd", L.cot_conv3x3g_forward(PTR, PTR, PTR, PTR, PTR, N, Ci, Co, gl, H, W, BF, None))
+                        rec(tag + " dgrad", L.cot_conv3x3g_backward_data(PTR, PTR, PTR, 0, PTR, PTR, N, Ci, Co, gl, H, W, BF, None))
+                        rec(tag + " wgrad", L.cot_conv3x3g_backward_weight(PTR, PTR, PTR, PTR, PTR, N, Ci, Co, g, H, W, BF, None))
+                        # (the single-node Bottleneck allocates the CoT layer's input with margins: cot_layer_fused._new_guarded)
+                        rec(tag + " wgrad(guarded)", L.cot_conv3x3g_backward_weight_guarded(PTR, PTR, PTR, PTR, PTR, N, Ci, Co, g, H, W, BF,
+                                                                                            (W + 8) // 8 * 8, None))
+                    elif kind == "bn":
+                        N, C, HW = shp
+                        rec(tag + " fwd", L.cot_bn_act_forward(PTR, None, PTR, PTR, PTR, PTR, PTR, PTR, PTR, PTR, PTR, N, C, HW, 1e-5, 0.1, 1,
+                                                               BF, None))
+                        rec(tag + " bwd", L.cot_bn_act_backward(PTR, PTR, None, PTR, None, PTR, PTR, PTR, PTR, PTR, PTR, PTR, N, C, HW, 1, BF,
+                                                                None))
+                    elif kind == "gn":
+                        N, C, HW, G = shp
+                        if G * 9 == C:
+                            rec(tag + " fwd", L.cot_group_norm9_forward(PTR, PTR, PTR, PTR, PTR, PTR, N, C, HW, 1e-5, BF, None))
+                            rec(tag + " bwd", L.cot_group_norm9_backward(PTR, PTR, PTR, PTR, PTR, PTR, PTR, PTR, PTR, N, C, HW, BF, None))
+                    elif kind == "agg":
+                        N, C, H, W, wC = shp
+                        g = _lib.AggGeom(N, C, H, W, 1, wC, 3, 3, 1, 1, 1, 1, 1, 1)
+                        rec(tag + " fwd", L.cot_agg_forward(PTR, PTR, PTR, ctypes.byref(g), BF, 0, None))
+                        rec(tag + " bwd", L.cot_agg_backward(PTR, PTR, PTR, PTR, PTR, ctypes.byref(g), BF, 0, None))
+                    elif kind in ("AvgPool2d", "MaxPool2d"):
+                        N, C, H, W = shp
+                        fn = L.cot_avgpool3x3s2_forward if kind == "AvgPool2d" else L.cot_maxpool3x3s2_forward
+                        rec(tag + " fwd", fn(PTR, PTR, N * C, H, W, BF, None))
+                    # ---- the channel-major forms of the deep stages' identity Bottlenecks (cot_layer_fused._BottleneckCMNode):
+                    # the same 1x1 / BatchNorm entry points on channel rows (N = 1, HW' = N*HW) and the per-tensor-layout BatchNorm
+                    if cfg == "cotnet50_b80_224" and kind == "conv1x1" and shp[3] == 1 and shp[6] == 1 and shp[4] * shp[5] in (196, 49):
+                        N, Ci, Co, g, H, W, s, bias = shp
+                        M = N * H * W
+                        cmt = f"{cfg} conv1x1cm {'x'.join(map(str, shp))}"
+                        rec(cmt + " fwd", L.cot_conv1x1_forward(PTR, None, Ci, PTR, PTR if bias else None, PTR, 1, Ci, Co, M, BF, None))
+                        rec(cmt + " dgrad", L.cot_conv1x1_backward_data(PTR, PTR, PTR, None, Ci, 0, PTR, 1, Ci, Co, M, BF, None))
+                        rec(cmt + " wgrad", L.cot_conv1x1_backward_weight(PTR, PTR, None, Ci, PTR, PTR if bias else None, PTR, 1, Ci, Co, M, BF,
+                                                                          None))
+                        if Ci % 2 == 0 and (Ci // 2) % 32 == 0 and not bias:
+                            rec(cmt + " fwd(two slabs)", L.cot_conv1x1_forward(PTR, PTR, Ci // 2, PTR, None, PTR, 1, Ci, Co, M, BF, None))
+                    if cfg == "cotnet50_b80_224" and kind == "bn" and shp[2] in (196, 49):
+                        N, C, HW = shp
+                        cmt = f"{cfg} bncm {'x'.join(map(str, shp))}"
+                        rec(cmt + " fwd", L.cot_bn_act_forward(PTR, None, PTR, PTR, PTR, PTR, PTR, PTR, PTR, PTR, PTR, 1, C, N * HW, 1e-5, 0.1, 1,
+                                                               BF, None))
+                        rec(cmt + " bwd", L.cot_bn_act_backward(PTR, PTR, None, PTR, None, PTR, PTR, PTR, PTR, PTR, PTR, PTR, 1, C, N * HW, 1, BF,
+                                                                None))
+                        lyt = f"{cfg} bnlay {'x'.join(map(str, shp))}"
+                        rec(lyt + " fwd", L.cot_bn_act_forward_lay(PTR, None, PTR, PTR, PTR, PTR, PTR, PTR, PTR, PTR, PTR, None, N, C, HW, 1e-5, 0.1,
+                                                                   1, 1 | 8, BF, None))
+                        rec(lyt + " bwd", L.cot_bn_act_backward_lay(PTR, PTR, PTR, None, PTR, None, PTR, PTR, PTR, PTR, PTR, PTR, None, N, C, HW, 1,
+                                                                    1 | 4 | 16, BF, None))
+        finally:
+            L.cot_launch_log(buf, len(buf))
     return table
 
 

@@ -14,13 +14,9 @@ _RAN = set()
 
 @pytest.fixture
 def _library_defaults():
-    E = tke._EMUL
-    defaults = ((10, 0), (11, 2048), (12, 1), (17, 0), (18, 256), (21, 1), (25, 0))
-    for k, v in defaults:
-        E.cot_set_tuning(k, v)
+    """the cases run on the library's defaults and set what they vary with _lib.tuned"""
     yield
-    for k, v in defaults:
-        E.cot_set_tuning(k, v)
+    fc._lib.reset_tuning(tke._EMUL)
 
 
 @_emulated

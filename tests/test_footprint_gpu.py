@@ -29,8 +29,6 @@ def device_lib():
     L = _DeviceLib(_lib.lib())  # (raises when the HIP library is missing: no fallback)
     yield L
     torch.cuda.synchronize()
-    for k, v in fc.tuned.DEFAULTS.items():
-        L.cot_set_tuning(k, v)
 
 
 @pytest.mark.parametrize("base", [0, 16])

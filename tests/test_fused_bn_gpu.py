@@ -14,16 +14,12 @@ DEV = "cuda"
 
 @pytest.fixture(params=[0, 1, 2], ids=["finalize-kernel", "finalize-folded", "channel-resident"])
 def fold(request):
-    """streaming kernels with the per-channel finalize step as its own launch (cot_set_tuning(12, 0)) or folded into the apply
-    kernels' prologue (12 = 1, what bench.py's `new` kernel set runs), both with the channel-resident kernels off
-    (cot_set_tuning(21, 0)); and the library default: channel-resident kernels wherever a channel fits a workgroup's registers"""
+    """streaming kernels with the per-channel finalize step as its own launch (BN_FOLD=0) or folded into the apply kernels' prologue
+    (BN_FOLD=1, what bench.py's `new` kernel set runs), both with the channel-resident kernels off (BN_CHAN=0); and channel-resident
+    kernels wherever a channel fits a workgroup's registers (BN_CHAN=1, the library default) over the separate finalize launch"""
     from cotnet_amd import _lib
-    L = _lib.lib()
-    _lib.check(L.cot_set_tuning(12, 1 if request.param == 1 else 0), "cot_set_tuning")
-    _lib.check(L.cot_set_tuning(21, 1 if request.param == 2 else 0), "cot_set_tuning")
-    yield request.param
-    _lib.check(L.cot_set_tuning(12, 0), "cot_set_tuning")
-    _lib.check(L.cot_set_tuning(21, 1), "cot_set_tuning")
+    with _lib.tuned(_lib.lib(), BN_FOLD=1 if request.param == 1 else 0, BN_CHAN=1 if request.param == 2 else 0):
+        yield request.param
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])

@@ -9,6 +9,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from cotnet_amd import _lib
 from tests import test_kernels_emulated as tke
 
 pytestmark = pytest.mark.skipif(tke._EMUL is None, reason="host emulation build unavailable")
@@ -18,6 +19,14 @@ BF = 2  # COT_BF16
 # host model's bits here (same operations in the same order as the C oracle / as torch) are there within a few ulps of them
 ON_DEVICE = False
 SCALE = 1  # (scripts/fuzz_gpu.py --scale: larger planes on the device -- the 128-pixel-tile forms of the convolution kernels, H * W > 256)
+
+
+@pytest.fixture(autouse=True)
+def _library_defaults():
+    """every case sets the keys it draws with _lib.tuned; whatever a failing one leaves behind ends here"""
+    yield
+    E.emul_set_dma_mode(0)
+    _lib.reset_tuning(E)
 
 
 def P(t):
@@ -35,61 +44,61 @@ def case_conv1x1(rng):
     split = rng.random() < 0.3 and Ci > 8
     bias = rng.random() < 0.5
     c1 = 8 * rng.randint(1, Ci // 8 - 1) if split else Ci
-    E.cot_set_tuning(10, rng.choice([0, 0, 2, 4]))          # rows per wave
-    E.cot_set_tuning(11, rng.choice([2048, 2048, -2, -3]))  # split count (sizes the workspace: set it first)
-    x = torch.randn(N, Ci, H, W).bfloat16()
-    w = (torch.randn(Co, Ci) / Ci ** 0.5).bfloat16()
-    b = torch.randn(Co).bfloat16() if bias else None
-    gy = torch.randn(N, Co, H, W).bfloat16()
-    xf, wf = x.float().requires_grad_(True), w.float().requires_grad_(True)
-    bf = b.float().requires_grad_(True) if bias else None
-    yr = F.conv2d(xf, wf[:, :, None, None], bf)
-    yr.backward(gy.float())
-    x1 = x[:, :c1].contiguous() if split else x
-    x2 = x[:, c1:].contiguous() if split else None
-    y = torch.empty(N, Co, H, W).bfloat16()
-    assert E.cot_conv1x1_forward(P(x1), P(x2), c1, P(w), P(b), P(y), N, Ci, Co, H * W, BF, None) == 0
-    ws = torch.empty(E.cot_conv1x1_workspace(N, Ci, Co, H * W, 1 if bias else 0), dtype=torch.uint8)
-    # accumulate bits: 1 = add into the first slab's buffer, 2 = into the second's (fp32 sum, one rounding)
-    accumulate = rng.choice([0, 0, 1, 2, 3]) & (3 if split else 1)
-    init1, init2 = torch.randn_like(x1.float()).bfloat16(), (torch.randn_like(x2.float()).bfloat16() if split else None)
-    gx1, gx2 = init1.clone(), (init2.clone() if split else None)
-    assert E.cot_conv1x1_backward_data(P(gy), P(w), P(gx1), P(gx2), c1, accumulate, P(ws), N, Ci, Co, H * W, BF, None) == 0
-    gx = torch.cat([gx1, gx2], 1) if split else gx1
-    add = [init1.float() if accumulate & 1 else torch.zeros_like(init1.float())]
-    if split:
-        add.append(init2.float() if accumulate & 2 else torch.zeros_like(init2.float()))
-    xf.grad += torch.cat(add, 1)
-    gw = torch.empty_like(w)
-    gb = torch.empty_like(b) if bias else None
-    assert E.cot_conv1x1_backward_weight(P(gy), P(x1), P(x2), c1, P(gw), P(gb), P(ws), N, Ci, Co, H * W, BF, None) == 0
-    ok = close(y, yr.detach()) and close(gx, xf.grad, 3e-2) and close(gw, wf.grad) and (not bias or close(gb, bf.grad))
-    return ok, ("conv1x1", N, Ci, Co, H, W, c1, bias)
+    rows, waves = rng.choice([0, 0, 2, 4]), rng.choice([2048, 2048, -2, -3])  # rows per wave; split count
+    with _lib.tuned(E, C1_ROWS_PER_WAVE=rows, C1_WGRAD_WAVES=waves):  # (C1_WGRAD_WAVES sizes the workspace: set before it is asked for)
+        x = torch.randn(N, Ci, H, W).bfloat16()
+        w = (torch.randn(Co, Ci) / Ci ** 0.5).bfloat16()
+        b = torch.randn(Co).bfloat16() if bias else None
+        gy = torch.randn(N, Co, H, W).bfloat16()
+        xf, wf = x.float().requires_grad_(True), w.float().requires_grad_(True)
+        bf = b.float().requires_grad_(True) if bias else None
+        yr = F.conv2d(xf, wf[:, :, None, None], bf)
+        yr.backward(gy.float())
+        x1 = x[:, :c1].contiguous() if split else x
+        x2 = x[:, c1:].contiguous() if split else None
+        y = torch.empty(N, Co, H, W).bfloat16()
+        assert E.cot_conv1x1_forward(P(x1), P(x2), c1, P(w), P(b), P(y), N, Ci, Co, H * W, BF, None) == 0
+        ws = torch.empty(E.cot_conv1x1_workspace(N, Ci, Co, H * W, 1 if bias else 0), dtype=torch.uint8)
+        # accumulate bits: 1 = add into the first slab's buffer, 2 = into the second's (fp32 sum, one rounding)
+        accumulate = rng.choice([0, 0, 1, 2, 3]) & (3 if split else 1)
+        init1, init2 = torch.randn_like(x1.float()).bfloat16(), (torch.randn_like(x2.float()).bfloat16() if split else None)
+        gx1, gx2 = init1.clone(), (init2.clone() if split else None)
+        assert E.cot_conv1x1_backward_data(P(gy), P(w), P(gx1), P(gx2), c1, accumulate, P(ws), N, Ci, Co, H * W, BF, None) == 0
+        gx = torch.cat([gx1, gx2], 1) if split else gx1
+        add = [init1.float() if accumulate & 1 else torch.zeros_like(init1.float())]
+        if split:
+            add.append(init2.float() if accumulate & 2 else torch.zeros_like(init2.float()))
+        xf.grad += torch.cat(add, 1)
+        gw = torch.empty_like(w)
+        gb = torch.empty_like(b) if bias else None
+        assert E.cot_conv1x1_backward_weight(P(gy), P(x1), P(x2), c1, P(gw), P(gb), P(ws), N, Ci, Co, H * W, BF, None) == 0
+        ok = close(y, yr.detach()) and close(gx, xf.grad, 3e-2) and close(gw, wf.grad) and (not bias or close(gb, bf.grad))
+        return ok, ("conv1x1", N, Ci, Co, H, W, c1, bias)
 
 
 def case_conv3x3(rng):
     G, Kc = rng.choice([1, 2, 4, 8]), 8 * rng.randint(1, 4)
     C, N, H, W = G * Kc, rng.randint(1, 2), rng.randint(1, 12 * SCALE), rng.randint(1, 12 * SCALE)
-    E.cot_set_tuning(11, rng.choice([2048, -2]))
-    x = torch.randn(N, C, H, W).bfloat16()
-    w = (torch.randn(C, Kc, 3, 3) / (9 * Kc) ** 0.5).bfloat16()
-    gy = torch.randn(N, C, H, W).bfloat16()
-    xf, wf = x.float().requires_grad_(True), w.float().requires_grad_(True)
-    yr = F.conv2d(xf, wf, None, 1, 1, 1, G)
-    yr.backward(gy.float())
-    masks = torch.empty(E.cot_conv3x3g_masks_bytes(H, W), dtype=torch.uint8)
-    assert E.cot_conv3x3g_masks(P(masks), H, W, None) == 0
-    ws = torch.empty(E.cot_conv3x3g_workspace(N, C, C, G, H, W), dtype=torch.uint8)
-    y, gw = torch.empty_like(x), torch.empty_like(w)
-    accumulate = rng.choice([0, 1])
-    init = torch.randn_like(x.float()).bfloat16()
-    gx = init.clone()
-    assert E.cot_conv3x3g_forward(P(x), P(w), P(y), P(masks), P(ws), N, C, C, G, H, W, BF, None) == 0
-    assert E.cot_conv3x3g_backward_data(P(gy), P(w), P(gx), accumulate, P(masks), P(ws), N, C, C, G, H, W, BF, None) == 0
-    if accumulate:
-        xf.grad += init.float()
-    assert E.cot_conv3x3g_backward_weight(P(gy), P(x), P(gw), P(masks), P(ws), N, C, C, G, H, W, BF, None) == 0
-    return close(y, yr.detach()) and close(gx, xf.grad, 3e-2) and close(gw, wf.grad), ("conv3x3g", N, C, G, H, W)
+    with _lib.tuned(E, C1_WGRAD_WAVES=rng.choice([2048, -2])):
+        x = torch.randn(N, C, H, W).bfloat16()
+        w = (torch.randn(C, Kc, 3, 3) / (9 * Kc) ** 0.5).bfloat16()
+        gy = torch.randn(N, C, H, W).bfloat16()
+        xf, wf = x.float().requires_grad_(True), w.float().requires_grad_(True)
+        yr = F.conv2d(xf, wf, None, 1, 1, 1, G)
+        yr.backward(gy.float())
+        masks = torch.empty(E.cot_conv3x3g_masks_bytes(H, W), dtype=torch.uint8)
+        assert E.cot_conv3x3g_masks(P(masks), H, W, None) == 0
+        ws = torch.empty(E.cot_conv3x3g_workspace(N, C, C, G, H, W), dtype=torch.uint8)
+        y, gw = torch.empty_like(x), torch.empty_like(w)
+        accumulate = rng.choice([0, 1])
+        init = torch.randn_like(x.float()).bfloat16()
+        gx = init.clone()
+        assert E.cot_conv3x3g_forward(P(x), P(w), P(y), P(masks), P(ws), N, C, C, G, H, W, BF, None) == 0
+        assert E.cot_conv3x3g_backward_data(P(gy), P(w), P(gx), accumulate, P(masks), P(ws), N, C, C, G, H, W, BF, None) == 0
+        if accumulate:
+            xf.grad += init.float()
+        assert E.cot_conv3x3g_backward_weight(P(gy), P(x), P(gw), P(masks), P(ws), N, C, C, G, H, W, BF, None) == 0
+        return close(y, yr.detach()) and close(gx, xf.grad, 3e-2) and close(gw, wf.grad), ("conv3x3g", N, C, G, H, W)
 
 
 def case_group_norm(rng):
@@ -151,15 +160,13 @@ def case_conv3x3_guarded(rng):
     F.conv2d(x.float(), wf, None, 1, 1, 1, G).backward(gy.float())
     masks = torch.empty(E.cot_conv3x3g_masks_bytes(H, W), dtype=torch.uint8)
     assert E.cot_conv3x3g_masks(P(masks), H, W, None) == 0
-    E.cot_set_tuning(25, rng.choice([0, 0, 1, 2, 3, 7]) << 24)  # forced slice counts (size the workspace afterwards)
+    force = rng.choice([0, 0, 1, 2, 3, 7]) << 24  # forced slice counts (size the workspace afterwards)
     E.emul_set_dma_mode(rng.choice([0, 1]))
-    try:
+    with _lib.tuned(E, WGRAD2_BITS=force):
         ws = torch.full((E.cot_conv3x3g_workspace(N, Ci, Co, G, H, W),), 0x7f, dtype=torch.uint8)
         gw = torch.full((Co, Kc, 3, 3), float("nan")).bfloat16()
         assert E.cot_conv3x3g_backward_weight_guarded(P(gy), P(x), P(gw), P(masks), P(ws), N, Ci, Co, G, H, W, BF, guard, None) == 0
-    finally:
-        E.cot_set_tuning(25, 0)
-        E.emul_set_dma_mode(0)
+    E.emul_set_dma_mode(0)
     scale = wf.grad.abs().max().item()
     ok = (gw.float() - wf.grad).abs().max().item() <= 1e-2 * scale + 1e-2
     return ok, ("conv3x3 guarded wgrad", N, Ci, Co, G, H, W, guard)
@@ -197,7 +204,8 @@ def case_conv3x3_lds(rng):
         G //= 2
     C, N = G * Kc, rng.randint(1, 3)
     H, W = rng.randint(3, 30 * min(SCALE, 2)), rng.randint(3, 30 * min(SCALE, 2))
-    keys = {39: rng.choice([0, 1, 1, 2]), 42: rng.choice([0, 1, 2]), 44: rng.choice([0, 1, 2]), 45: rng.choice([0, 1, 2])}
+    keys = dict(CONV3X3_RES=rng.choice([0, 1, 1, 2]), CONV3X3_WSINGLE=rng.choice([0, 1, 2]), CONV3X3_COLS=rng.choice([0, 1, 2]),
+                CONV3X3_PERM=rng.choice([0, 1, 2]))
     dma = rng.choice([0, 1])
     x = _nan_margined(torch.randn(N, C, H, W).bfloat16(), W + 1 + rng.randint(0, 9))
     gy = _nan_margined(torch.randn(N, C, H, W).bfloat16(), W + 1 + rng.randint(0, 9))
@@ -207,21 +215,15 @@ def case_conv3x3_lds(rng):
     yr.backward(gy.float())
     masks = torch.empty(E.cot_conv3x3g_masks_bytes(H, W), dtype=torch.uint8)
     assert E.cot_conv3x3g_masks(P(masks), H, W, None) == 0
-    for k, v in keys.items():
-        assert E.cot_set_tuning(k, v) == 0
-    assert E.cot_set_tuning(15, 1) == 0
     E.emul_set_dma_mode(dma)
-    try:
+    with _lib.tuned(E, **keys, CONV_LDS=1):
         ws = torch.full((E.cot_conv3x3g_workspace(N, C, C, G, H, W),), 0x7f, dtype=torch.uint8)
         y, init = torch.full_like(x, float("nan")), torch.randn(N, C, H, W).bfloat16()
         accumulate = rng.choice([0, 1])
         gx = init.clone() if accumulate else torch.full_like(x, float("nan"))
         assert E.cot_conv3x3g_forward(P(x), P(w), P(y), P(masks), P(ws), N, C, C, G, H, W, BF, None) == 0
         assert E.cot_conv3x3g_backward_data(P(gy), P(w), P(gx), accumulate, P(masks), P(ws), N, C, C, G, H, W, BF, None) == 0
-    finally:
-        for k in keys:
-            E.cot_set_tuning(k, 1)
-        E.emul_set_dma_mode(0)
+    E.emul_set_dma_mode(0)
     want = xf.grad + (init.float() if accumulate else 0)
     return close(y, yr.detach()) and close(gx, want, 3e-2), ("conv3x3g lds", N, C, G, H, W, keys, dma, accumulate)
 
@@ -235,7 +237,7 @@ def case_bn(rng):
         N = 2
     dtype = rng.choice([torch.float32, torch.bfloat16])
     act, use_res = rng.choice([0, 1, 2]), rng.random() < 0.5
-    keys = {12: rng.choice([0, 1]), 18: rng.choice([0, 256]), 21: rng.choice([0, 1]), 40: rng.choice([0, 1])}
+    keys = dict(BN_FOLD=rng.choice([0, 1]), BN_SMALL_M=rng.choice([0, 256]), BN_CHAN=rng.choice([0, 1]), BN_CHAN7=rng.choice([0, 1]))
     HW = H * W
     dt = tke._lib.dtype_code(dtype)
     x = (torch.randn(N, C, H, W) * 1.5 + 0.7).to(dtype)
@@ -250,9 +252,7 @@ def case_bn(rng):
         z = z + rr
     yr = {0: lambda t: t, 1: torch.relu, 2: F.silu}[act](z)
     yr.backward(dy.float())
-    for k, v in keys.items():
-        assert E.cot_set_tuning(k, v) == 0
-    try:
+    with _lib.tuned(E, **keys):
         nb = E.cot_bn_relu_mask_bytes(N, C, HW, dt) if (act == 1 and use_res) else 0
         outs = []
         for use_mask in ([False, True] if nb else [False]):
@@ -276,8 +276,6 @@ def case_bn(rng):
                                            P(ws), N, C, HW, act, dt, None)
                 assert rc == (-2 if act == 2 and use_res else 0)  # (SiLU after a residual add: forward only)
             outs.append((y, mean, rstd, dx, dres, dg, db))
-    finally:
-        E.cot_set_tuning(12, 1), E.cot_set_tuning(18, 256), E.cot_set_tuning(21, 1), E.cot_set_tuning(40, 1)
     desc = ("bn", N, C, H, W, str(dtype), act, use_res, keys, bool(nb))
     if len(outs) == 2 and not all(torch.equal(a, b) for a, b in zip(*outs)):
         return False, desc
@@ -306,8 +304,7 @@ def case_stem(rng):
     wf = w.float().requires_grad_(True)
     yr = F.conv2d(x.float(), wf, None, 2, 3)
     yr.backward(gy.float())
-    assert E.cot_set_tuning(41, lds) == 0
-    try:
+    with _lib.tuned(E, STEM_LDS=lds):
         nb = E.cot_stem7x7s2_workspace(N, H, W)
         if nb == 0:
             return True, ("stem: geometry not covered", N, H, W)
@@ -315,8 +312,6 @@ def case_stem(rng):
         assert E.cot_stem7x7s2_forward(P(x), P(w), P(y), N, H, W, BF, None) == 0
         ws, gw = torch.full((nb,), 0x7f, dtype=torch.uint8), torch.full_like(w, float("nan"))
         assert E.cot_stem7x7s2_backward_weight(P(gy), P(x), P(gw), P(ws), N, H, W, BF, None) == 0
-    finally:
-        E.cot_set_tuning(41, 1)
     ok = torch.allclose(y.float(), yr.detach(), atol=2e-2, rtol=2e-2)
     ok = ok and (gw.float() - wf.grad).abs().max().item() <= 1e-2 * wf.grad.abs().max().item() + 1e-2
     return ok, ("stem", N, H, W, lds)
@@ -345,15 +340,12 @@ def case_pool2(rng):
     yr = BlurPool2d(C)(xr)
     yr.backward(gy.double())
     outs = []
-    try:
-        for blk in (1, 0):
-            assert E.cot_set_tuning(27, blk) == 0
+    for blk in (1, 0):
+        with _lib.tuned(E, POOL_TILE=blk):
             y, gx = torch.full((N, C, Ho, Wo), float("nan")).to(dtype), torch.full_like(x, float("nan"))
             assert E.cot_blurpool3x3s2_forward(P(x), P(y), N * C, H, W, dt, None) == 0
             assert E.cot_blurpool3x3s2_backward(P(gy), P(gx), N * C, H, W, dt, None) == 0
             outs.append((y, gx))
-    finally:
-        E.cot_set_tuning(27, 1)
     tol = 1e-6 if dtype == torch.float32 else 1.5e-2
     ok = torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
     ok = ok and torch.allclose(outs[0][0].double(), yr.detach(), atol=tol, rtol=tol) and torch.allclose(outs[0][1].double(), xr.grad, atol=tol, rtol=tol)
@@ -372,17 +364,14 @@ def case_conv1x1_stages(rng):
     w = (torch.randn(Co, Ci) * Ci ** -0.5).bfloat16()
     ws = torch.empty(max(E.cot_conv1x1_workspace(N, Ci, Co, HW, 0), 256), dtype=torch.uint8)
     E.emul_set_dma_mode(dma)
-    assert E.cot_set_tuning(17, k17) == 0
     outs = []
-    try:
-        for ns3 in (2, 0):
-            assert E.cot_set_tuning(43, ns3) == 0
+    for ns3 in (2, 0):
+        with _lib.tuned(E, CONV_LDS_BITS=k17, CONV_FLAT_NS3=ns3):
             y, gx = torch.full((N, Co, H, W), float("nan")).bfloat16(), torch.full((N, Ci, H, W), float("nan")).bfloat16()
             assert E.cot_conv1x1_forward(P(x), None, Ci, P(w), None, P(y), N, Ci, Co, HW, BF, None) == 0
             assert E.cot_conv1x1_backward_data(P(gy), P(w), P(gx), None, Ci, 0, P(ws), N, Ci, Co, HW, BF, None) == 0
             outs.append((y, gx))
-    finally:
-        E.cot_set_tuning(43, 1), E.cot_set_tuning(17, 0), E.emul_set_dma_mode(0)
+    E.emul_set_dma_mode(0)
     ok = torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
     ok = ok and close(outs[0][0], F.conv2d(x.float(), w.float()[:, :, None, None]))
     ok = ok and close(outs[0][1], F.conv2d(gy.float(), w.float().t().contiguous()[:, :, None, None]), 3e-2)
@@ -420,7 +409,7 @@ def case_bn_ps(rng):
     N, C = rng.randint(2, 24), rng.randint(1, 5)
     H, W = rng.choice([(7, 7), (4, 4), (8, 8), (3, 5), (14, 14), (2, 2)])
     act, use_res, give_y = rng.choice([0, 1, 2]), rng.random() < 0.6, rng.random() < 0.5
-    keys = {12: rng.choice([0, 1]), 18: rng.choice([0, 256]), 21: rng.choice([0, 1]), 40: rng.choice([0, 1])}
+    keys = dict(BN_FOLD=rng.choice([0, 1]), BN_SMALL_M=rng.choice([0, 256]), BN_CHAN=rng.choice([0, 1]), BN_CHAN7=rng.choice([0, 1]))
     HW, dt = H * W, tke._lib.dtype_code(torch.float32)
     x, dy = torch.randn(N, C, H, W) * 1.5 + 0.7, torch.randn(N, C, H, W)
     res = torch.randn(N, C, H, W) if use_res else None
@@ -434,9 +423,7 @@ def case_bn_ps(rng):
         z = z + rr
     yr = {0: lambda t: t, 1: torch.relu, 2: F.silu}[act](z)
     yr.backward(dy)
-    for k, v in keys.items():
-        assert E.cot_set_tuning(k, v) == 0
-    try:
+    with _lib.tuned(E, **keys):
         y, mean, rstd = torch.full_like(x, float("nan")), torch.empty(C), torch.empty(C)
         ws = torch.empty(E.cot_bn_act_workspace(N, C))
         assert E.cot_bn_act_forward_ps(P(x), P(res), P(y), P(gamma), P(beta), P(mean), P(rstd), None, None, None, P(ws), P(ps),
@@ -446,8 +433,6 @@ def case_bn_ps(rng):
         need_y = act == 1 and use_res
         rc = E.cot_bn_act_backward_ps(P(dy), P(x), P(y) if (need_y or give_y) else None, P(dx), P(dres), P(gamma), P(beta), P(mean),
                                       P(rstd), P(dg), P(db), P(ws), P(ps), N, C, HW, act, dt, None)
-    finally:
-        E.cot_set_tuning(12, 1), E.cot_set_tuning(18, 256), E.cot_set_tuning(21, 1), E.cot_set_tuning(40, 1)
     desc = ("bn ps", N, C, H, W, act, use_res, give_y, keys)
     if act == 2:
         return rc == -2 and ((y - yr.detach()).abs() <= 2e-5 * (1 + yr.detach().abs())).all().item(), desc
@@ -828,14 +813,10 @@ def test_random_shapes(seed):
     rng = random.Random(seed)
     torch.manual_seed(seed)
     failures = []
-    try:
-        for _ in range(40):
-            ok, desc = rng.choice(CASES)(rng)
-            if not ok:
-                failures.append(desc)
-    finally:
-        E.cot_set_tuning(10, 0)
-        E.cot_set_tuning(11, 2048)
+    for _ in range(40):
+        ok, desc = rng.choice(CASES)(rng)
+        if not ok:
+            failures.append(desc)
     assert not failures, failures
 
 
@@ -863,13 +844,8 @@ def case_mix(rng):
     mk = lambda *s: torch.randn(*s, dtype=torch.float64).to(dtype)  # noqa: E731
     x, w1, w2 = mk(N, C, H, W), mk(N, heads, wC, 9, H, W), mk(N, heads, wC, 25, H, W)
     gout = mk(N, 2 * heads * C, H, W)
-    E.cot_set_tuning(52, lanes)
-    E.cot_set_tuning(53, ppl)
-    try:
+    with _lib.tuned(E, MIX_LANES=lanes, MIX_PPL=ppl):
         out, gx, gw1, gw2, names = tke._mix_run(E, x, w1, w2, gout)
-    finally:
-        E.cot_set_tuning(52, 256)
-        E.cot_set_tuning(53, 0)
     od = torch.float32 if dtype == torch.bfloat16 else dtype
     want = (cref.mix_forward(x.to(od), w1.to(od), w2.to(od), 1, 1, 2, 1),
             cref.mix_backward_input(gout.to(od), w1.to(od), w2.to(od), x.shape, 1, 1, 2, 1, False),
@@ -932,9 +908,9 @@ def case_bn_tail(rng):
     if N * H * W < 4:
         N = 4
     dtype, lay_k, sums = rng.choice([torch.float32, torch.bfloat16]), rng.choice([0, 1]), rng.random() < 0.5
-    E.cot_set_tuning(12, 1)
     desc = ("bn tail", N, C, H, W, str(dtype), lay_k, sums)
-    return _asserting(lambda: bn_tail_case(E, N, C, H, W, dtype, lay_k, sums, seed=rng.randint(0, 10 ** 6)), desc)
+    with _lib.tuned(E, BN_FOLD=1):
+        return _asserting(lambda: bn_tail_case(E, N, C, H, W, dtype, lay_k, sums, seed=rng.randint(0, 10 ** 6)), desc)
 
 
 def case_rowstats(rng):

@@ -61,8 +61,6 @@ def device_fuzz():
         tfe.ON_DEVICE = False
         for n, f in oracle_fns.items():
             setattr(cref, n, f)
-        for k, v in ((10, 0), (11, 2048)):
-            dev.cot_set_tuning(k, v)
 
 
 def run_cases(tfe, seed, count, cases=None, descs=None):

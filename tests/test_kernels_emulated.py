@@ -2,6 +2,7 @@
 launch-loop shim (tests/emul/), driven through the C ABI with CPU pointers and compared with the oracle.
 This is not the parity gate (tests/test_agg_gpu.py on a real MI355X is); it exists so that indexing bugs are
 caught in the GPU-less build container."""
+import contextlib
 import copy
 import ctypes
 import os
@@ -19,6 +20,7 @@ try:
 except FileNotFoundError as e:  # no host compiler: skip, the GPU tests still gate parity
     _EMUL = None
     _WHY = repr(e)
+T = _lib.Tune(_EMUL)  # the tuning keys by name: T.BN_FOLD
 # (a build that succeeds but does not load -- an undefined symbol -- is an error, not a reason to skip 1000 tests)
 
 pytestmark = pytest.mark.skipif(_EMUL is None, reason="host emulation build unavailable")
@@ -30,20 +32,17 @@ def P(t):
 
 @pytest.fixture(autouse=True)
 def _default_knobs():
-    # the emulated tests use tensors of a few hundred samples per channel: keep them on the STREAMING BatchNorm kernels
-    # (the fp64 small-batch path, cot_set_tuning(18), has its own test below)
-    if _EMUL is not None:
-        _EMUL.cot_set_tuning(12, 0)  # (library default since round 3: folded; the tests name the form they want)
-        _EMUL.cot_set_tuning(18, 0)
-        _EMUL.cot_set_tuning(21, 0)  # ... and off the channel-resident ones (own test: `chan` below)
-    yield
-    if _EMUL is not None:  # process-global developer knobs back to their defaults after every test
-        _EMUL.cot_set_tuning(10, 0)
-        _EMUL.cot_set_tuning(11, 2048)
-        _EMUL.cot_set_tuning(12, 0)
-        _EMUL.cot_set_tuning(17, 0)
-        _EMUL.cot_set_tuning(18, 256)
-        _EMUL.cot_set_tuning(21, 1)
+    """This file's baseline on top of the library's defaults.  The emulated tests use tensors of a few hundred samples per channel:
+    BN_SMALL_M=0 and BN_CHAN=0 keep them on the STREAMING BatchNorm kernels (the fp64 small-batch path and the channel-resident
+    kernels have their own tests below), BN_FOLD=0 on the separate finalize launch (library default since round 3: folded; the tests
+    name the form they want).  A test sets further keys by name and need not put them back: after each test every key, whoever set
+    it, is at the library's default again."""
+    if _EMUL is None:
+        yield
+        return
+    with _lib.tuned(_EMUL, BN_FOLD=0, BN_SMALL_M=0, BN_CHAN=0):
+        yield
+    _lib.reset_tuning(_EMUL)
 
 
 def to_layout(t, layout):
@@ -121,12 +120,9 @@ def test_non_finite_values_propagate_as_in_the_reference(C, H, W, dtype):
 
 @pytest.fixture
 def tuning():
-    def set_(version=0, fwd_p=4, bwd_p=2, xchg=0, jp=0, nw=4, pad=0, xcd=0, split=0, dot2=1, d_jp=0, d_xcd=-1, d_nw=0, d_safe=1, d_db=1):
-        for k, v in ((0, version), (1, fwd_p), (2, bwd_p), (3, xchg), (4, jp), (5, nw), (6, pad), (7, xcd), (8, split),
-                     (29, dot2), (30, d_jp), (31, d_xcd), (32, d_nw), (33, d_safe), (34, d_db)):
-            assert _EMUL.cot_set_tuning(k, v) == 0
-    yield set_
-    set_()
+    """tuning(AGG_VERSION=3, ...): the keys hold for the rest of the test"""
+    with contextlib.ExitStack() as stack:
+        yield lambda **knobs: stack.enter_context(_lib.tuned(_EMUL, **knobs))
 
 
 _ALL_VARIANTS = ["v1", "v2_dpp", "v2_shfl", "v2_P8", "v3_lds", "v3_lds_P8_jp2", "v3_lds_jp8", "v3_lds_nw8_bP4",
@@ -141,15 +137,19 @@ _VERSION_CASES = [(c, h, w, dt, v) for (c, h, w) in _SHAPES for dt in (torch.flo
 @pytest.mark.parametrize("C,H,W,dtype,variant", _VERSION_CASES)
 def test_k3_kernel_versions(C, H, W, dtype, variant, tuning):
     """every 3x3 kernel generation and lane-exchange primitive against the oracle (NCHW)"""
-    kw = {"v1": dict(version=1), "v2_dpp": dict(version=2), "v2_shfl": dict(version=2, xchg=1),
-          "v2_P8": dict(version=2, fwd_p=8), "v3_lds": dict(version=3), "v3_lds_P8_jp2": dict(version=3, fwd_p=8, jp=2),
-          "v3_lds_jp8": dict(version=3, jp=8), "v3_lds_nw8_bP4": dict(version=3, nw=8, bwd_p=4, pad=8),
-          "v3_lds_xcd_split": dict(version=3, xcd=1, split=1),
+    kw = {"v1": dict(AGG_VERSION=1), "v2_dpp": dict(AGG_VERSION=2), "v2_shfl": dict(AGG_VERSION=2, AGG_XCHG=1),
+          "v2_P8": dict(AGG_VERSION=2, AGG_PPL_FWD=8), "v3_lds": dict(AGG_VERSION=3),
+          "v3_lds_P8_jp2": dict(AGG_VERSION=3, AGG_PPL_FWD=8, AGG_V3_GROUPS=2), "v3_lds_jp8": dict(AGG_VERSION=3, AGG_V3_GROUPS=8),
+          "v3_lds_nw8_bP4": dict(AGG_VERSION=3, AGG_V3_WAVES=8, AGG_PPL_BWD=4, AGG_V3_LDS_KIB=8),
+          "v3_lds_xcd_split": dict(AGG_VERSION=3, AGG_V3_XCD=1, AGG_BWD_SPLIT=1),
           # automatic dispatch (version 0): bf16 fused backward at W = 14 / 28 / 56 takes the packed dot-product kernel
           # (csrc/agg_dot2.hip) in its phase / workgroup / masking variants; everything else the LDS kernel
-          "dot2": dict(), "dot2_jp2_nw2_fast_xcd": dict(d_jp=2, d_nw=2, d_safe=0, d_xcd=1), "dot2_jp4_nw4": dict(d_jp=4, d_nw=4), "dot2_single_buffer": dict(d_db=0), "dot2_jp4_single_buffer": dict(d_db=0, d_jp=4), "dot2_nw7": dict(d_nw=7), "dot2_jp8_roll": dict(d_jp=8),
-          "dot2_off": dict(dot2=0)}[variant]
-    tuning(**kw)
+          "dot2": dict(), "dot2_jp2_nw2_fast_xcd": dict(DOT2_GROUPS=2, DOT2_WAVES=2, DOT2_SAFE=0, DOT2_XCD=1),
+          "dot2_jp4_nw4": dict(DOT2_GROUPS=4, DOT2_WAVES=4), "dot2_single_buffer": dict(DOT2_DOUBLE_BUFFER=0),
+          "dot2_jp4_single_buffer": dict(DOT2_DOUBLE_BUFFER=0, DOT2_GROUPS=4), "dot2_nw7": dict(DOT2_WAVES=7), "dot2_jp8_roll": dict(DOT2_GROUPS=8),
+          "dot2_off": dict(DOT2=0)}[variant]
+    # (the lane exchange and the tile order named, not probed / chosen by plane size: AGG_XCHG=0 the DPP wave shift, AGG_V3_XCD=0 off)
+    tuning(**{"AGG_XCHG": 0, "AGG_V3_XCD": 0, **kw})
     g = torch.Generator().manual_seed(C + W)
     N, wC = 2, C // 8  # small channel counts keep the 256-host-thread emulation fast; indexing is size-agnostic
     x = torch.randn(N, C, H, W, generator=g).to(dtype)
@@ -303,18 +303,12 @@ def test_mix_tile_kernels(C, wC, H, W, heads, dtype, lanes, ppl):
     w1 = torch.randn(N, heads, wC, 9, H, W, dtype=torch.float64, generator=g).to(dtype)
     w2 = torch.randn(N, heads, wC, 25, H, W, dtype=torch.float64, generator=g).to(dtype)
     gout = torch.randn(N, 2 * heads * C, H, W, dtype=torch.float64, generator=g).to(dtype)
-    _EMUL.cot_set_tuning(52, lanes)
-    _EMUL.cot_set_tuning(53, ppl)  # pixels per lane: automatic / forced narrower
-    try:
+    with _lib.tuned(_EMUL, MIX_LANES=lanes, MIX_PPL=ppl):  # pixels per lane: automatic / forced narrower
         out, gx, gw1, gw2, names = _mix_run(_EMUL, x, w1, w2, gout)
         assert names == ["aggmix_fwd_tile", "aggmix_bwd_input_tile", "aggmix_bwd_weight_tile"], names
-        _EMUL.cot_set_tuning(51, 1)
-        ref = _mix_run(_EMUL, x, w1, w2, gout)
+        with _lib.tuned(_EMUL, MIX_GENERIC=1):
+            ref = _mix_run(_EMUL, x, w1, w2, gout)
         assert ref[4] == ["aggmix_fwd", "aggmix_bwd_input", "aggmix_bwd_weight"]
-    finally:
-        _EMUL.cot_set_tuning(51, 0)
-        _EMUL.cot_set_tuning(52, 256)
-        _EMUL.cot_set_tuning(53, 0)
     od = torch.float32 if dtype == torch.bfloat16 else dtype
     want = (cref.mix_forward(x.to(od), w1.to(od), w2.to(od), 1, 1, 2, 1),
             cref.mix_backward_input(gout.to(od), w1.to(od), w2.to(od), x.shape, 1, 1, 2, 1, False),
@@ -400,11 +394,10 @@ def test_bn_act_kernels_match_torch(N, C, H, W, act, use_res, dtype, fold, reque
     if fold == "chan-elementwise" and (H * W) % 7 != 0:
         pytest.skip("key 40 only matters on odd planes that are multiples of 7")
     if str(fold).startswith("chan"):
-        assert _EMUL.cot_set_tuning(21, 1) == 0
-        assert _EMUL.cot_set_tuning(40, 0 if fold == "chan-elementwise" else 1) == 0
-        request.addfinalizer(lambda: _EMUL.cot_set_tuning(40, 1))
+        assert _EMUL.cot_set_tuning(T.BN_CHAN, 1) == 0
+        assert _EMUL.cot_set_tuning(T.BN_CHAN7, 0 if fold == "chan-elementwise" else 1) == 0
     else:
-        assert _EMUL.cot_set_tuning(12, fold) == 0
+        assert _EMUL.cot_set_tuning(T.BN_FOLD, fold) == 0
     """csrc/bn_act.hip (host-emulated) against torch's batch_norm + activation + residual, forward and backward"""
     g = torch.Generator().manual_seed(N * C + H)
     x = (torch.randn(N, C, H, W, generator=g) * 1.5 + 0.7).to(dtype)
@@ -497,11 +490,11 @@ def test_conv1x1_flat_three_stage_ring(N, Ci, Co, H, dma, request):
     gy = torch.randn(N, Co, H, H).bfloat16()
     ws = torch.empty(max(_EMUL.cot_conv1x1_workspace(N, Ci, Co, HW, 0), 256), dtype=torch.uint8)
     _EMUL.emul_set_dma_mode(dma)
-    assert _EMUL.cot_set_tuning(17, 1 << 8) == 0  # (no 64-row blocks for few-tile launches: the 128-row tiles are the subject)
-    request.addfinalizer(lambda: (_EMUL.cot_set_tuning(43, 1), _EMUL.cot_set_tuning(17, 0), _EMUL.emul_set_dma_mode(0)))
+    assert _EMUL.cot_set_tuning(T.CONV_LDS_BITS, 1 << 8) == 0  # (no 64-row blocks for few-tile launches: the 128-row tiles are the subject)
+    request.addfinalizer(lambda: _EMUL.emul_set_dma_mode(0))
     outs = []
     for ns3 in (2, 0):
-        assert _EMUL.cot_set_tuning(43, ns3) == 0
+        assert _EMUL.cot_set_tuning(T.CONV_FLAT_NS3, ns3) == 0
         y, gx = torch.full((N, Co, H, H), float("nan")).bfloat16(), torch.full_like(x, float("nan"))
         assert _EMUL.cot_conv1x1_forward(P(x), None, Ci, P(w), None, P(y), N, Ci, Co, HW, dt, None) == 0, _EMUL.cot_last_error()
         assert _EMUL.cot_conv1x1_backward_data(P(gy), P(w), P(gx), None, Ci, 0, P(ws), N, Ci, Co, HW, dt, None) == 0
@@ -511,11 +504,8 @@ def test_conv1x1_flat_three_stage_ring(N, Ci, Co, H, dma, request):
     assert torch.allclose(outs[0][0].float(), ref, atol=2e-2, rtol=2e-2)
     buf = ctypes.create_string_buffer(2048)
     _EMUL.cot_launch_log(buf, 2048)
-    assert _EMUL.cot_set_tuning(43, 2) == 0 and _EMUL.cot_set_tuning(26, 1) == 0
-    try:
+    with _lib.tuned(_EMUL, CONV_FLAT_NS3=2, DRY_RUN=1):
         _EMUL.cot_conv1x1_forward(P(x), None, Ci, P(w), None, P(y), N, Ci, Co, HW, dt, None)
-    finally:
-        assert _EMUL.cot_set_tuning(26, 0) == 0
     _EMUL.cot_launch_log(buf, 2048)
     assert "NS=3" in buf.value.decode() or "NS = 3" in buf.value.decode(), buf.value
 
@@ -537,10 +527,10 @@ def test_conv1x1_big_tiles_permuted_x_stage(N, Ci, Co, H, W, split, dma, request
     gy = torch.randn(N, Co, H, W).bfloat16()
     ws = torch.empty(max(_EMUL.cot_conv1x1_workspace(N, Ci, Co, HW, 0), 256), dtype=torch.uint8)
     _EMUL.emul_set_dma_mode(dma)
-    request.addfinalizer(lambda: (_EMUL.cot_set_tuning(48, 7), _EMUL.emul_set_dma_mode(0)))
+    request.addfinalizer(lambda: _EMUL.emul_set_dma_mode(0))
     outs = []
     for sw in (7, 0, 1, 2, 4):  # (bit 0: the X stage, bits 1 / 2: the W tile's / transposed W tile's permutation, conflict-free form)
-        assert _EMUL.cot_set_tuning(48, sw) == 0
+        assert _EMUL.cot_set_tuning(T.CONV_BIG_XSWZ, sw) == 0
         y, gx = torch.full((N, Co, H, W), float("nan")).bfloat16(), torch.full_like(x, float("nan"))
         assert _EMUL.cot_conv1x1_forward(P(x1), P(x2) if split else None, split or Ci, P(w), None, P(y), N, Ci, Co, HW, dt,
                                          None) == 0, _EMUL.cot_last_error()
@@ -562,9 +552,9 @@ def test_bn_relu_sign_mask_equals_the_saved_output_path(N, C, H, W, fold, ps_on,
     elements, the backward reads those instead of y -- outputs, statistics and every gradient bit-identical to the _ps pair,
     on the three kernel families; the mask is exactly (y > 0); geometries the mask does not cover are refused"""
     if fold == "chan":
-        assert _EMUL.cot_set_tuning(21, 1) == 0
+        assert _EMUL.cot_set_tuning(T.BN_CHAN, 1) == 0
     else:
-        assert _EMUL.cot_set_tuning(12, fold) == 0
+        assert _EMUL.cot_set_tuning(T.BN_FOLD, fold) == 0
     g = torch.Generator().manual_seed(N + C * H)
     dt = _lib.dtype_code(torch.bfloat16)
     x = (torch.randn(N, C, H, W, generator=g) * 1.5 + 0.3).bfloat16()
@@ -574,9 +564,8 @@ def test_bn_relu_sign_mask_equals_the_saved_output_path(N, C, H, W, fold, ps_on,
     nb = _EMUL.cot_bn_relu_mask_bytes(N, C, H * W, dt)
     assert nb == N * C * H * W // 8
     assert _EMUL.cot_bn_relu_mask_bytes(N, C, 49, dt) == 0   # odd plane
-    assert _EMUL.cot_set_tuning(18, 256) == 0                # (the one-wave fp64 path of tiny batches takes no mask)
-    assert _EMUL.cot_bn_relu_mask_bytes(2, C, 64, dt) == 0 and _EMUL.cot_bn_relu_mask_bytes(8, C, 64, dt) == 8 * C * 8
-    assert _EMUL.cot_set_tuning(18, 0) == 0
+    with _lib.tuned(_EMUL, BN_SMALL_M=256):  # (the one-wave fp64 path of tiny batches takes no mask)
+        assert _EMUL.cot_bn_relu_mask_bytes(2, C, 64, dt) == 0 and _EMUL.cot_bn_relu_mask_bytes(8, C, 64, dt) == 8 * C * 8
     assert _EMUL.cot_bn_relu_mask_bytes(N, C, H * W, _lib.dtype_code(torch.float32)) == 0
     outs = []
     for use_mask in (False, True):
@@ -622,7 +611,7 @@ def test_bn_act_with_stochastic_depth(N, C, H, W, dtype, path):
     (models/cotnet.py:250-262 with models/layers/drop.py:140-168) against torch autograd in fp32 on the same inputs -- the
     streaming kernels (the scale forces the image-by-image form; tiny tensors leave the fp64 small-batch path) and the
     channel-resident ones"""
-    assert _EMUL.cot_set_tuning(21, 1 if path == "chan" else 0) == 0 and _EMUL.cot_set_tuning(18, 256) == 0
+    assert _EMUL.cot_set_tuning(T.BN_CHAN, 1 if path == "chan" else 0) == 0 and _EMUL.cot_set_tuning(T.BN_SMALL_M, 256) == 0
     g = torch.Generator().manual_seed(N + C * H)
     x = (torch.randn(N, C, H, W, generator=g) * 1.5 + 0.7).to(dtype)
     res = torch.randn(N, C, H, W, generator=g).to(dtype)
@@ -672,17 +661,14 @@ def test_ring_depth_choice_does_not_change_results(H):
     assert _EMUL.cot_conv3x3g_masks(P(masks), H, H, None) == 0
     ws = torch.empty(_EMUL.cot_conv3x3g_workspace(N, Ci, Co, G, H, H), dtype=torch.uint8)
     outs = []
-    try:
-        for thr in (1, 1 << 30):
-            assert _EMUL.cot_set_tuning(14, thr) == 0
+    for thr in (1, 1 << 30):
+        with _lib.tuned(_EMUL, C1_SHALLOW_RING_WAVES=thr):
             y1, y3, g1 = torch.empty(N, Co, H, H).bfloat16(), torch.empty(N, Co, H, H).bfloat16(), torch.empty_like(x)
             assert _EMUL.cot_conv1x1_forward(P(x), None, Ci, P(w1), None, P(y1), N, Ci, Co, H * H, 2, None) == 0
             ws1 = torch.empty(_EMUL.cot_conv1x1_workspace(N, Ci, Co, H * H, 0), dtype=torch.uint8)
             assert _EMUL.cot_conv1x1_backward_data(P(y1), P(w1), P(g1), None, Ci, 0, P(ws1), N, Ci, Co, H * H, 2, None) == 0
             assert _EMUL.cot_conv3x3g_forward(P(x), P(w3), P(y3), P(masks), P(ws), N, Ci, Co, G, H, H, 2, None) == 0
             outs.append((y1, g1, y3))
-    finally:
-        _EMUL.cot_set_tuning(14, 0)
     for a, b in zip(*outs):
         assert torch.equal(a, b)
     ref = torch.nn.functional.conv2d(x.float(), w3.float(), None, 1, 1, 1, G)
@@ -695,7 +681,7 @@ def test_bn_small_batch_fp64_path(N, C, H, W, act, use_res):
     """csrc/bn_act.hip "small batches": the CoT layer's se branch normalises over the batch alone (2 samples per channel
     in the 7x7 fixture).  Against an fp64 evaluation; the 2-sample input gradient -- catastrophic cancellation in fp32 --
     must come out at fp32-rounding accuracy of the fp64 result, not at the 1e-3 relative level MIOpen's kernel shows."""
-    assert _EMUL.cot_set_tuning(18, 4096) == 0  # (the test shapes have up to 80 samples; the library default is 256)
+    assert _EMUL.cot_set_tuning(T.BN_SMALL_M, 4096) == 0  # (the test shapes have up to 80 samples; the library default is 256)
     g = torch.Generator().manual_seed(N + 7 * C)
     x = torch.randn(N, C, H, W, generator=g) * (0.05 if N == 2 else 1.0) + 0.3   # small variance: rstd ~ 20 .. 300
     res = torch.randn(N, C, H, W, generator=g) if use_res else None
@@ -747,11 +733,10 @@ def test_bn_apply_kernels_do_not_depend_on_the_grid(N, C, H, W, dtype, cap):
     dy = torch.randn(N, C, H, W, generator=g).to(dtype)
     gamma, beta = torch.rand(C, generator=g) + 0.5, torch.randn(C, generator=g) * 0.2
     dt = _lib.dtype_code(dtype)
-    assert _EMUL.cot_set_tuning(12, 0) == 0
+    assert _EMUL.cot_set_tuning(T.BN_FOLD, 0) == 0
     outs = {}
-    try:
-        for k in (0, cap):
-            assert _EMUL.cot_set_tuning(13, k) == 0
+    for k in (0, cap):
+        with _lib.tuned(_EMUL, BN_GRID_CAP=k):
             for act in (0, 1, 2):
                 y, dx, dres = torch.empty_like(x), torch.empty_like(x), torch.zeros_like(x)
                 mean, rstd, dgamma, dbeta = torch.empty(C), torch.empty(C), torch.empty(C), torch.empty(C)
@@ -762,8 +747,6 @@ def test_bn_apply_kernels_do_not_depend_on_the_grid(N, C, H, W, dtype, cap):
                 assert _EMUL.cot_bn_act_backward(P(dy), P(x), P(y), P(dx), P(dres) if with_res else None, P(gamma), P(beta), P(mean),
                                                  P(rstd), P(dgamma), P(dbeta), P(ws), N, C, H * W, act, dt, None) == 0
                 outs[(k, act)] = (y, dx, dres)
-    finally:
-        _EMUL.cot_set_tuning(13, 0)
     for act in (0, 1, 2):
         for a, b in zip(outs[(0, act)], outs[(cap, act)]):
             assert torch.equal(a, b)
@@ -853,14 +836,13 @@ def _conv1x1_ref(x, w, b):
     (1, 520, 40, 7, 7, 0, False),     # deep K (16.25 steps): the prefetch ring wraps several times, partial last step
     (1, 328, 136, 8, 8, 200, True),   # deep K over two slabs, M = 136 (data gradient: K = 136, 4.25 steps)
 ])
-@pytest.mark.parametrize("splits", [0, 3, -1])   # -1: the general (any H*W) LDS weight-gradient kernel, cot_set_tuning(17, 8)
+@pytest.mark.parametrize("splits", [0, 3, -1])   # -1: the general (any H*W) LDS weight-gradient kernel, cot_set_tuning(T.CONV_LDS_BITS, 8)
 def test_conv1x1_mfma_kernels(N, Ci, Co, H, W, c1, bias, splits, request):
-    assert _EMUL.cot_set_tuning(25, 1) == 0  # (the third-generation weight gradient has its own test below)
-    request.addfinalizer(lambda: _EMUL.cot_set_tuning(25, 0))
+    assert _EMUL.cot_set_tuning(T.WGRAD2_BITS, 1) == 0  # (the third-generation weight gradient has its own test below)
     if splits < 0:
-        assert _EMUL.cot_set_tuning(17, 8) == 0
+        assert _EMUL.cot_set_tuning(T.CONV_LDS_BITS, 8) == 0
         splits = 0
-    assert _EMUL.cot_set_tuning(11, -splits if splits else 2048) == 0
+    assert _EMUL.cot_set_tuning(T.C1_WGRAD_WAVES, -splits if splits else 2048) == 0
     torch.manual_seed(5)
     HW = H * W
     x = torch.randn(N, Ci, H, W).bfloat16()
@@ -899,7 +881,6 @@ def test_conv1x1_mfma_kernels(N, Ci, Co, H, W, c1, bias, splits, request):
     assert (gw.float() - wf.grad).abs().max().item() <= 1e-2 * scale + 1e-2
     if bias:
         assert (gb.float() - bf.grad).abs().max().item() <= 1e-2 * bf.grad.abs().max().item() + 1e-2
-    assert _EMUL.cot_set_tuning(11, 2048) == 0
 
 
 @pytest.mark.parametrize("N,Ci,Co,H,W,c1,bias", [
@@ -921,7 +902,7 @@ def test_conv1x1_mfma_kernels(N, Ci, Co, H, W, c1, bias, splits, request):
                                      (68, 2, 1), (128, 0, 1), (128, 2, 1), (128, 5, 0)])
 def test_conv1x1_weight_gradient_third_generation(N, Ci, Co, H, W, c1, bias, variant):
     """csrc/conv_wgrad2.hip behind cot_conv1x1_backward_weight: every tile shape, planes that are / are not multiples of 8 and
-    32 / 64 pixels, two slabs, the bias column, forced slice counts (cot_set_tuning(25) bits 24..), the three forms of the K loop
+    32 / 64 pixels, two slabs, the bias column, forced slice counts (cot_set_tuning(WGRAD2_BITS) bits 24..), the three forms of the K loop
     (default: 64-pixel stages + loader waves on planes of more than 64 pixels, prefetching 32-pixel stages below; bit 1 the
     plain form; bits 6 / 7 one form for every plane), the old chunk permutation (bit 2), LDS-DMA landing modes of the emulator
     -- against fp32 on the bf16-rounded operands, and against the second-generation kernels"""
@@ -938,7 +919,7 @@ def test_conv1x1_weight_gradient_third_generation(N, Ci, Co, H, W, c1, bias, var
     cc1 = c1 if split else Ci
     PN = lambda t: P(t) if t is not None else None
     try:
-        assert _EMUL.cot_set_tuning(25, bits | (force << 24)) == 0
+        assert _EMUL.cot_set_tuning(T.WGRAD2_BITS, bits | (force << 24)) == 0
         _EMUL.emul_set_dma_mode(dma)
         ws = torch.full((_EMUL.cot_conv1x1_workspace(N, Ci, Co, HW, 1 if bias else 0),), 0x7f, dtype=torch.uint8)
         gw = torch.full((Co, Ci), float("nan")).bfloat16()
@@ -950,7 +931,7 @@ def test_conv1x1_weight_gradient_third_generation(N, Ci, Co, H, W, c1, bias, var
         if bias:
             assert (gb.float() - gbr).abs().max().item() <= 1e-2 * gbr.abs().max().item() + 1e-2
         # the previous generation on the same data (same products, different summation order)
-        assert _EMUL.cot_set_tuning(25, 1) == 0
+        assert _EMUL.cot_set_tuning(T.WGRAD2_BITS, 1) == 0
         gw0 = torch.full_like(gw, float("nan"))
         gb0 = torch.full_like(gb, float("nan")) if bias else None
         ws0 = torch.full((_EMUL.cot_conv1x1_workspace(N, Ci, Co, HW, 1 if bias else 0),), 0x7f, dtype=torch.uint8)
@@ -958,7 +939,6 @@ def test_conv1x1_weight_gradient_third_generation(N, Ci, Co, H, W, c1, bias, var
         assert (gw.float() - gw0.float()).abs().max().item() <= 2e-2 * scale + 1e-2
     finally:
         _EMUL.emul_set_dma_mode(0)
-        assert _EMUL.cot_set_tuning(25, 0) == 0
 
 
 def test_conv1x1_weight_gradient_third_generation_non_finite_rows():
@@ -980,7 +960,7 @@ def test_conv1x1_weight_gradient_third_generation_non_finite_rows():
     assert (gw.float()[fin] - ref[fin]).abs().max() <= 1e-2 * ref[fin].abs().max() + 1e-2
 
 
-# (cot_set_tuning(17), cot_set_tuning(23), LDS-DMA landing mode of the emulator): key 17 bit 1 = 2-byte gathers instead of
+# (cot_set_tuning(CONV_LDS_BITS), cot_set_tuning(CONV_LDS2_BITS), LDS-DMA landing mode of the emulator): key 17 bit 1 = 2-byte gathers instead of
 # transposing reads, 256 = 128-channel blocks even for few tiles; key 23 bit 0 = second-generation kernel (conv_lds.hip), bit 1
 # = no fragment prefetch in the FLAT kernels, bit 2 = fragment prefetch in the BIG kernels; landing mode 1 = a copy lands only
 # when the issuing lane's counted vmcnt wait retires it (checks the hand-counted waits), 0 = at once (checks re-fill hazards)
@@ -990,11 +970,10 @@ _LDS_VARIANTS = [(0, 0, 0), (0, 0, 1), (2, 0, 1), (256, 0, 0), (0, 6, 0), (0, 6,
 @pytest.fixture
 def lds_variant(request):
     k17, k23, dma = request.param
-    assert _EMUL.cot_set_tuning(17, k17) == 0 and _EMUL.cot_set_tuning(23, k23) == 0
-    _EMUL.emul_set_dma_mode(dma)
-    yield k17
-    _EMUL.emul_set_dma_mode(0)
-    assert _EMUL.cot_set_tuning(17, 0) == 0 and _EMUL.cot_set_tuning(23, 0) == 0
+    with _lib.tuned(_EMUL, CONV_LDS_BITS=k17, CONV_LDS2_BITS=k23):
+        _EMUL.emul_set_dma_mode(dma)
+        yield k17
+        _EMUL.emul_set_dma_mode(0)
 
 
 @pytest.mark.parametrize("N,Ci,Co,H,W,c1,bias", [
@@ -1013,7 +992,7 @@ def lds_variant(request):
 ])
 @pytest.mark.parametrize("lds_variant", _LDS_VARIANTS, indirect=True)
 def test_conv1x1_lds_kernels(N, Ci, Co, H, W, c1, bias, lds_variant):
-    """LDS-pipelined 1x1 kernels (csrc/conv_lds2.hip, and conv_lds.hip behind cot_set_tuning(23) bit 0): every case satisfies
+    """LDS-pipelined 1x1 kernels (csrc/conv_lds2.hip, and conv_lds.hip behind cot_set_tuning(CONV_LDS2_BITS) bit 0): every case satisfies
     K % 32 == 0 so the LDS path is the one that runs; forward, data gradient, the accumulate flags of both output slabs,
     against torch in fp32 on the same bf16-rounded operands"""
     waves4 = lds_variant
@@ -1031,15 +1010,14 @@ def test_conv1x1_lds_kernels(N, Ci, Co, H, W, c1, bias, lds_variant):
     cc1 = c1 if split else Ci
     dt = _lib.dtype_code(torch.bfloat16)
     PN = lambda t: P(t) if t is not None else None
-    assert _EMUL.cot_set_tuning(15, 1) == 0
+    assert _EMUL.cot_set_tuning(T.CONV_LDS, 1) == 0
     y = torch.full((N, Co, H, W), float("nan")).bfloat16()
     assert _EMUL.cot_conv1x1_forward(P(x1), PN(x2), cc1, P(w), PN(b), P(y), N, Ci, Co, HW, dt, None) == 0, _EMUL.cot_last_error()
     assert torch.allclose(y.float(), yref.detach(), atol=2e-2, rtol=2e-2), (y.float() - yref).abs().max()
     # the same through the first-generation kernel: both paths must agree to rounding (same products, different order)
-    assert _EMUL.cot_set_tuning(15, 0) == 0
-    y0 = torch.full_like(y, float("nan"))
-    assert _EMUL.cot_conv1x1_forward(P(x1), PN(x2), cc1, P(w), PN(b), P(y0), N, Ci, Co, HW, dt, None) == 0
-    assert _EMUL.cot_set_tuning(15, 1) == 0
+    with _lib.tuned(_EMUL, CONV_LDS=0):
+        y0 = torch.full_like(y, float("nan"))
+        assert _EMUL.cot_conv1x1_forward(P(x1), PN(x2), cc1, P(w), PN(b), P(y0), N, Ci, Co, HW, dt, None) == 0
     assert (y.float() - y0.float()).abs().max() <= 2e-2 * yref.abs().max()
     if Co % 32 == 0 or True:
         ws = torch.empty(_EMUL.cot_conv1x1_workspace(N, Ci, Co, HW, 1 if bias else 0), dtype=torch.uint8)
@@ -1116,20 +1094,20 @@ def test_conv1x1_lds_kernels_partial_last_k_step(N, Ci, Co, H, W, dma):
     _EMUL.emul_set_dma_mode(dma)
     try:
         for k54 in (1, 0):
-            assert _EMUL.cot_set_tuning(54, k54) == 0
+            assert _EMUL.cot_set_tuning(T.CONV_K_TAIL, k54) == 0
             y, gx, ga = torch.full_like(gy, float("nan")), torch.full_like(x, float("nan")), init.clone()
             assert _EMUL.cot_conv1x1_forward(P(x), None, Ci, P(w), None, P(y), N, Ci, Co, HW, dt, None) == 0, _EMUL.cot_last_error()
             assert _EMUL.cot_conv1x1_backward_data(P(gy), P(w), P(gx), None, Ci, 0, P(ws), N, Ci, Co, HW, dt, None) == 0, _EMUL.cot_last_error()
             assert _EMUL.cot_conv1x1_backward_data(P(gy), P(w), P(ga), None, Ci, 1, P(ws), N, Ci, Co, HW, dt, None) == 0, _EMUL.cot_last_error()
             outs[k54] = (y.clone(), gx.clone(), ga.clone())
-        assert _EMUL.cot_set_tuning(54, 1) == 0 and _EMUL.cot_set_tuning(26, 1) == 0
+        assert _EMUL.cot_set_tuning(T.CONV_K_TAIL, 1) == 0 and _EMUL.cot_set_tuning(T.DRY_RUN, 1) == 0
         _EMUL.cot_conv1x1_forward(P(x), None, Ci, P(w), None, P(y), N, Ci, Co, HW, dt, None)
         _EMUL.cot_conv1x1_backward_data(P(gy), P(w), P(gx), None, Ci, 0, P(ws), N, Ci, Co, HW, dt, None)
         buf = ctypes.create_string_buffer(1 << 14)
         _EMUL.cot_launch_log(buf, 1 << 14)
         log = buf.value.decode()
     finally:
-        _EMUL.cot_set_tuning(26, 0), _EMUL.cot_set_tuning(54, 1), _EMUL.emul_set_dma_mode(0)
+        _EMUL.emul_set_dma_mode(0)
     assert log.count("conv1x1_lds_fwd2") == 2 and log.count("KT = 1") == (Ci % 32 != 0) + (Co % 32 != 0), log
     y, gx, ga = outs[1]
     assert torch.allclose(y.float(), yr, atol=2e-2, rtol=2e-2), (y.float() - yr).abs().max()
@@ -1145,11 +1123,12 @@ def test_conv1x1_lds_kernel_is_the_one_that_runs():
     w = torch.randn(32, 64).bfloat16()
     y = torch.zeros(1, 32, 16, 16).bfloat16()
     dt = _lib.dtype_code(torch.bfloat16)
-    assert _EMUL.cot_set_tuning(15, 1) == 0
+    assert _EMUL.cot_set_tuning(T.CONV_LDS, 1) == 0
     assert _EMUL.cot_conv1x1_lds_covers(64, 64, 0, 256) == 1 and _EMUL.cot_conv1x1_lds_covers(36, 36, 0, 256) == 0
     # (a depth on the 8-channel grid but off the 32-row K step: the KT instantiations, one slab only; tuning key 54 = 0: as before round 6)
     assert _EMUL.cot_conv1x1_lds_covers(40, 40, 0, 256) == 1 and _EMUL.cot_conv1x1_lds_covers(72, 40, 1, 256) == 0
-    assert _EMUL.cot_set_tuning(54, 0) == 0 and _EMUL.cot_conv1x1_lds_covers(40, 40, 0, 256) == 0 and _EMUL.cot_set_tuning(54, 1) == 0
+    with _lib.tuned(_EMUL, CONV_K_TAIL=0):
+        assert _EMUL.cot_conv1x1_lds_covers(40, 40, 0, 256) == 0
     assert _EMUL.cot_conv1x1_forward(P(x), None, 64, P(w), None, P(y), 1, 64, 32, 256, dt, None) == 0
     ref = torch.einsum("oc,nchw->nohw", w.float(), x.float())
     assert (y.float() - ref).abs().max() < 0.01 * ref.abs().max()  # (one bf16 rounding of outputs up to ~30)
@@ -1211,7 +1190,7 @@ def test_conv1x1_autograd_wiring_on_emulated_kernels(split, bias, monkeypatch):
 ])
 @pytest.mark.parametrize("splits", [0, 2])
 def test_conv3x3_grouped_mfma_kernels(N, C, G, H, W, splits):
-    assert _EMUL.cot_set_tuning(11, -splits if splits else 2048) == 0
+    assert _EMUL.cot_set_tuning(T.C1_WGRAD_WAVES, -splits if splits else 2048) == 0
     torch.manual_seed(7)
     x = torch.randn(N, C, H, W).bfloat16()
     w = (torch.randn(C, C // G, 3, 3) / (9 * C // G) ** 0.5).bfloat16()
@@ -1238,7 +1217,6 @@ def test_conv3x3_grouped_mfma_kernels(N, C, G, H, W, splits):
     assert rc == 0, _EMUL.cot_last_error()
     scale = wf.grad.abs().max().item()
     assert (gw.float() - wf.grad).abs().max().item() <= 1e-2 * scale + 1e-2
-    assert _EMUL.cot_set_tuning(11, 2048) == 0
 
 
 @pytest.mark.parametrize("N,Ci,Co,G,H,W", [
@@ -1267,7 +1245,7 @@ def test_conv3x3_grouped_weight_gradient_lds_staged(N, Ci, Co, G, H, W, force, d
     masks = torch.empty(_EMUL.cot_conv3x3g_masks_bytes(H, W), dtype=torch.uint8)
     assert _EMUL.cot_conv3x3g_masks(P(masks), H, W, None) == 0
     try:
-        assert _EMUL.cot_set_tuning(25, force << 24) == 0
+        assert _EMUL.cot_set_tuning(T.WGRAD2_BITS, force << 24) == 0
         _EMUL.emul_set_dma_mode(dma)
         ws = torch.full((_EMUL.cot_conv3x3g_workspace(N, Ci, Co, G, H, W),), 0x7f, dtype=torch.uint8)
         gw = torch.full((Co, Ci // G, 3, 3), float("nan")).bfloat16()
@@ -1281,7 +1259,6 @@ def test_conv3x3_grouped_weight_gradient_lds_staged(N, Ci, Co, G, H, W, force, d
         assert (gw.float() - gw0.float()).abs().max().item() <= 2e-2 * scale + 1e-2
     finally:
         _EMUL.emul_set_dma_mode(0)
-        assert _EMUL.cot_set_tuning(25, 0) == 0
 
 
 def test_conv3x3_grouped_weight_gradient_guard_decides_the_kernel():
@@ -1296,12 +1273,9 @@ def test_conv3x3_grouped_weight_gradient_guard_decides_the_kernel():
         x, gy = torch.zeros(N, Ci, H, W).bfloat16(), torch.zeros(N, Co, H, W).bfloat16()
         gw = torch.empty(Co, Ci // G, 3, 3).bfloat16()
         ws = torch.empty(_EMUL.cot_conv3x3g_workspace(N, Ci, Co, G, H, W), dtype=torch.uint8)
-        try:
-            assert _EMUL.cot_set_tuning(26, 1) == 0
+        with _lib.tuned(_EMUL, DRY_RUN=1):
             assert _EMUL.cot_conv3x3g_backward_weight_guarded(P(gy), P(x), P(gw), P(masks), P(ws), N, Ci, Co, G, H, W, dt, guard, None) == 0
             _EMUL.cot_launch_log(buf, 4096)
-        finally:
-            assert _EMUL.cot_set_tuning(26, 0) == 0
         return buf.value.decode()
     assert "conv1x1_wgrad_lds2" in kernels(2, 64, 64, 4, 14, 14, 15) and "wgrad_reduce" in kernels(8, 64, 64, 4, 14, 14, 15)
     assert "conv3x3g_wgrad_mfma" in kernels(2, 64, 64, 4, 14, 14, 14)      # one element short of W + 1
@@ -1335,9 +1309,9 @@ def test_conv3x3_grouped_lds_kernels(N, C, G, H, W, res, dma, request):
     """csrc/conv_lds.hip conv3x3g_lds_res (chunk-resident weights, tuning key 39 = 1) and conv3x3g_lds_fwd (per-step ring, 0):
     forward and data gradient incl. accumulate against torch on the same rounded operands, and against the first-generation
     kernel; LDS copies landing at the earliest and at the latest legal time (the vmcnt arithmetic and the buffer re-use)"""
-    assert _EMUL.cot_set_tuning(39, abs(res)) == 0 and _EMUL.cot_set_tuning(42, 2 if res < 0 else 0) == 0 and _EMUL.cot_set_tuning(44, 2 if res < 0 else 1) == 0 and _EMUL.cot_set_tuning(45, 2 if res < 0 else (1 if dma else 0)) == 0
+    assert _EMUL.cot_set_tuning(T.CONV3X3_RES, abs(res)) == 0 and _EMUL.cot_set_tuning(T.CONV3X3_WSINGLE, 2 if res < 0 else 0) == 0 and _EMUL.cot_set_tuning(T.CONV3X3_COLS, 2 if res < 0 else 1) == 0 and _EMUL.cot_set_tuning(T.CONV3X3_PERM, 2 if res < 0 else (1 if dma else 0)) == 0
     _EMUL.emul_set_dma_mode(dma)
-    request.addfinalizer(lambda: (_EMUL.cot_set_tuning(39, 1), _EMUL.cot_set_tuning(42, 1), _EMUL.cot_set_tuning(44, 1), _EMUL.cot_set_tuning(45, 1), _EMUL.emul_set_dma_mode(0)))  # (2: 16-channel groups too)
+    request.addfinalizer(lambda: _EMUL.emul_set_dma_mode(0))  # (2: 16-channel groups too)
     torch.manual_seed(17)
     x = torch.randn(N, C, H, W).bfloat16()
     w = (torch.randn(C, C // G, 3, 3) / (9 * C // G) ** 0.5).bfloat16()
@@ -1351,19 +1325,16 @@ def test_conv3x3_grouped_lds_kernels(N, C, G, H, W, res, dma, request):
     ws = torch.empty(_EMUL.cot_conv3x3g_workspace(N, C, C, G, H, W), dtype=torch.uint8)
     outs = []
     for gen in (1, 0):
-        assert _EMUL.cot_set_tuning(15, gen) == 0
+        assert _EMUL.cot_set_tuning(T.CONV_LDS, gen) == 0
         y = torch.full_like(x, float("nan"))
         assert _EMUL.cot_conv3x3g_forward(P(x), P(w), P(y), P(masks), P(ws), N, C, C, G, H, W, dt, None) == 0, _EMUL.cot_last_error()
         if gen == 1:  # which form ran (dry-run log of the same call)
-            assert _EMUL.cot_set_tuning(26, 1) == 0
-            try:
+            with _lib.tuned(_EMUL, DRY_RUN=1):
                 buf = ctypes.create_string_buffer(4096)
                 _EMUL.cot_launch_log(buf, 4096)  # (clears the log)
                 _EMUL.cot_conv3x3g_forward(P(x), P(w), P(y), P(masks), P(ws), N, C, C, G, H, W, dt, None)
                 _EMUL.cot_launch_log(buf, 4096)
                 log = buf.value.decode()
-            finally:
-                assert _EMUL.cot_set_tuning(26, 0) == 0
             assert "conv3x3g_lds_res" in log or "conv3x3g_lds_fwd" in log, log
             if not res:
                 assert "conv3x3g_lds_res" not in log, log
@@ -1378,7 +1349,7 @@ def test_conv3x3_grouped_lds_kernels(N, C, G, H, W, res, dma, request):
         assert torch.allclose(gx.float(), xf.grad, atol=3e-2, rtol=2e-2), (gen, (gx.float() - xf.grad).abs().max())
         assert torch.allclose(ga.float(), base.float() + xf.grad, atol=6e-2, rtol=2e-2), gen
         outs.append((y, gx))
-    assert _EMUL.cot_set_tuning(15, 1) == 0
+    assert _EMUL.cot_set_tuning(T.CONV_LDS, 1) == 0
     assert (outs[0][0].float() - outs[1][0].float()).abs().max() <= 2e-2 * yref.abs().max()
 
 
@@ -1396,7 +1367,7 @@ def test_conv3x3_lds_masks_by_selection():
     assert _EMUL.cot_conv3x3g_masks(P(masks), H, W, None) == 0
     ws = torch.empty(_EMUL.cot_conv3x3g_workspace(N, C, C, G, H, W), dtype=torch.uint8)
     y = torch.empty(N, C, H, W).bfloat16()
-    assert _EMUL.cot_set_tuning(15, 1) == 0
+    assert _EMUL.cot_set_tuning(T.CONV_LDS, 1) == 0
     assert _EMUL.cot_conv3x3g_forward(P(x), P(w), P(y), P(masks), P(ws), N, C, C, G, H, W, dt, None) == 0
     assert torch.isnan(y[:, :Kc].float()).all()
     assert torch.allclose(y[:, Kc:].float(), yref, atol=2e-2, rtol=2e-2)
@@ -1407,8 +1378,7 @@ def test_conv3x3_lds_padded_chunk_is_cleared_by_selection(res, request):
     """groups of 48 channels on the LDS kernels (chunk-resident form / per-step ring): the second 32-channel chunk of group 0 is
     half group 1's channels.  They meet zero weights -- and must be cleared by selection all the same: group 1 is all NaN here,
     group 0's outputs must not notice"""
-    assert _EMUL.cot_set_tuning(39, abs(res)) == 0 and _EMUL.cot_set_tuning(45, 2 if res < 0 else 0) == 0
-    request.addfinalizer(lambda: (_EMUL.cot_set_tuning(39, 1), _EMUL.cot_set_tuning(45, 1)))
+    assert _EMUL.cot_set_tuning(T.CONV3X3_RES, abs(res)) == 0 and _EMUL.cot_set_tuning(T.CONV3X3_PERM, 2 if res < 0 else 0) == 0
     torch.manual_seed(19)
     N, C, G, H, W = 2, 96, 2, 6, 8
     Kc = C // G
@@ -1421,15 +1391,12 @@ def test_conv3x3_lds_padded_chunk_is_cleared_by_selection(res, request):
     assert _EMUL.cot_conv3x3g_masks(P(masks), H, W, None) == 0
     ws = torch.empty(_EMUL.cot_conv3x3g_workspace(N, C, C, G, H, W), dtype=torch.uint8)
     y = torch.empty(N, C, H, W).bfloat16()
-    assert _EMUL.cot_set_tuning(15, 1) == 0
+    assert _EMUL.cot_set_tuning(T.CONV_LDS, 1) == 0
     buf = ctypes.create_string_buffer(1 << 12)
     _EMUL.cot_launch_log(buf, len(buf))
-    assert _EMUL.cot_set_tuning(26, 1) == 0
-    try:
+    with _lib.tuned(_EMUL, DRY_RUN=1):
         assert _EMUL.cot_conv3x3g_forward(P(x), P(w), P(y), P(masks), P(ws), N, C, C, G, H, W, dt, None) == 0
         _EMUL.cot_launch_log(buf, len(buf))
-    finally:
-        assert _EMUL.cot_set_tuning(26, 0) == 0
     assert ("conv3x3g_lds_res" if res else "conv3x3g_lds_fwd") in buf.value.decode(), buf.value
     assert _EMUL.cot_conv3x3g_forward(P(x), P(w), P(y), P(masks), P(ws), N, C, C, G, H, W, dt, None) == 0
     assert torch.allclose(y[:, :Kc].float(), yref, atol=2e-2, rtol=2e-2)
@@ -1667,8 +1634,7 @@ def test_fused_cot_layer_node_on_emulated_kernels(cls, C, H, monkeypatch):
 @pytest.mark.parametrize("N,C,H,W", [(3, 8, 8, 8), (2, 16, 14, 14), (5, 12, 7, 7), (1, 4, 3, 5), (3, 11, 7, 7), (1, 3, 7, 7)])
 def test_radix_tail_channel_major_kernels(N, C, H, W, dtype, pack7, request):
     """cot_radix_gap_t / _mix_logits / _mix_backward_reduce / _mix_backward_apply against the torch formulas"""
-    assert _EMUL.cot_set_tuning(50, pack7) == 0  # (7 x 7 bf16 planes: eight per wave, 7 lanes x 7 elements, or one wave each)
-    request.addfinalizer(lambda: _EMUL.cot_set_tuning(50, 1))
+    assert _EMUL.cot_set_tuning(T.RADIX_PACK7, pack7) == 0  # (7 x 7 bf16 planes: eight per wave, 7 lanes x 7 elements, or one wave each)
     torch.manual_seed(9)
     HW = H * W
     dt = _lib.dtype_code(dtype)
@@ -1708,7 +1674,7 @@ def test_radix_tail_channel_major_kernels(N, C, H, W, dtype, pack7, request):
 @pytest.mark.parametrize("N,C,H,W", [(3, 8, 8, 8), (4, 16, 14, 14), (5, 12, 7, 7), (2, 4, 3, 5), (3, 11, 7, 7), (9, 3, 7, 7), (2, 8, 24, 24)])
 def test_radix_tail_bn_fused_kernels(N, C, H, W, dtype, lay_k, sums):
     """BatchNorm + SiLU folded into the radix tail (cot_radix_*_bn): forward bit-identical to the unfused kernels, backward against autograd"""
-    _EMUL.cot_set_tuning(12, 1)  # the unfused composition on the folded streaming kernels (the library's default form)
+    _EMUL.cot_set_tuning(T.BN_FOLD, 1)  # the unfused composition on the folded streaming kernels (the library's default form)
     same = bn_tail_case(_EMUL, N, C, H, W, dtype, lay_k, bool(sums))
     # True: the bit-for-bit branch of the forward comparison ran (7 x 7 bf16 planes: the statistics pass reads 7 elements per lane where
     # the unfused streaming kernel reads one -- another summation order)
@@ -1738,8 +1704,7 @@ def test_group_norm9_kernels(N, G, H, W, pack, request):
     """cot_group_norm9_forward / _backward against torch's GroupNorm in fp32 on the same bf16-rounded operands; planes of at most
     256 pixels with several (image, group) pairs per wave (tuning key 49, default) and with one each -- group counts that fill
     the last wave and that do not"""
-    assert _EMUL.cot_set_tuning(49, pack) == 0
-    request.addfinalizer(lambda: _EMUL.cot_set_tuning(49, 1))
+    assert _EMUL.cot_set_tuning(T.GN9_PACK, pack) == 0
     torch.manual_seed(13)
     C, HW = 9 * G, H * W
     dt = _lib.dtype_code(torch.bfloat16)
@@ -2109,7 +2074,7 @@ def test_whole_cotnet50_forward_backward_with_every_opt_in_on_emulated_kernels(m
 
 
 def test_whole_model_with_folded_batchnorm_finalize(monkeypatch):
-    """cot_set_tuning(12, 1) (BatchNorm finalize folded into the apply kernels) inside the single-node Bottleneck: same
+    """cot_set_tuning(T.BN_FOLD, 1) (BatchNorm finalize folded into the apply kernels) inside the single-node Bottleneck: same
     numbers as with the separate finalize launches"""
     import copy
     import cotnet_amd.aggregation_zeropad as az
@@ -2127,7 +2092,7 @@ def test_whole_model_with_folded_batchnorm_finalize(monkeypatch):
     for fold in (0, 1):
         for cache in (clf._SIZES, clf._MASKS, clf._BSIZES):
             cache.clear()
-        assert _EMUL.cot_set_tuning(12, fold) == 0
+        assert _EMUL.cot_set_tuning(T.BN_FOLD, fold) == 0
         b = copy.deepcopy(blk)
         xi = x.clone().requires_grad_(True)
         y = b(xi)
@@ -2155,8 +2120,8 @@ def test_no_kernel_touches_memory_past_its_tensors():
 @pytest.mark.parametrize("N,Ci,Co,H,W", [(2, 64, 144, 16, 24), (1, 72, 80, 7, 7), (1, 200, 64, 14, 14)])
 def test_conv1x1_with_64_rows_per_wave(N, Ci, Co, H, W):
     """the 64-output-channels-per-wave variants (picked automatically only for launches with thousands of waves) forced
-    through cot_set_tuning(10, 4)"""
-    assert _EMUL.cot_set_tuning(10, 4) == 0
+    through cot_set_tuning(T.C1_ROWS_PER_WAVE, 4)"""
+    assert _EMUL.cot_set_tuning(T.C1_ROWS_PER_WAVE, 4) == 0
     torch.manual_seed(17)
     HW = H * W
     x = torch.randn(N, Ci, H, W).bfloat16()
@@ -2178,8 +2143,7 @@ def test_conv1x1_with_64_rows_per_wave(N, Ci, Co, H, W):
                                      (1, 40, 14, 14), (3, 11, 7, 7), (1, 3, 56, 56)])
 @pytest.mark.parametrize("tile", [1, 0])
 def test_pooling_kernels_match_torch(N, C, H, W, dtype, tile, request):
-    assert _EMUL.cot_set_tuning(27, tile) == 0  # (1: whole planes through LDS where eligible; 0: one lane per pixel)
-    request.addfinalizer(lambda: _EMUL.cot_set_tuning(27, 1))
+    assert _EMUL.cot_set_tuning(T.POOL_TILE, tile) == 0  # (1: whole planes through LDS where eligible; 0: one lane per pixel)
     _pooling_kernels_match_torch(N, C, H, W, dtype)
 
 
@@ -2211,9 +2175,8 @@ def test_pooling_plane_tile_form_is_bit_identical(N, C, H, W):
     Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
     gy = torch.randn(N, C, Ho, Wo).bfloat16()
     res = []
-    try:
-        for tile in (1, 0):
-            assert _EMUL.cot_set_tuning(27, tile) == 0
+    for tile in (1, 0):
+        with _lib.tuned(_EMUL, POOL_TILE=tile):
             y, ya = torch.full_like(gy, float("nan")), torch.full_like(gy, float("nan"))
             gx, gxa = torch.full_like(x, float("nan")), torch.full_like(x, float("nan"))
             taps = torch.full((N, C, Ho, Wo), 255, dtype=torch.uint8)
@@ -2222,8 +2185,6 @@ def test_pooling_plane_tile_form_is_bit_identical(N, C, H, W):
             assert _EMUL.cot_avgpool3x3s2_forward(P(x), P(ya), N * C, H, W, dt, None) == 0
             assert _EMUL.cot_avgpool3x3s2_backward(P(gy), P(gxa), N * C, H, W, dt, None) == 0
             res.append((y, taps, gx, ya, gxa))
-    finally:
-        assert _EMUL.cot_set_tuning(27, 1) == 0
     for a, b in zip(*res):
         assert torch.equal(a, b)
 
@@ -2340,20 +2301,16 @@ def test_stem_convolution_kernels(N, H, W):
     xi[:, 1, H // 2, W // 2] = float("inf")
     outs = []
     for lds in (1, 0):
-        assert _EMUL.cot_set_tuning(41, lds) == 0
-        try:
+        with _lib.tuned(_EMUL, STEM_LDS=lds):
             ya, yb = torch.full_like(y, float("nan")), torch.full_like(y, float("nan"))
             assert _EMUL.cot_stem7x7s2_forward(P(x), P(w), P(ya), N, H, W, dt, None) == 0
             assert _EMUL.cot_stem7x7s2_forward(P(xi), P(w), P(yb), N, H, W, dt, None) == 0
             buf = ctypes.create_string_buffer(2048)
             _EMUL.cot_launch_log(buf, 2048)
-            assert _EMUL.cot_set_tuning(26, 1) == 0
-            _EMUL.cot_stem7x7s2_forward(P(x), P(w), P(ya), N, H, W, dt, None)
-            assert _EMUL.cot_set_tuning(26, 0) == 0
+            with _lib.tuned(_EMUL, DRY_RUN=1):
+                _EMUL.cot_stem7x7s2_forward(P(x), P(w), P(ya), N, H, W, dt, None)
             _EMUL.cot_launch_log(buf, 2048)
             assert ("stem7x7_fwd_lds" if lds else "stem7x7_fwd_mfma") in buf.value.decode(), buf.value
-        finally:
-            assert _EMUL.cot_set_tuning(26, 0) == 0 and _EMUL.cot_set_tuning(41, 1) == 0
         outs.append((ya, yb))
     assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][0], y)
     fin = torch.isfinite(outs[1][1].float())
@@ -2365,21 +2322,15 @@ def test_stem_convolution_kernels(N, H, W):
     assert _EMUL.cot_stem7x7s2_backward_weight(P(gy), P(x), P(gw), P(ws), N, H, W, dt, None) == 0
     assert (gw.float() - wf.grad).abs().max() <= 1e-2 * wf.grad.abs().max() + 1e-2
     # the gather form (tuning key 41 = 0; its own slice count and workspace) agrees to the rounding of the slices' fp32 sums
-    assert _EMUL.cot_set_tuning(41, 0) == 0
-    try:
+    with _lib.tuned(_EMUL, STEM_LDS=0):
         ws0 = torch.empty(_EMUL.cot_stem7x7s2_workspace(N, H, W), dtype=torch.uint8)
         gw0 = torch.full_like(w, float("nan"))
         assert _EMUL.cot_stem7x7s2_backward_weight(P(gy), P(x), P(gw0), P(ws0), N, H, W, dt, None) == 0
-    finally:
-        assert _EMUL.cot_set_tuning(41, 1) == 0
     assert (gw.float() - gw0.float()).abs().max() <= 4e-3 * wf.grad.abs().max() + 1e-3
     buf = ctypes.create_string_buffer(2048)
     _EMUL.cot_launch_log(buf, 2048)
-    assert _EMUL.cot_set_tuning(26, 1) == 0
-    try:
+    with _lib.tuned(_EMUL, DRY_RUN=1):
         _EMUL.cot_stem7x7s2_backward_weight(P(gy), P(x), P(gw0), P(ws), N, H, W, dt, None)
-    finally:
-        assert _EMUL.cot_set_tuning(26, 0) == 0
     _EMUL.cot_launch_log(buf, 2048)
     staged = W % 8 == 0 and (2 * Wo) % 32 == 0 and Ho % 2 == 0
     assert ("stem7x7_wgrad_lds" if staged else "stem7x7_wgrad_mfma") in buf.value.decode(), buf.value
@@ -2556,7 +2507,7 @@ def test_plans_of_the_single_node_layers_do_not_travel_with_the_module(monkeypat
 @pytest.mark.parametrize("fold", [0, 1])
 def test_bn_relu_backward_without_the_saved_output(fold):
     """cot_bn_act_backward with y == NULL for ReLU (no residual): the mask is recomputed from x -- same gradients as with y"""
-    assert _EMUL.cot_set_tuning(12, fold) == 0
+    assert _EMUL.cot_set_tuning(T.BN_FOLD, fold) == 0
     torch.manual_seed(23)
     N, C, H, W = 4, 8, 7, 7
     dt = _lib.dtype_code(torch.bfloat16)
@@ -2631,18 +2582,17 @@ def test_results_do_not_depend_on_the_lane_schedule(order):
         out.extend(run(x, w, g, 3, 1, 1, 1, 0, True)[:3])
         # fused BatchNorm (block reductions through LDS), both finalize modes
         for fold in (0, 1):
-            _EMUL.cot_set_tuning(12, fold)
-            xb, dy = torch.randn(5, 16, 14, 14).bfloat16(), torch.randn(5, 16, 14, 14).bfloat16()
-            ga, be = torch.rand(16) + 0.5, torch.randn(16)
-            mean, rstd, dg, db = (torch.empty(16) for _ in range(4))
-            ws = torch.empty(_EMUL.cot_bn_act_workspace(5, 16))
-            y, dx = torch.empty_like(xb), torch.empty_like(xb)
-            assert _EMUL.cot_bn_act_forward(P(xb), None, P(y), P(ga), P(be), P(mean), P(rstd), None, None, None, P(ws), 5, 16,
-                                            196, 1e-5, 0.1, 2, dtb, None) == 0
-            assert _EMUL.cot_bn_act_backward(P(dy), P(xb), None, P(dx), None, P(ga), P(be), P(mean), P(rstd), P(dg), P(db),
-                                             P(ws), 5, 16, 196, 2, dtb, None) == 0
-            out.extend([y, dx, dg.clone(), db.clone()])
-        _EMUL.cot_set_tuning(12, 0)
+            with _lib.tuned(_EMUL, BN_FOLD=fold):
+                xb, dy = torch.randn(5, 16, 14, 14).bfloat16(), torch.randn(5, 16, 14, 14).bfloat16()
+                ga, be = torch.rand(16) + 0.5, torch.randn(16)
+                mean, rstd, dg, db = (torch.empty(16) for _ in range(4))
+                ws = torch.empty(_EMUL.cot_bn_act_workspace(5, 16))
+                y, dx = torch.empty_like(xb), torch.empty_like(xb)
+                assert _EMUL.cot_bn_act_forward(P(xb), None, P(y), P(ga), P(be), P(mean), P(rstd), None, None, None, P(ws), 5, 16,
+                                                196, 1e-5, 0.1, 2, dtb, None) == 0
+                assert _EMUL.cot_bn_act_backward(P(dy), P(xb), None, P(dx), None, P(ga), P(be), P(mean), P(rstd), P(dg), P(db),
+                                                 P(ws), 5, 16, 196, 2, dtb, None) == 0
+                out.extend([y, dx, dg.clone(), db.clone()])
         # GroupNorm9 (LDS block sums), two workgroup sizes
         for H in (8, 40):
             xg, dyg = torch.randn(2, 18, H, H).bfloat16(), torch.randn(2, 18, H, H).bfloat16()
@@ -2723,12 +2673,9 @@ def test_general_grouped_conv1x1_kernels(N, Ci, Co, G, H, W, bias, dtype):
     tuned = dtype == torch.bfloat16 and G > 1 and (Ci // G) % 8 == 0 and (Co // G) % 8 == 0  # (depth % 32 != 0: the kernels' KT form, round 6)
     buf = ctypes.create_string_buffer(1 << 14)
     _EMUL.cot_launch_log(buf, len(buf))
-    assert _EMUL.cot_set_tuning(26, 1) == 0  # dry run: which kernels would this call launch?
-    try:
+    with _lib.tuned(_EMUL, DRY_RUN=1):  # dry run: which kernels would this call launch?
         assert _EMUL.cot_conv1x1g_forward(P(x), P(w), P(b) if bias else None, P(y), N, Ci, Co, G, HW, dt, None) == 0
         _EMUL.cot_launch_log(buf, len(buf))
-    finally:
-        assert _EMUL.cot_set_tuning(26, 0) == 0
     log = buf.value.decode()
     assert (log.count("conv1x1_lds_fwd2") == G) if tuned else ("convg_fwd_kernel" in log), log
     gx = torch.full_like(x, float("nan"))
@@ -2925,12 +2872,9 @@ def test_blurpool_kernels_match_the_reference_formula(N, C, H, W, dtype):
     assert _EMUL.cot_blurpool3x3s2_forward(P(x), P(y), N * C, 1, W, dt, None) == -2   # reflection needs two rows
     # the row-block form (even W: a lane owns 1 / 2 / 4 windows of a row) adds in the order of the per-pixel form: same bits
     y1, gx1 = torch.full_like(y, float("nan")), torch.full_like(gx, float("nan"))
-    assert _EMUL.cot_set_tuning(27, 0) == 0
-    try:
+    with _lib.tuned(_EMUL, POOL_TILE=0):
         assert _EMUL.cot_blurpool3x3s2_forward(P(x), P(y1), N * C, H, W, dt, None) == 0
         assert _EMUL.cot_blurpool3x3s2_backward(P(gy), P(gx1), N * C, H, W, dt, None) == 0
-    finally:
-        assert _EMUL.cot_set_tuning(27, 1) == 0
     assert torch.equal(y1, y) and torch.equal(gx1, gx)
 
 
@@ -3049,7 +2993,7 @@ def test_split_attn_radix1_and_blurpool_modules_on_emulated_kernels(monkeypatch)
 def test_conv1x1_lds_data_gradient_reads_the_weight_in_place(N, Ci, Co, H, W, c1, lds_variant):
     """cot_conv1x1_backward_data on the LDS kernels with the [Co][Ci] weight tensor read in place as the transposed operand
     (WT kernels: transposing LDS reads, chunk-permuted rows) must equal -- bit for bit: same products, same order -- the
-    form that multiplies a transposed copy (cot_set_tuning(17) bit 5), and both the fp32 reference"""
+    form that multiplies a transposed copy (cot_set_tuning(CONV_LDS_BITS) bit 5), and both the fp32 reference"""
     torch.manual_seed(17)
     waves4 = lds_variant
     HW, dt = H * W, _lib.dtype_code(torch.bfloat16)
@@ -3059,7 +3003,7 @@ def test_conv1x1_lds_data_gradient_reads_the_weight_in_place(N, Ci, Co, H, W, c1
     ws = torch.full((_EMUL.cot_conv1x1_workspace(N, Ci, Co, HW, 0),), 0x7f, dtype=torch.uint8)
     outs = []
     for copy_form in (0, 1):
-        assert _EMUL.cot_set_tuning(17, waves4 | (32 if copy_form else 0)) == 0
+        assert _EMUL.cot_set_tuning(T.CONV_LDS_BITS, waves4 | (32 if copy_form else 0)) == 0
         k1 = c1 if c1 else Ci
         g1 = torch.full((N, k1, H, W), float("nan")).bfloat16()
         g2 = torch.full((N, Ci - k1, H, W), float("nan")).bfloat16() if c1 else None
@@ -3074,7 +3018,6 @@ def test_conv1x1_lds_data_gradient_reads_the_weight_in_place(N, Ci, Co, H, W, c1
         assert torch.allclose(g.float(), 2 * ref, atol=8e-2, rtol=3e-2)
         outs.append(g.clone())
     assert torch.equal(outs[0], outs[1])
-    assert _EMUL.cot_set_tuning(17, 0) == 0
 
 
 @pytest.mark.parametrize("Ci,Co,NB,bias", [
@@ -3088,7 +3031,7 @@ def test_conv1x1_lds_data_gradient_reads_the_weight_in_place(N, Ci, Co, H, W, c1
 def test_one_image_convolutions_of_the_se_branch(Ci, Co, NB, bias):
     """csrc/conv_tiny.hip behind cot_conv1x1_* for ONE image of <= 256 pixels (one wave per 16 x 16 output tile, no LDS):
     forward, data gradient (+ accumulate), weight / bias gradient against fp32 on the same bf16-rounded operands, and against
-    the tiled kernels (cot_set_tuning(22, 0))"""
+    the tiled kernels (cot_set_tuning(T.CONV_TINY, 0))"""
     torch.manual_seed(Ci + NB)
     dt = _lib.dtype_code(torch.bfloat16)
     x = torch.randn(1, Ci, NB).bfloat16()
@@ -3102,7 +3045,7 @@ def test_one_image_convolutions_of_the_se_branch(Ci, Co, NB, bias):
     ws = torch.full((_EMUL.cot_conv1x1_workspace(1, Ci, Co, NB, 1 if bias else 0),), 0x7f, dtype=torch.uint8)
     res = []
     for tiny in (1, 0):
-        assert _EMUL.cot_set_tuning(22, tiny) == 0
+        assert _EMUL.cot_set_tuning(T.CONV_TINY, tiny) == 0
         y = torch.full((1, Co, NB), float("nan")).bfloat16()
         assert _EMUL.cot_conv1x1_forward(P(x), None, Ci, P(w), P(b) if bias else None, P(y), 1, Ci, Co, NB, dt, None) == 0
         gx = torch.full((1, Ci, NB), float("nan")).bfloat16()
@@ -3121,7 +3064,6 @@ def test_one_image_convolutions_of_the_se_branch(Ci, Co, NB, bias):
         if bias:
             assert (gb.float() - gbr).abs().max() <= 1e-2 * gbr.abs().max() + 1e-2
         res.append((y.clone(), gw.clone()))
-    assert _EMUL.cot_set_tuning(22, 1) == 0
     assert torch.allclose(res[0][0].float(), res[1][0].float(), atol=3e-2, rtol=2e-2)
 
 

@@ -17,9 +17,10 @@ pytestmark = pytest.mark.skipif(_EMUL is None, reason="host emulation build unav
 
 @pytest.fixture(autouse=True)
 def _knobs():
-    _EMUL.cot_set_tuning(18, 256)
-    _EMUL.cot_set_tuning(21, 1)  # channel-resident BatchNorm kernels on
-    yield
+    """the channel-resident BatchNorm kernels on, the fp64 path up to 256 samples per channel; every other key at the library's default"""
+    with _lib.tuned(_EMUL, BN_SMALL_M=256, BN_CHAN=1):
+        yield
+    _lib.reset_tuning(_EMUL)
 
 
 @pytest.mark.parametrize("HW", [196, 49, 64])

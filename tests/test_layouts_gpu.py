@@ -49,12 +49,11 @@ def test_batchnorm_statistics_from_the_convolution_epilogue(Ci, Co, HW, act, res
 @pytest.mark.parametrize("N,Ci,Co,HW,split", [(1, 1024, 256, 15680, 0), (1, 256, 1024, 15680, 0), (1, 512, 128, 15680, 256), (1, 2048, 512, 3920, 0),
                                               (1, 512, 2048, 3920, 0), (80, 512, 128, 784, 0), (80, 64, 256, 3136, 0), (80, 256, 64, 3136, 0),
                                               (1, 128, 288, 15680, 0)])
-def test_conv1x1_lds_layouts_do_not_change_the_result(N, Ci, Co, HW, split, request):
-    """cot_set_tuning(48): the bank-conflict-free LDS layouts of the 1x1 forward / data-gradient kernel (X stage of the 128-pixel tiles
+def test_conv1x1_lds_layouts_do_not_change_the_result(N, Ci, Co, HW, split):
+    """cot_set_tuning(CONV_BIG_XSWZ): the bank-conflict-free LDS layouts of the 1x1 forward / data-gradient kernel (X stage of the 128-pixel tiles
     permuted per channel row; W and transposed-W chunk permutations) against the layouts of rounds 2-4 on the MI355X --
     the same bits, on the channel-major deep layers and on NCHW layers of the benchmark step"""
     L, st, BF = _lib.lib(), _st(), _lib.COT_BF16
-    request.addfinalizer(lambda: L.cot_set_tuning(48, 7))
     torch.manual_seed(5)
     P = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
     x1 = torch.randn(N, split or Ci, HW, device="cuda").bfloat16()
@@ -64,14 +63,14 @@ def test_conv1x1_lds_layouts_do_not_change_the_result(N, Ci, Co, HW, split, requ
     ws = torch.empty(int(L.cot_conv1x1_workspace(N, Ci, Co, HW, 0)), dtype=torch.uint8, device="cuda")
     outs = []
     for key in (7, 0):
-        assert L.cot_set_tuning(48, key) == 0
-        y = torch.full((N, Co, HW), float("nan"), device="cuda").bfloat16()
-        g1 = torch.full_like(x1, float("nan"))
-        g2 = torch.full_like(x2, float("nan")) if split else None
-        assert L.cot_conv1x1_forward(P(x1), P(x2), split or Ci, P(w), None, P(y), N, Ci, Co, HW, BF, st) == 0, L.cot_last_error()
-        assert L.cot_conv1x1_backward_data(P(gy), P(w), P(g1), P(g2), split or Ci, 0, P(ws), N, Ci, Co, HW, BF, st) == 0, L.cot_last_error()
-        torch.cuda.synchronize()
-        outs.append((y, g1, g2))
+        with _lib.tuned(L, CONV_BIG_XSWZ=key):
+            y = torch.full((N, Co, HW), float("nan"), device="cuda").bfloat16()
+            g1 = torch.full_like(x1, float("nan"))
+            g2 = torch.full_like(x2, float("nan")) if split else None
+            assert L.cot_conv1x1_forward(P(x1), P(x2), split or Ci, P(w), None, P(y), N, Ci, Co, HW, BF, st) == 0, L.cot_last_error()
+            assert L.cot_conv1x1_backward_data(P(gy), P(w), P(g1), P(g2), split or Ci, 0, P(ws), N, Ci, Co, HW, BF, st) == 0, L.cot_last_error()
+            torch.cuda.synchronize()
+            outs.append((y, g1, g2))
     assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
     if split:
         assert torch.equal(outs[0][2], outs[1][2])

@@ -3,7 +3,7 @@
 The host side of the training step (cot_layer_fused.py, cot_block_cm.py, cot_block_sa.py) is a long sequence of launches whose
 correctness rests on details no numerical test isolates: which buffer a gradient is accumulated into, which one is reused, which
 launches go to the weight-gradient side stream.  So the sequence is pinned: every node kind runs forward + backward on CPU tensors
-against the REAL library in dry-run mode (cot_set_tuning(26, 1): no launch, no HIP call -- as tests/test_dispatch_table.py does; the
+against the REAL library in dry-run mode (cot_set_tuning(COT_TUNE_DRY_RUN, 1): no launch, no HIP call -- as tests/test_dispatch_table.py does; the
 outputs are uninitialised memory, which the sequence does not depend on), a recorder in front of the library handle notes every call,
 and the result is compared with tests/golden/node_call_trace.json: per case the number of calls and the SHA-256 of its lines, and for
 one case of each node kind (FULL) the lines themselves, to be read.  `python tests/test_node_call_trace.py CASE` prints a trace; when a
@@ -293,27 +293,26 @@ def trace(name, sw=None, val=None):
     caches = [getattr(clf, n) for n in ("_SIZES", "_MASKS", "_BSIZES", "_CM_SIZES", "_CM_OK", "_SASIZES", "_RES_FOLD_OK", "_GN_OK",
                                         "_ROWSTATS_OK", "_EPI_OK", "_MASK_BYTES")]
     mp = pytest.MonkeyPatch()
-    assert raw.cot_set_tuning(26, 1) == 0  # (also empties every registered shape cache)
-    try:
-        for c in caches:
-            c.clear()
-        pinned = _install(mp, rec)
-        mp.setattr(clf, "ENABLED", True)
-        for s, v in (("SIDE_WGRAD", True), ("LAZY_WGRAD", True), ("BN_TAIL", True), ("GN_FUSED", True), ("RES_FOLD", False),
-                     ("AGG_ROWSTATS", False), ("BN_EPILOGUE", False), ("RELU_MASK", True), ("CM_LAYOUT", True), ("CM_OPENING", True),
-                     ("GX_SLABS", True), ("MERGE12", True), ("PREPACK", True)):
-            mp.setattr(clf, s, v)
-        if sw is not None:
-            mp.setattr(clf, sw, val)
-        torch.manual_seed(0)
-        (COT_CASES.get(name) or SA_CASES[name])(clf)
-        assert pinned
-    finally:
-        mp.undo()
-        clf._SIDE_PENDING.pop(None, None)
-        for c in caches:
-            c.clear()
-        assert raw.cot_set_tuning(26, 0) == 0
+    with _lib.tuned(raw, DRY_RUN=1):  # (also empties every registered shape cache)
+        try:
+            for c in caches:
+                c.clear()
+            pinned = _install(mp, rec)
+            mp.setattr(clf, "ENABLED", True)
+            for s, v in (("SIDE_WGRAD", True), ("LAZY_WGRAD", True), ("BN_TAIL", True), ("GN_FUSED", True), ("RES_FOLD", False),
+                         ("AGG_ROWSTATS", False), ("BN_EPILOGUE", False), ("RELU_MASK", True), ("CM_LAYOUT", True), ("CM_OPENING", True),
+                         ("GX_SLABS", True), ("MERGE12", True), ("PREPACK", True)):
+                mp.setattr(clf, s, v)
+            if sw is not None:
+                mp.setattr(clf, sw, val)
+            torch.manual_seed(0)
+            (COT_CASES.get(name) or SA_CASES[name])(clf)
+            assert pinned
+        finally:
+            mp.undo()
+            clf._SIDE_PENDING.pop(None, None)
+            for c in caches:
+                c.clear()
     return rec.calls
 
 

@@ -51,9 +51,8 @@ def _randn(*shape, seed=0, scale=1.0):
 
 @pytest.fixture(autouse=True)
 def _bench_tuning():
-    L = _lib.lib()
-    assert L.cot_set_tuning(12, 1) == 0  # (bench.py's `new` set: finalize folded into the apply kernels)
-    yield
+    with _lib.tuned(_lib.lib(), BN_FOLD=1):  # (bench.py's `new` set: finalize folded into the apply kernels)
+        yield
 
 
 # bn3 of every stage of CoTNet-50 at B = 80: (channels, plane)
