@@ -10,6 +10,7 @@ Public surface mirrors the reference (JDAI-CV/CoTNet):
     loss.cross_entropy                   -> cotnet_amd.loss                 (soft_target_cross_entropy, LabelSmoothingCrossEntropy)
     evaler.evaler / utils.meters         -> cotnet_amd.evaler               (Evaler, DeviceTestMeter, accuracy: scored on the device)
     models.factory / models.registry     -> cotnet_amd.registry             (create_model, register_model)
+    models.features / features_only=True -> cotnet_amd.features             (FeatureInfo, FeatureListNet, FeatureDictNet: on the fused walker)
     utils.checkpoint_saver / models.helpers.resume_checkpoint -> cotnet_amd.checkpoint (CheckpointSaver, resume_checkpoint)
     optim.optim_factory / optim.adamw / optim.lookahead -> cotnet_amd.optim_factory (create_optimizer -> FlatSGD, FlatAdam, FlatAdamW;
                                             split_opt_name: `lookahead_*` -> the keywords lookahead_k, lookahead_alpha)
@@ -35,6 +36,7 @@ from .mixup import DeviceMixup, PerSampleMixup, create_mixup  # noqa: F401
 from .evaler import DeviceTestMeter, Evaler, accuracy  # noqa: F401
 from .registry import create_model, list_models, load_checkpoint, register_model  # noqa: F401
 from .resnet import ResNet  # noqa: F401
+from .features import FeatureDictNet, FeatureInfo, FeatureListNet  # noqa: F401
 from .checkpoint import CheckpointSaver, resume_checkpoint  # noqa: F401
 from .flat_adamw import FlatAdam, FlatAdamW  # noqa: F401
 from .optim_factory import create_optimizer, split_opt_name  # noqa: F401

@@ -17,7 +17,7 @@ from .fused_bn import fused_bn_act
 from .head_fused import head
 from .layers import BlurPool2d, SplitAttnConv2d, create_classifier, get_act_layer
 from .registry import build_model_with_cfg, register_model
-from .resnet import init_weights, make_blocks, make_stem, stem_forward
+from .resnet import init_weights, make_blocks, make_stem, walk_features
 
 default_cfgs = {
     "cot_basic": _cfg(url=""),
@@ -157,9 +157,11 @@ class CoTHybridNet(nn.Module):
         self.num_classes = num_classes
         self.global_pool, self.fc = create_classifier(self.num_features, self.num_classes, pool_type=global_pool)
 
+    # no max-pool (ref :431: the class has no such child); its blocks draw their own stochastic depth and none is channel-major
+    walk_args = dict(drop_path_plan=False, layout_stages=())
+
     def forward_features(self, x):
-        x = stem_forward(self.conv1, self.bn1, self.act1, x)  # no max-pool (ref :431)
-        return self.layer4(self.layer3(self.layer2(self.layer1(x))))
+        return walk_features(self, x, **self.walk_args)
 
     def forward(self, x):
         x = self.forward_features(x)

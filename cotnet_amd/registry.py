@@ -38,16 +38,34 @@ def list_models(filter="", module=""):
     return sorted(names)
 
 
-def build_model_with_cfg(model_cls, variant, pretrained, default_cfg, **kwargs):
+def build_model_with_cfg(model_cls, variant, pretrained, default_cfg, feature_cfg=None, **kwargs):
+    """reference helpers.py:311-357.  `features_only=True` wraps the built model in a feature backbone
+    (cotnet_amd/features.py): `feature_cfg` holds the wrapper's keywords, `out_indices` defaults to (0, 1, 2, 3, 4) and a keyword
+    `out_indices` overrides it, `feature_cfg['feature_cls']` names another wrapper class."""
     if pretrained:
         # the reference's default_cfgs carry empty urls for every CoT model (cotnet.py:21-34): there is
         # nothing to download; weights come through `checkpoint_path`.
         raise RuntimeError(f"no pretrained url for '{variant}'; pass checkpoint_path= to create_model")
-    for unsupported in ("features_only", "pruned", "out_indices"):
-        if kwargs.pop(unsupported, None):
-            raise NotImplementedError(f"{unsupported} is outside the CoT hot-path scope")
+    if kwargs.pop("pruned", None):
+        raise NotImplementedError("pruned is outside the CoT hot-path scope")
+    features = bool(kwargs.pop("features_only", False))
+    feature_cfg = dict(feature_cfg or {})
+    if features:
+        feature_cfg.setdefault("out_indices", (0, 1, 2, 3, 4))
+        if "out_indices" in kwargs:
+            feature_cfg["out_indices"] = kwargs.pop("out_indices")
     model = model_cls(**kwargs)
     model.default_cfg = deepcopy(default_cfg)
+    if features:
+        from . import features as F
+        feature_cls = feature_cfg.pop("feature_cls", F.FeatureListNet)
+        if isinstance(feature_cls, str):
+            if "hook" in feature_cls.lower():
+                raise NotImplementedError("feature_cls='hook' (FeatureHookNet) is not provided: a hooked tensor's lifetime is "
+                                          "unchecked against the nodes' buffers; use FeatureListNet / FeatureDictNet")
+            assert False, f"Unknown feature class {feature_cls}"
+        model = feature_cls(model, **feature_cfg)
+        model.default_cfg = F.default_cfg_for_features(default_cfg)
     return model
 
 
@@ -71,7 +89,14 @@ def load_state_dict(checkpoint_path, use_ema=False):
 def load_checkpoint(model, checkpoint_path, use_ema=False, strict=True):
     """weights only, into the model's own tensors.  After a FlatSGD has been built on the model, load through the optimizer
     (cotnet_amd.checkpoint.resume_checkpoint, FlatSGD.load_model_state_dict): it steps on fp32 masters it took when it was built, and
-    the next step() would write them back over what was loaded here."""
+    the next step() would write them back over what was loaded here.
+
+    Into a feature backbone (create_model(..., features_only=True)) a CLASSIFIER checkpoint loads: keys of the modules the wrapper
+    dropped (fc.*, a dropped layerN.*) are ignored, any other unexpected key and any missing key raise.  (The reference's strict load
+    would reject its own classifier checkpoints there.)"""
+    if strict and hasattr(model, "dropped_modules"):
+        from .features import load_classifier_state_dict
+        return load_classifier_state_dict(model, load_state_dict(checkpoint_path, use_ema))
     return model.load_state_dict(load_state_dict(checkpoint_path, use_ema), strict=strict)
 
 

@@ -140,6 +140,36 @@ def _deep_stem_conv(conv, x):
     return conv(x)
 
 
+def walk_features(net, x, tap=None, drop_path_plan=True, layout_stages=("layer3", "layer4")):
+    """The backbone's call sequence, stated once: stem, [max-pool,] layer1..4 (resnet.py:593-603; cotnet_hybrid.py:431-436).
+    `ResNet.forward_features`, `CoTHybridNet.forward_features` and the feature wrappers (cotnet_amd/features.py) all run THIS, so
+    the classifier and the backbone issue the same launches.  `net` owns conv1 / bn1 / act1 and, as direct children, whatever of
+    maxpool, layer1..4 it kept (a wrapper holds only the stages its taps need: the walk ends behind the last one it finds);
+    `tap(name, x)` is called behind every named module.  drop_path_plan: one vectorised stochastic-depth draw per step for the
+    single-node blocks; layout_stages: the stages whose blocks may hand a channel-major tensor to their successor --
+    the last block of a stage always writes NCHW, so what a stage returns, and what `tap` sees, is NCHW-contiguous."""
+    kept = net._modules
+    if drop_path_plan:
+        cot_layer_fused.prepare_drop_path(net, x)  # (single-node blocks: one vectorised stochastic-depth draw per step)
+    x = stem_forward(net.conv1, net.bn1, net.act1, x)  # stem BN + ReLU in one pass over 112x112
+    if tap is not None:
+        tap("act1", x)
+    if "maxpool" in kept:
+        x = pool(net.maxpool, x)
+        if tap is not None:
+            tap("maxpool", x)
+    for name in ("layer1", "layer2", "layer3", "layer4"):
+        if name not in kept:
+            break
+        stage = kept[name]
+        if name in layout_stages:  # (which blocks hand a channel-major tensor to their successor: DESIGN 5.8)
+            cot_layer_fused.plan_stage_layouts(stage)
+        x = stage(x)
+        if tap is not None:
+            tap(name, x)
+    return x
+
+
 def init_weights(model, zero_init_last_bn=True):
     """kaiming-normal(fan_out, relu) on every Conv2d, BN gamma=1 beta=0, then bn3.weight=0 per block
     (resnet.py:575-584).  GroupNorm / Linear keep torch defaults, as in the reference."""
@@ -197,14 +227,10 @@ class ResNet(nn.Module):
         self.num_classes = num_classes
         self.global_pool, self.fc = create_classifier(self.num_features, self.num_classes, pool_type=global_pool)
 
+    walk_args = {}  # how walk_features runs this class (a feature wrapper takes them over: cotnet_amd/features.py)
+
     def forward_features(self, x):
-        cot_layer_fused.prepare_drop_path(self, x)  # (single-node blocks: one vectorised stochastic-depth draw per step)
-        x = stem_forward(self.conv1, self.bn1, self.act1, x)  # stem BN + ReLU in one pass over 112x112
-        x = pool(self.maxpool, x)
-        x = self.layer2(self.layer1(x))
-        for stage in (self.layer3, self.layer4):  # (which blocks hand a channel-major tensor to their successor: DESIGN 5.8)
-            cot_layer_fused.plan_stage_layouts(stage)
-        return self.layer4(self.layer3(x))
+        return walk_features(self, x, **self.walk_args)
 
     def forward(self, x):
         x = self.forward_features(x)
